@@ -2,9 +2,14 @@
 """bench.py — headline benchmark of the hot path: geodesic RK (Tsit5) step attempts/s and rays/s on the Kerr–Schild
 4096² screen (BASELINE.json metric / configs[2]), rows sharded over N GPUs of one node with one RCCL gather.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`: one timed step).  --dump-outputs DIR
+writes what the last timed step delivered (dump_outputs).  --full measures and checks everything else as well: the CPU baseline
+(`cpu_baseline`), the `roofline` below, the other entry points and BASELINE configurations (--extras), and the frame checksum
+against the recorded N = 1 frame of the same kernel sources (`frame_checksum_ok`; exit status 2 when it differs).
 
 A "step" of this bench is one full pass of the hot path over the whole screen (every ray integrated to its event and
 coloured, rows — RGB and status bytes — gathered on rank 0).  `value` = Tsit5 step attempts (accepted + rejected, each =
@@ -16,7 +21,7 @@ device (make_canvas fused into the set-up kernel), so nothing crosses PCIe insid
                x the step attempts THIS run counted / the integrate kernels' time THIS run measured with HIP events on the launch stream
     frac     = achieved / 78.6 TF/s  (fp64 vector peak)  — always <= 1
     traffic  = HBM bytes per pass of the whole pipeline (2 x FETCH_SIZE + WRITE_SIZE)
-The counters are read BY THIS RUN on this box (`roofline.counters: "live"`; default run at N = 1): after the timed region one frame of
+The counters are read BY THIS RUN on this GPU (`roofline.counters: "live"`; --full run at N = 1): after the timed region one frame of
 the same workload is run three times under `rocprofv3 --pmc` in child processes — arithmetic counters, FETCH_SIZE, WRITE_SIZE, each
 set in a run of its own, never with a trace (live_counters()).  The committed profile of the same kernel sources
 (profiles/rNN/flops.json, keyed by the sha256 of the device headers + flags, raytracegr.jl_amd/build.py:kernel_source_hash) is
@@ -61,8 +66,14 @@ def parse():
     ap.add_argument("--variant", default="ks_ref0",
                     choices=["ks_ref0", "ks_ref08", "ks_true0", "ks_true08", "ks_true0998", "ks_true0998_disk", "mink"])
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
-    ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="CPU baseline renders a sample x sample screen; -1 = auto (~15 s of CPU work), 0 = off")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure and check everything else: the CPU baseline, the other entry points "
+                         "and BASELINE configurations (--extras), the roofline with live hardware counters, the frame checksum against "
+                         "the recorded N = 1 frame.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one delivered as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="--full: CPU baseline renders a sample x sample screen; -1 = auto (~15 s of CPU work, the --full default), 0 = off")
     ap.add_argument("--rhs", default="closed", choices=["closed", "generic", "user", "user_ks"],
                     help="closed = Kerr-Schild-form contraction (production); generic = reference-style dual-number RHS "
                          "(RTGR_METRIC_GENERIC): its executed flops are the reference formulation's; "
@@ -80,20 +91,20 @@ def parse():
                          "sharded = rtgr_trace_sharded_device_f64: ONE process drives every device of the context, rows "
                          "gathered on device 0 by peer copies — the single-process twin of the torchrun form, same "
                          "frame_checksum.  host / pixels / sharded: one process (--gpus 1 under no launcher)")
-    ap.add_argument("--extras", type=int, default=1,
-                    help="1: after the timed region (rank 0, N = 1, default workload) also time the host and pixels entry "
+    ap.add_argument("--extras", type=int, default=None,
+                    help="--full (default 1 there): after the timed region (rank 0, N = 1, default workload) also time the host and pixels entry "
                          "points and the Kerr a = 0.8 variant, reported in entry_points / variants; 0: skip")
-    ap.add_argument("--live-counters", type=int, default=-1,
-                    help="-1 (default): as --extras.  1: after the timed region (rank 0, N = 1, device entry) run ONE pass of the same workload three times under "
+    ap.add_argument("--live-counters", type=int, default=None,
+                    help="--full: as --extras by default.  1: after the timed region (rank 0, N = 1, device entry) run ONE pass of the same workload three times under "
                          "`rocprofv3 --pmc` in child processes (f64 / f32 FMA-MUL-ADD counters; FETCH_SIZE; WRITE_SIZE — each set in a "
                          "run of its own) and compute the roofline's executed flops and HBM traffic from THIS box's counters; the "
                          "hash-keyed profile of profiles/rNN/flops.json is then the cross-check, and the fallback when a pass fails "
                          "or rocprofv3 is not there.  0: the profile only")
     ap.add_argument("--emit-row-checksums", action="store_true",
-                    help="put the per-image-row checksums of the delivered frame on the line (nj integers): what tools/merge_flops.py "
+                    help="--full: put the per-image-row checksums of the delivered frame on the line (nj integers): what tools/merge_flops.py "
                          "records as the N = 1 reference a mismatch at N > 1 is attributed to rows — and ranks — with")
     ap.add_argument("--checksum-reference", default="",
-                    help="a file holding the JSON line of an N = 1 run with --emit-row-checksums of the SAME configuration: the reference the "
+                    help="--full: a file holding the JSON line of an N = 1 run with --emit-row-checksums of the SAME configuration: the reference the "
                          "delivered frame is checked against instead of the one recorded under profiles/ (rehearsals at sizes that have none)")
     ap.add_argument("--user-sphere", action="store_true",
                     help="example2's small sphere as a USER-DEFINED object of the same geometry (examples/user_objects.py "
@@ -114,7 +125,18 @@ def parse():
                     help="collective backend for N>1: nccl (= RCCL over xGMI, the real thing) or gloo (CPU-staged; lets "
                          "the multi-rank logic be rehearsed with several ranks sharing one GPU)")
     a = ap.parse_args()
-    if a.live_counters < 0:
+    if a.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if not a.full:   # a plain run measures the headline and nothing else: what only --full does cannot be asked for without it
+        asked = [o for o, on in (("--cpu-sample", a.cpu_sample), ("--extras", a.extras), ("--live-counters", (a.live_counters or 0) > 0),
+                                 ("--emit-row-checksums", a.emit_row_checksums), ("--checksum-reference", a.checksum_reference)) if on]
+        if asked:
+            ap.error(f"{', '.join(asked)}: only with --full")
+    if a.dump_outputs and a.no_gather and (a.gpus > 1 or a.exchange_at_n1):
+        ap.error("--dump-outputs: the frame is assembled by the gather (drop --no-gather)")
+    a.cpu_sample = (-1 if a.full else 0) if a.cpu_sample is None else a.cpu_sample
+    a.extras = (1 if a.full else 0) if a.extras is None else a.extras
+    if a.live_counters is None or a.live_counters < 0:
         a.live_counters = 1 if a.extras else 0
     return a
 
@@ -710,7 +732,7 @@ def main():
         #  devices of the context time-share ONE GPU their kernel times overlap: no roofline on such lines.  ADVICE r3.)
         approx_roofline = bool(ctx) and len(ctx_ids) > 1
         k_s = (float(kms[1]) + float(kms[3])) * 1e-3   # seconds in the integrate kernels, all launches of this rank
-        prof, why = load_profile(a)
+        prof, why = load_profile(a) if a.full else (None, "--full only")
         # … and the same two figures counted HERE, on this box, by this run (N = 1, device entry): the profile is then the cross-check
         live, why_not_live = (None, "off")
         if a.live_counters and not multi and a.entry == "device" and not ctx:
@@ -800,8 +822,10 @@ def main():
             "rays_per_s": rays / dt, "rays": rays // a.steps, "step_attempts_per_pass": attempts // a.steps,
             "passes_in_process": a.warmup + extra_warm + a.steps,
             "accepted": acc // a.steps, "rejected": rej // a.steps, "rhs_evals_per_pass": nrhs // a.steps,
-            "device": name, "roofline": roof, "cpu_baseline": cpu,
+            "device": name,
         }
+        if a.full:
+            line["roofline"], line["cpu_baseline"] = roof, cpu
         line.update(extras)
         if multi and not a.no_gather:
             line["gathered_status_not_event"] = int((image["status"] != 0).sum())
@@ -845,17 +869,24 @@ def main():
         if nflight > 1:
             roof["note"] = ("kernel durations overlap between the frames in flight: kernel_ms_per_pass is a sum of stretched "
                             "durations and `achieved` an underestimate; the N = 1 line carries the clean figure")
-        # order-independent bit-level checksum of the delivered frame: equal at every N iff the frames are bit-identical
-        frame = None
-        if a.entry == "device":
-            frame = image["rgb"] if (multi and not a.no_gather) else (outs[0]["rgb"] if ws == 1 else None)
-        elif a.entry == "sharded":
-            frame = host["d_rgb"]
-        elif a.entry == "host":
-            frame = torch.from_numpy(host["rgb"])
-        elif a.entry == "pixels":
-            frame = torch.from_numpy(np.ascontiguousarray(host["px_out"]["rgb"].T))   # planes, like the other entries
-        if frame is not None:
+        # the frame the last timed pass delivered: RGB planes [3, ni * nj] (and the status bytes where the path delivers them)
+        frame, status = None, None
+        if a.full or a.dump_outputs:
+            if a.entry == "device":
+                if multi and not a.no_gather:
+                    frame, status = image["rgb"], image["status"]
+                elif ws == 1:
+                    frame, status = outs[(npass[0] - 1) % nbuf]["rgb"], outs[(npass[0] - 1) % nbuf].get("status")
+            elif a.entry == "sharded":
+                frame, status = host["d_rgb"], host["d_status"]
+            elif a.entry == "host":
+                frame = torch.from_numpy(host["rgb"])
+            elif a.entry == "pixels":
+                frame = torch.from_numpy(np.ascontiguousarray(host["px_out"]["rgb"].T))   # planes, like the other entries
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, frame, status)
+        # --full: order-independent bit-level checksum of the delivered frame: equal at every N iff the frames are bit-identical
+        if frame is not None and a.full:
             bits = frame.contiguous().view(torch.int64 if a.dtype == "f64" else torch.int32).to(torch.int64)
             line["frame_checksum"] = int(bits.sum().item())
             # one checksum per IMAGE ROW (the unit the frame is dealt by): rgb planes are [3, ni * nj] with pixel i + j * ni
@@ -896,6 +927,32 @@ def main():
         print(f"bench.py: the delivered frame differs from the N = 1 frame of the same kernel sources: {line.get('frame_checksum_bad_rows')}",
               file=sys.stderr, flush=True)
         sys.exit(2)
+
+
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 20     # pixels of the fixed sample written when the whole frame does not fit
+
+
+def dump_outputs(d, rgb, status=None):
+    """--dump-outputs DIR: the frame the last timed pass delivered, as arrays a build can be compared with another by.
+        DIR/rgb.npy          [3, M]  the RGB planes, in the run's dtype (float64 / float32)
+        DIR/pixel_index.npy  [M]     float64: the pixel i + j * ni of every column
+        DIR/status.npy       [M]     float32: the ray status bytes, where the path delivers them (N > 1, --entry sharded)
+    M is the whole frame when it fits in DUMP_BYTES, otherwise a fixed sample of DUMP_SAMPLE pixels (seeded: the same pixels for
+    every run of the same --size)."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    npix = rgb.shape[-1]
+    per_pixel = 3 * rgb.element_size() + 8 + (4 if status is not None else 0)
+    if npix * per_pixel <= DUMP_BYTES:
+        idx = np.arange(npix, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(npix, DUMP_SAMPLE, replace=False))
+    sel = torch.from_numpy(idx).to(rgb.device)
+    np.save(os.path.join(d, "rgb.npy"), rgb.index_select(1, sel).cpu().numpy())
+    np.save(os.path.join(d, "pixel_index.npy"), idx.astype(np.float64))
+    if status is not None:
+        np.save(os.path.join(d, "status.npy"), status.index_select(0, sel.to(status.device)).to(torch.float32).cpu().numpy())
 
 
 _LAST_FRAME = [None]

@@ -70,6 +70,61 @@ def test_per_row_checksums_sum_to_the_frame_checksum_and_localise_a_wrong_row():
     assert list(np.nonzero(rows != rows2)[0]) == [3]
 
 
+def _bench_module():
+    import importlib.util
+    import os
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location("rtgr_bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_bench_plain_run_asks_for_nothing_that_only_full_does(monkeypatch):
+    """bench.py without --full: no CPU baseline, extras or live counters (and asking for one of them is an error); --full: today's
+    defaults (CPU baseline auto, extras, live counters as the extras)."""
+    import pytest
+    b = _bench_module()
+    def parse(*args):
+        monkeypatch.setattr("sys.argv", ["bench.py", *args])
+        return b.parse()
+    plain = parse("--steps", "4")
+    assert (plain.full, plain.steps, plain.cpu_sample, plain.extras, plain.live_counters) == (False, 4, 0, 0, 0)
+    assert parse("--cpu-sample", "0", "--extras", "0", "--live-counters", "0").extras == 0
+    full = parse("--full")
+    assert (full.cpu_sample, full.extras, full.live_counters) == (-1, 1, 1)
+    assert parse("--full", "--extras", "0").live_counters == 0
+    for args in (("--extras", "1"), ("--cpu-sample", "48"), ("--live-counters", "1"), ("--emit-row-checksums",),
+                 ("--checksum-reference", "x.json"), ("--steps", "0")):
+        with pytest.raises(SystemExit):
+            parse(*args)
+
+
+def test_bench_dump_outputs_whole_frame_or_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the whole frame when it fits, otherwise the same seeded sample of pixels every time; float32 / float64
+    only, and never more than DUMP_BYTES in all."""
+    b = _bench_module()
+    assert b.DUMP_SAMPLE * (3 * 8 + 8 + 4) <= b.DUMP_BYTES
+    rgb = torch.from_numpy(np.random.default_rng(5).normal(size=(3, 400)))
+    b.dump_outputs(str(tmp_path / "whole"), rgb)
+    assert np.array_equal(np.load(tmp_path / "whole" / "rgb.npy"), rgb.numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "pixel_index.npy"), np.arange(400.0))
+    assert not (tmp_path / "whole" / "status.npy").exists()
+    monkeypatch.setattr(b, "DUMP_BYTES", 1000)
+    monkeypatch.setattr(b, "DUMP_SAMPLE", 20)
+    status = torch.arange(400, dtype=torch.int32).to(torch.uint8)
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), rgb.float(), status)
+    idx = np.load(tmp_path / "s1" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and len(np.unique(idx)) == 20 and (np.diff(idx) > 0).all()
+    got = np.load(tmp_path / "s1" / "rgb.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rgb.float().numpy()[:, idx.astype(np.int64)])
+    st = np.load(tmp_path / "s1" / "status.npy")
+    assert st.dtype == np.float32 and np.array_equal(st, (idx.astype(np.int64) % 256).astype(np.float32))
+    for f in ("rgb", "pixel_index", "status"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{f}.npy"), np.load(tmp_path / "s2" / f"{f}.npy"))
+
+
 # ---- the groups of a long list's spheres (rtgr_context.hip: group_spheres / bounding_sphere; DevScene in rtgr_args.hpp) -------------
 def _group(spheres, f32=False):
     """spheres: (n, 4) array of centre x, y, z and radius -> (order, nloose, groups[ng, 6]) through the library's test hook"""

@@ -5,7 +5,7 @@ OTHER=$1; ROUNDS=${2:-2}; shift 2
 for i in $(seq $ROUNDS); do
   for which in default other; do
     if [ $which = other ]; then export RTGR_LIB=$OTHER; else unset RTGR_LIB; fi
-    python bench.py --cpu-sample 0 --extras 0 --live-counters 0 "$@" 2>/dev/null | python -c "
+    python bench.py --full --cpu-sample 0 --extras 0 --live-counters 0 "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 # bench default).  usage: tools/configs.sh <outfile>
 OUT=${1:-gpurun_out/configs.log}
 # (small frames get enough passes for the clocks to settle: 2 passes of a 3 ms frame measure the ramp, not the kernel)
-run() { echo "### $1" | tee -a $OUT; shift; S=2; W=1; case "$*" in *"--size 200"*|*"--size 1024"*|*"--dtype f32"*) S=30; W=6;; esac; python bench.py --cpu-sample 0 --extras 0 --steps $S --warmup $W "$@" 2>/dev/null | python -c "
+run() { echo "### $1" | tee -a $OUT; shift; S=2; W=1; case "$*" in *"--size 200"*|*"--size 1024"*|*"--dtype f32"*) S=30; W=6;; esac; python bench.py --full --cpu-sample 0 --extras 0 --steps $S --warmup $W "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

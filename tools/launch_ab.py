@@ -13,7 +13,7 @@ and/or alternative builds of the library.
         per-rank time of a cyclic N-way split, N = 1, 2, 4, 8 (a REHEARSAL of the strong-scaling curve: compute only, one GPU)
     python tools/launch_ab.py builds --flags "name1:-DA=1,-DB=2;name2:-DC=3" [--size ...]
         builds raytracegr.jl_amd/build/variants/librtgr_<name>.so with the extra flags and times each (fresh process per
-        library, RTGR_LIB) against the default build with `bench.py --cpu-sample 0 --extras 0`
+        library, RTGR_LIB) against the default build with `bench.py --full --cpu-sample 0 --extras 0`
 """
 import argparse
 import ctypes
@@ -111,7 +111,7 @@ def main():
                 if path:
                     env["RTGR_LIB"] = path
                 steps = a.bench_steps or (30 if a.size <= 2048 else 3)
-                r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(max(1, steps // 5)), "--cpu-sample", "0",
+                r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(max(1, steps // 5)), "--full", "--cpu-sample", "0",
                                     "--extras", "0", "--size", str(a.size), "--variant", variant, "--dtype", a.dtype],
                                    capture_output=True, text=True, env=env)
                 line = next((json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")), None)
