@@ -81,8 +81,11 @@ enum rtgr_metric {
                            (src/RayTraceGR.jl:284); the reference hard-wires M=1, a=0 (:275-276)               */
     RTGR_KS_TRUE = 2,   /* textbook Kerr–Schild radius r^2 = (q + sqrt(q^2 + 4 a^2 z^2))/2, q = rho^2 - a^2
                            (no reference counterpart; needed for a != 0 configs)                               */
-    RTGR_USER = 3       /* the metric function rtgr_scene.user_metric names (rtgr_user_metric_load); always traced
+    RTGR_USER = 3,      /* the metric function rtgr_scene.user_metric names (rtgr_user_metric_load); always traced
                            with the generic dual-number RHS (RTGR_METRIC_GENERIC is implied)                   */
+    RTGR_GRID = 4       /* a stationary metric given as SAMPLES on a uniform 3-D grid: rtgr_scene.user_metric holds the
+                           grid's id (rtgr_grid_metric_load, below).  Always the generic contraction (RTGR_GRID |
+                           RTGR_METRIC_GENERIC means the same).                                                */
 };
 
 /* OR-ed into rtgr_scene.metric: evaluate the geodesic RHS the way the reference does for ANY metric callable — 4-wide
@@ -117,7 +120,7 @@ typedef struct rtgr_scene {
     uint32_t nobj;   /* length of the object list: 0..RTGR_MAX_OBJECTS in obj[], or any number (<= RTGR_OBJECTS_LIMIT) in objects[] */
     double M;        /* mass  (reference: 1, :275) */
     double a;        /* spin  (reference: 0, :276) */
-    uint64_t user_metric; /* id of the run-time compiled UNIT this scene is written for — the module that carries the kernels
+    uint64_t user_metric; /* RTGR_GRID: the id of the grid (rtgr_grid_metric_load).  Otherwise: the id of the run-time compiled UNIT this scene is written for — the module that carries the kernels
                              of a user metric (RTGR_USER), of user objects (RTGR_USER_OBJECT), or of both
                              (rtgr_user_metric_load / _compile, rtgr_user_unit_compile); a scene can never run with another
                              unit's kernels.  0: built-in metric and built-in objects only. */
@@ -158,7 +161,9 @@ enum rtgr_ray_status {
     RTGR_RAY_LAMBDA1 = 1,   /* reached lambda1 without an event                              */
     RTGR_RAY_MAXSTEPS = 2,  /* hit max_steps                                                 */
     RTGR_RAY_DTMIN = 3,     /* step size underflow                                           */
-    RTGR_RAY_NAN = 4        /* state became non-finite                                       */
+    RTGR_RAY_NAN = 4,       /* state became non-finite                                       */
+    RTGR_RAY_OUTSIDE = 5    /* RTGR_GRID only: the ray left the grid's valid box before any event
+                               (counted in not_finished; coloured like a ray that reached lambda1) */
 };
 
 /* ---- counters accumulated over a call (8 x uint64) -------------------------------------------------------- */
@@ -445,6 +450,42 @@ int rtgr_user_metric_compile(rtgr_context* ctx, const char* source, int stationa
  * keep the file, load it in every later process).  Needs no GPU and no context. */
 int rtgr_user_metric_build(const char* source, int stationary, const char* code_object_path);
 int rtgr_user_metric_unload(rtgr_context* ctx, uint64_t id); /* id 0: all */
+
+/* ---- metrics sampled on a grid: a spacetime that exists only as numbers ------------------------------------------------
+ * A numerically computed spacetime (e.g. a binary black hole from a numerical-relativity code) is g_ab sampled on a Cartesian
+ * grid; no source text can stand in for it.  A STATIONARY metric (d_t g = 0) sampled on a uniform 3-D grid is handed over as data:
+ *   grid->n[3]        samples along x, y, z (each >= 4);  grid->pad = 0
+ *   grid->origin[3]   (x, y, z) of sample (0, 0, 0);      grid->spacing[3] > 0 (h_x, h_y, h_z)
+ *   g                 n[2]*n[1]*n[0]*10 doubles, x fastest: sample (i, j, k) at g[((k*n[1] + j)*n[0] + i)*10 + c], the 10
+ *                     components the upper triangle in row order: tt tx ty tz xx xy xz yy yz zz
+ * The call refuses (RTGR_ERR_BAD_ARG, the index of the first bad sample in rtgr_last_error()) any non-finite value and any sample
+ * with det g >= 0 (which also catches a transposed layout), and grids of more than RTGR_GRID_MAX_SAMPLES points.  It uploads the
+ * samples to every device of the context, in Float64 and in Float32 (the _f32 entry points read the latter), and returns an id; a
+ * scene selects the grid with metric = RTGR_GRID, user_metric = id in every entry point that takes a scene.  Grid ids and unit ids
+ * never coincide.  M and a of the scene are not read.
+ *   Interpolant: tricubic Catmull-Rom (cubic convolution, a = -1/2), separable.  Per axis s = (x - origin)/h, i = clamp(floor(s),
+ * 1, n - 3), t = s - i, weights on samples i-1 .. i+2:  (-t^3 + 2t^2 - t)/2, (3t^3 - 5t^2 + 2)/2, (-3t^3 + 4t^2 + t)/2, (t^3 - t^2)/2;
+ * derivative weights d/dt of those times 1/h.  It interpolates the samples, g and its first derivatives are continuous across cell
+ * faces, quadratics are reproduced exactly, and g and dg come from the same polynomial.  The VALID BOX is s in [1, n - 2] on every
+ * axis; outside it the clamped cell's cubic is extrapolated (finite, meaningless).  Every geodesic RHS evaluation reads 4x4x4
+ * samples: 16 rows of 4 consecutive x-samples, 40 contiguous doubles each.
+ *   Tracing: a step whose scan finds an event ends the ray as RTGR_RAY_EVENT; otherwise an accepted step that ends outside the valid
+ * box ends it as RTGR_RAY_OUTSIDE with state_end / lambda_end at the end of that step; a ray that STARTS outside ends as
+ * RTGR_RAY_OUTSIDE with 0 accepted steps.  All entry points (device, host-pointer, frames in flight, sharded) and both pass
+ * structures (FULL == FAR + NEAR bit for bit) take grid scenes; rtgr_make_canvas_*, the redshift output and rtgr_eval_metric_*
+ * evaluate the interpolant (d_t g = 0), rtgr_eval_geodesic_* evaluates the grid RHS for every `path`.  Out of scope: user objects in
+ * a grid scene (RTGR_ERR_BAD_ARG), time-dependent grids, several patches.
+ *   Lifetime: rtgr_grid_metric_unload makes the id unknown at once (a scene naming it fails with RTGR_ERR_BAD_ARG), but the device
+ * memory is RETIRED, not freed — a hipGraph captured earlier may still replay it — until rtgr_trim / rtgr_destroy. */
+#define RTGR_GRID_MAX_SAMPLES (1ull << 28)   /* n[0]*n[1]*n[2] at most: 21.5 GB in Float64 + 10.7 GB in Float32 per device */
+typedef struct rtgr_grid {
+    uint32_t n[3];      /* samples along x, y, z; each >= 4 */
+    uint32_t pad;       /* 0 */
+    double origin[3];   /* (x, y, z) of sample (0,0,0) */
+    double spacing[3];  /* > 0 */
+} rtgr_grid;            /* 64 bytes */
+int rtgr_grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out);
+int rtgr_grid_metric_unload(rtgr_context* ctx, uint64_t id);
 
 /* ---- user objects: `Object{T}` is an OPEN abstract type (src/RayTraceGR.jl:374-389) ------------------------------------------
  * The reference's second extension point: any `struct MyThing{T} <: Object{T}` with the two methods

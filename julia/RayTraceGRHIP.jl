@@ -23,6 +23,7 @@
 #   RtgrCamera      128   pos 0, widthx 32, widthy 64, normal 96
 #   RtgrCounters     64   rays 0, accepted 8, rejected 16, rhs_evals 24, events 32, events_interior 40, not_finished 48, reserved 56
 #   RtgrRayOutputs   64   state_end 0, lambda_end 8, status 16, hit 24, n_accept 32, n_reject 40, redshift 48, hit32 56
+#   RtgrGrid         64   n 0, pad 12, origin 16, spacing 40
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64          (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -82,6 +83,12 @@ struct RtgrCounters
     rays::UInt64; accepted::UInt64; rejected::UInt64; rhs_evals::UInt64
     events::UInt64; events_interior::UInt64; not_finished::UInt64; reserved::UInt64
 end
+struct RtgrGrid                # a metric sampled on a uniform grid (rtgr_grid_metric_load)
+    n::NTuple{3,UInt32}         # samples along x, y, z; each >= 4
+    pad::UInt32
+    origin::NTuple{3,Float64}   # (x, y, z) of sample (0, 0, 0)
+    spacing::NTuple{3,Float64}
+end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
     lambda_end::Ptr{Cvoid}
@@ -98,6 +105,7 @@ const RTGR_MINKOWSKI = UInt32(0)
 const RTGR_KS_REF = UInt32(1)
 const RTGR_KS_TRUE = UInt32(2)
 const RTGR_USER = UInt32(3)
+const RTGR_GRID = UInt32(4)
 const RTGR_METRIC_GENERIC = UInt32(0x100)
 const RTGR_PLANE = UInt32(1)
 const RTGR_SPHERE = UInt32(2)
@@ -108,6 +116,7 @@ const RTGR_RAY_LAMBDA1 = UInt8(1)
 const RTGR_RAY_MAXSTEPS = UInt8(2)
 const RTGR_RAY_DTMIN = UInt8(3)
 const RTGR_RAY_NAN = UInt8(4)
+const RTGR_RAY_OUTSIDE = UInt8(5)
 
 function check(rc)
     rc < 0 && error("librtgr_hip: ", unsafe_string(ccall((:rtgr_last_error, librtgr), Cstring, ())))
@@ -303,7 +312,45 @@ function module_id(m::DeviceMetric, ctx)
     id[]
 end
 
+"""
+    GridMetric(g, origin, spacing)
+
+A stationary metric given as SAMPLES on a uniform grid — a numerically computed spacetime (include/rtgr.h "metrics sampled on
+a grid"): `g` is a 10 x nx x ny x nz Array{Float64} (the upper triangle tt tx ty tz xx xy xz yy yz zz first, then x fastest — the
+C layout, column-major), `origin` and `spacing` 3-tuples.  Uploaded to the context on first use (`rtgr_grid_metric_load`); rays that
+leave the grid's valid box end with status RTGR_RAY_OUTSIDE.  `unload(m, ctx)` releases the id (`rtgr_grid_metric_unload`).
+"""
+struct GridMetric
+    g::Array{Float64,4}
+    origin::NTuple{3,Float64}
+    spacing::NTuple{3,Float64}
+    ids::Dict{Ptr{Cvoid},UInt64}
+end
+function GridMetric(g::AbstractArray{<:Real,4}, origin, spacing)
+    size(g, 1) == 10 || error("GridMetric: g must be 10 x nx x ny x nz")
+    all(size(g)[2:4] .>= 4) || error("GridMetric: at least 4 samples per axis")
+    all(v -> v - v == 0, g) || error("GridMetric: non-finite sample")   # (v - v is NaN for Inf and NaN)
+    all(h -> h > 0, spacing) || error("GridMetric: spacing must be > 0")
+    GridMetric(Array{Float64,4}(g), Tuple(Float64.(origin)), Tuple(Float64.(spacing)), Dict{Ptr{Cvoid},UInt64}())
+end
+function module_id(m::GridMetric, ctx)
+    id = Ref{UInt64}(get(m.ids, handle(ctx), UInt64(0)))
+    if id[] == 0   # first use in this context (or unloaded since): upload
+        desc = Ref(RtgrGrid(UInt32.(size(m.g)[2:4]), UInt32(0), m.origin, m.spacing))
+        check(ccall((:rtgr_grid_metric_load, librtgr), Cint, (Ctx, Ptr{RtgrGrid}, Ptr{Float64}, Ptr{UInt64}), handle(ctx), desc, m.g, id))
+        m.ids[handle(ctx)] = id[]
+    end
+    id[]
+end
+function unload(m::GridMetric, ctx = nothing)
+    id = get(m.ids, handle(ctx), UInt64(0))
+    id == 0 || check(ccall((:rtgr_grid_metric_unload, librtgr), Cint, (Ctx, UInt64), handle(ctx), id))
+    m.ids[handle(ctx)] = UInt64(0)
+    nothing
+end
+
 # (enum, M, a, user_metric id) of a metric argument, or nothing when it cannot cross the ABI
+metric_desc(m::GridMetric, ctx) = (RTGR_GRID, 0.0, 0.0, module_id(m, ctx))
 metric_desc(m::DeviceMetric, ctx) = (RTGR_USER, m.M, m.a, module_id(m, ctx))
 metric_desc(m::KerrSchild, ctx) = ((m.textbook ? RTGR_KS_TRUE : RTGR_KS_REF) | (m.generic ? RTGR_METRIC_GENERIC : UInt32(0)),
                                    m.M, m.a, UInt64(0))

@@ -56,6 +56,90 @@ def KerrSchild(M=1.0, a=0.0, textbook=True, generic=False):
     return Metric(_abi.KS_TRUE if textbook else _abi.KS_REF, M, a, name="KerrSchild", generic=generic)
 
 
+_UPPER = [(0, 0), (0, 1), (0, 2), (0, 3), (1, 1), (1, 2), (1, 3), (2, 2), (2, 3), (3, 3)]   # tt tx ty tz xx xy xz yy yz zz
+
+
+class GridMetric:
+    """A stationary metric given as SAMPLES on a uniform 3-D grid (RTGR_GRID, include/rtgr.h) — a numerically computed spacetime
+    has no formula.  g: numpy array (nz, ny, nx, 10) of the upper triangle tt tx ty tz xx xy xz yy yz zz, or (nz, ny, nx, 4, 4)
+    (the upper triangle is taken); origin = (x, y, z) of sample [0, 0, 0]; spacing = (hx, hy, hz) (a scalar: the same on every
+    axis).  Values and first derivatives are interpolated on the device (tricubic Catmull-Rom) inside the integrate loop; rays that
+    leave the valid box end with status RAY_OUTSIDE.  Uploaded lazily, once per context; calling it evaluates g on the GPU."""
+    kind = _abi.GRID
+    generic = False   # (grids always take the generic contraction; the scene's metric is plain RTGR_GRID)
+    M = a = 0.0
+
+    def __init__(self, g, origin, spacing, name="grid"):
+        g = np.asarray(g)
+        if g.ndim == 5 and g.shape[3:] == (4, 4):
+            g = np.stack([g[..., p, q] for p, q in _UPPER], axis=-1)
+        if g.ndim != 4 or g.shape[3] != 10:
+            raise ValueError(f"GridMetric: g must have shape (nz, ny, nx, 10) or (nz, ny, nx, 4, 4), got {g.shape}")
+        if min(g.shape[:3]) < 4:
+            raise ValueError(f"GridMetric: at least 4 samples per axis, got (nz, ny, nx) = {g.shape[:3]}")
+        if g.shape[0] * g.shape[1] * g.shape[2] > _abi.RTGR_GRID_MAX_SAMPLES:
+            raise ValueError("GridMetric: more than RTGR_GRID_MAX_SAMPLES samples")
+        origin = np.broadcast_to(np.asarray(origin, np.float64), (3,)).copy()
+        spacing = np.broadcast_to(np.asarray(spacing, np.float64), (3,)).copy()
+        if not np.all(np.isfinite(origin)) or not np.all(np.isfinite(spacing)) or not np.all(spacing > 0):
+            raise ValueError(f"GridMetric: origin must be finite and spacing finite and > 0, got {origin}, {spacing}")
+        self.g = np.ascontiguousarray(g, dtype=np.float64)
+        if not np.all(np.isfinite(self.g)):
+            bad = int(np.flatnonzero(~np.isfinite(self.g).all(axis=-1).ravel())[0])
+            raise ValueError(f"GridMetric: sample {bad} (x fastest) holds a non-finite value")
+        self.origin, self.spacing, self.__name__ = origin, spacing, name
+        self.n = (g.shape[2], g.shape[1], g.shape[0])   # (nx, ny, nz)
+        self._ids = {}
+
+    def box(self):
+        """the valid box ((x0, x1), (y0, y1), (z0, z1)): samples 1 .. n-2 of every axis"""
+        return tuple((self.origin[a] + self.spacing[a], self.origin[a] + (self.n[a] - 2) * self.spacing[a]) for a in range(3))
+
+    def module_id(self, ctx=None):
+        """id of this grid in the context (uploaded on first use)"""
+        key = getattr(ctx, "value", ctx)
+        gid = self._ids.get(key)
+        if gid is not None:
+            return gid
+        lib = _lib()
+        desc = _abi.rtgr_grid()
+        for a in range(3):
+            desc.n[a], desc.origin[a], desc.spacing[a] = self.n[a], self.origin[a], self.spacing[a]
+        out = C.c_uint64(0)
+        _abi.check(lib, lib.rtgr_grid_metric_load(ctx, C.byref(desc), self.g.ctypes.data, C.byref(out)))
+        self._ids[key] = out.value
+        return out.value
+
+    def unload(self, ctx=None):
+        """release this grid's id in the context (the device memory goes at the next rtgr_trim)"""
+        gid = self._ids.pop(getattr(ctx, "value", ctx), None)
+        if gid is not None:
+            _abi.check(_lib(), _lib().rtgr_grid_metric_unload(ctx, gid))
+
+    def __call__(self, x, dtype=np.float64):
+        return _eval_metric(self, x, want=(True, False, False), dtype=dtype)[0]
+
+    def __repr__(self):
+        return f"GridMetric({self.__name__}, n={self.n}, origin={tuple(self.origin)}, spacing={tuple(self.spacing)})"
+
+
+def sample_metric(metric, origin, spacing, n, chunk=1 << 20):
+    """Samples any metric the library evaluates (built-in, UserMetric, GridMetric) on a uniform grid through rtgr_eval_metric_f64:
+    n = (nx, ny, nz) points from origin with spacing (scalar or per axis), at t = 0.  Returns the (nz, ny, nx, 10) array GridMetric
+    takes.  Evaluated in chunks of `chunk` points."""
+    nx, ny, nz = (int(v) for v in n)
+    origin = np.broadcast_to(np.asarray(origin, np.float64), (3,))
+    spacing = np.broadcast_to(np.asarray(spacing, np.float64), (3,))
+    z, y, x = np.meshgrid(*(origin[a] + spacing[a] * np.arange(m) for a, m in ((2, nz), (1, ny), (0, nx))), indexing="ij")
+    pts = np.stack([np.zeros(x.size), x.ravel(), y.ravel(), z.ravel()], axis=1)
+    out = np.empty((pts.shape[0], 10))
+    for s0 in range(0, pts.shape[0], chunk):
+        g, _, _ = _eval_metric(metric, pts[s0:s0 + chunk], want=(True, False, False))
+        g = g.reshape(-1, 4, 4)
+        out[s0:s0 + chunk] = np.stack([g[:, p, q] for p, q in _UPPER], axis=1)
+    return out.reshape(nz, ny, nx, 10)
+
+
 # ---- objects (src/RayTraceGR.jl:374-428) ------------------------------------------------------------------------
 class Object:
     kind = 0
@@ -105,10 +189,11 @@ def make_scene(metric, objs, ctx=None, units=True):
     UserMetric and / or of UserObjects carries the id of its run-time unit in `ctx` (built and loaded on first use), so it
     can only ever run with its own kernels — whichever other units are resident.  units=False leaves the id 0 and touches
     neither compiler nor GPU (a scene description for something else than this library: the tests' CPU oracle)."""
-    if not isinstance(metric, (Metric, UserMetric)):
+    if not isinstance(metric, (Metric, UserMetric, GridMetric)):
         raise TypeError(
-            "a metric is one of the built-ins (minkowski, kerr_schild, KerrSchild(M,a)) or a UserMetric(source) "
-            "compiled for the device; a Python callable cannot cross the C ABI (SURVEY §8b)")
+            "a metric is one of the built-ins (minkowski, kerr_schild, KerrSchild(M,a)), a UserMetric(source) "
+            "compiled for the device or a GridMetric of samples; "
+            "a Python callable cannot cross the C ABI (SURVEY §8b)")
     objs = list(objs)
     if len(objs) > _abi.RTGR_OBJECTS_LIMIT:
         raise ValueError(f"at most {_abi.RTGR_OBJECTS_LIMIT} objects")
@@ -123,8 +208,12 @@ def make_scene(metric, objs, ctx=None, units=True):
         base = {id(f): b for f, b in zip(families, bases)}
         families = [joined]
     user_id = 0
+    if isinstance(metric, GridMetric) and any(isinstance(o, UserObject) for o in objs):
+        raise ValueError("user objects in a scene with a GridMetric are not supported")
     if not units:
         pass
+    elif isinstance(metric, GridMetric):
+        user_id = metric.module_id(ctx)
     elif families:
         user_id = families[0].unit_id(metric, ctx)
     elif isinstance(metric, UserMetric):
@@ -420,7 +509,7 @@ def example2(ni=200, nj=200, save=True, ctx=None):
     return _run_example(example2_scene(), ni, nj, "sphere2.png", save, ctx)
 
 
-__all__ = ["D", "Metric", "UserMetric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
+__all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
            "trace_rays", "trace_ray", "trace_frames", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

@@ -25,8 +25,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 UNITS = ["tu_f64_ksref.hip", "tu_f64_kstrue.hip", "tu_f64_generic.hip", "tu_f64_mink.hip", "tu_f32_closed.hip",
-         "tu_f32_generic.hip", "rtgr_misc.hip", "rtgr_context.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip",
-         "rtgr_units.hip", "rtgr_abi.hip"]
+         "tu_f32_generic.hip", "tu_f64_grid.hip", "tu_f32_grid.hip", "rtgr_misc.hip", "rtgr_context.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip",
+         "rtgr_units.hip", "rtgr_grid.hip", "rtgr_abi.hip"]
 # the device-side headers: what the KERNELS are made of (bench.py keys its roofline profile on their hash)
 KERNEL_HEADERS = ["rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_integrator.hpp", "rtgr_persistent.hpp", "rtgr_packed_f32.hpp",
                   "rtgr_tsit5_tables.hpp"]
@@ -37,7 +37,7 @@ OBJ = os.path.join(HERE, "build", "obj")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 LLVM_BIN = os.path.join(os.path.dirname(os.path.realpath(HIPCC)), "..", "lib", "llvm", "bin")
 # no kernel in them: they never need the listing route
-HOST_ONLY_UNITS = ("rtgr_context.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip", "rtgr_units.hip", "rtgr_abi.hip")
+HOST_ONLY_UNITS = ("rtgr_context.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip", "rtgr_units.hip", "rtgr_grid.hip", "rtgr_abi.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 

@@ -1,7 +1,7 @@
 // rtgr_abi.hip — the C ABI of include/rtgr.h: every exported symbol, and nothing else.  Each is a one-line shim onto the function of
 // the same name (minus the rtgr_ prefix) in namespace rtgr::api, defined in rtgr_context.hip (lifecycle, options, timing, device entry
 // points), rtgr_host_pipeline.hip (host-pointer entry points), rtgr_sharded.hip (all devices of a context), rtgr_hooks.hip (camera,
-// parity hooks, quantisation) and rtgr_units.hip (run-time units).  tests/test_abi.py holds this list against include/rtgr.h.
+// parity hooks, quantisation), rtgr_units.hip (run-time units) and rtgr_grid.hip (metrics sampled on a grid).  tests/test_abi.py holds this list against include/rtgr.h.
 #include "rtgr_internal.hpp"
 
 extern "C" {
@@ -56,6 +56,8 @@ int rtgr_user_metric_load(rtgr_context* ctx, const char* code_object_path, uint6
 int rtgr_user_metric_compile(rtgr_context* ctx, const char* source, int stationary, uint64_t* id_out) { return rtgr::api::user_metric_compile(ctx, source, stationary, id_out); }
 int rtgr_user_metric_build(const char* source, int stationary, const char* code_object_path) { return rtgr::api::user_metric_build(source, stationary, code_object_path); }
 int rtgr_user_metric_unload(rtgr_context* ctx, uint64_t id) { return rtgr::api::user_metric_unload(ctx, id); }
+int rtgr_grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out) { return rtgr::api::grid_metric_load(ctx, grid, g, id_out); }
+int rtgr_grid_metric_unload(rtgr_context* ctx, uint64_t id) { return rtgr::api::grid_metric_unload(ctx, id); }
 int rtgr_user_unit_compile(rtgr_context* ctx, const char* source, int stationary, const rtgr_scene* built_for, uint64_t* id_out) { return rtgr::api::user_unit_compile(ctx, source, stationary, built_for, id_out); }
 int rtgr_user_unit_build(const char* source, int stationary, const rtgr_scene* built_for, const char* code_object_path) { return rtgr::api::user_unit_build(source, stationary, built_for, code_object_path); }
 int rtgr_user_source_join(const char* const* sources, const uint32_t* ntypes, int n, char* out, uint64_t cap, uint64_t* need) { return rtgr::api::user_source_join(sources, ntypes, n, out, cap, need); }

@@ -26,6 +26,18 @@ struct DevObject {
 // (in the caller's order), each object carrying its original index (DevObject::orig), which the colour rule breaks ties by and
 // reports.  The integrate kernels then walk the spheres — all but two or three objects of any long list — in a loop of their own
 // with no dispatch on the kind: a third of the scalar instructions per object.
+// A metric sampled on a grid (RTGR_GRID, include/rtgr.h): the device copy of the caller's samples in the scalar type of the kernels
+// (10 per point, x fastest: the caller's own layout) and what the interpolant needs per axis, all wave-uniform (read from the kernarg).
+template <class R>
+struct DevGrid {
+    const R* g;         // null unless the scene's metric is RTGR_GRID
+    uint64_t sy, sz;    // scalars between neighbouring samples along y / z (10 n_x, 10 n_x n_y)
+    R origin[3];        // (x, y, z) of sample (0, 0, 0)
+    R inv_h[3];         // 1 / spacing
+    R hi[3];            // n - 3: the highest cell index the interpolant clamps to
+    R top[3];           // n - 2: upper edge of the valid box in index units (the lower edge is 1)
+};
+
 template <class R>
 struct DevScene {
     uint32_t metric;
@@ -37,6 +49,7 @@ struct DevScene {
     const DevObject<R>* more;   // objects RTGR_MAX_OBJECTS .. nobj-1 (the table holds the WHOLE list: table = more - RTGR_MAX_OBJECTS)
     uint32_t nloose;    // (ngroups > 0) spheres [0, nloose) belong to no group
     uint32_t nsuper;    // > 0: the groups themselves come in that many runs of neighbouring groups with a bounding sphere each (a second level)
+    DevGrid<R> grid;    // metric == RTGR_GRID: the samples (rtgr_context.hip: grid tables)
 };
 // GROUPS (long lists: DESIGN.md §4.7).  The FAR pass's reach test asks of every object, every step, "can this step reach you?"; of a
 // list of 64 small spheres the answer is no for all but one or two.  The host therefore sorts the spheres of a long list into groups of

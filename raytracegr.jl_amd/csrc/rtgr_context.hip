@@ -155,6 +155,12 @@ void free_device_state(DeviceCtx& d, bool all) {
             if (kv.second.queue) (void)hipFree(kv.second.queue);
         }
     }
+    for (auto& g : d.retired_grids) { (void)hipFree(g.d64); (void)hipFree(g.d32); }   // unloaded grid metrics (idle device: see above)
+    d.retired_grids.clear();
+    if (all) {
+        for (auto& g : d.grids) { (void)hipFree(g.d64); (void)hipFree(g.d32); }
+        d.grids.clear();
+    }
     for (auto& kv : d.object_tables) (void)hipFree(kv.second.dev);   // (the device is idle: synchronised above)
     d.object_tables.clear();
     d.object_table_bytes = 0;
@@ -453,15 +459,26 @@ static void super_sphere(const DevObject<R>* t, const std::vector<SphereGroup>& 
 template <class R>
 int convert_scene(DeviceCtx& D, const rtgr_scene* s, DevScene<R>& d, const UserModule** user, hipStream_t st) {
     if (!s) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
-    if ((s->metric & ~RTGR_METRIC_GENERIC) > RTGR_USER) return fail(RTGR_ERR_BAD_ARG, "unknown metric enum");
+    if ((s->metric & ~RTGR_METRIC_GENERIC) > RTGR_GRID) return fail(RTGR_ERR_BAD_ARG, "unknown metric enum");
     *user = nullptr;
     if (s->nobj > RTGR_MAX_OBJECTS && !s->objects)
         return fail(RTGR_ERR_BAD_ARG, "more than RTGR_MAX_OBJECTS objects: hand the list over through rtgr_scene.objects (any length)");
     if (s->nobj > RTGR_OBJECTS_LIMIT) return fail(RTGR_ERR_BAD_ARG, "more than RTGR_OBJECTS_LIMIT objects");
     const rtgr_object* objs = scene_objects(s);
     const bool user_metric = (s->metric & ~RTGR_METRIC_GENERIC) == RTGR_USER;
+    const GridTable* grid = nullptr;
+    if ((s->metric & ~RTGR_METRIC_GENERIC) == RTGR_GRID) {   // a metric sampled on a grid: rtgr_scene.user_metric is the grid's id
+        for (uint32_t o = 0; o < s->nobj; o++)
+            if (objs[o].kind == RTGR_USER_OBJECT)
+                return fail(RTGR_ERR_BAD_ARG, "RTGR_GRID: user objects (RTGR_USER_OBJECT) in a scene with a grid metric are not supported");
+        grid = D.find_grid(s->user_metric);
+        if (!grid)
+            return fail(RTGR_ERR_BAD_ARG, "RTGR_GRID: no grid metric with id " + std::to_string(s->user_metric) +
+                                          " is loaded in this context (rtgr_grid_metric_load; an unloaded id stays unknown)");
+    }
     bool user_objects = tl_probe_forces_unit && s->user_metric != 0 && !user_metric;
     for (uint32_t o = 0; o < s->nobj; o++) user_objects = user_objects || objs[o].kind == RTGR_USER_OBJECT;
+    if (grid) user_objects = false;   // (rtgr_scene.user_metric names the grid, never a unit)
     if (user_metric || user_objects) {
         const char* what = user_metric ? "RTGR_USER" : "RTGR_USER_OBJECT";
         if (D.modules.empty())
@@ -491,6 +508,17 @@ int convert_scene(DeviceCtx& D, const rtgr_scene* s, DevScene<R>& d, const UserM
     d.nobj = s->nobj;
     d.M = (R)s->M;
     d.a = (R)s->a;
+    if (grid) {
+        d.grid.g = (const R*)(sizeof(R) == 8 ? grid->d64 : grid->d32);
+        d.grid.sy = 10ull * grid->n[0];
+        d.grid.sz = 10ull * grid->n[0] * grid->n[1];
+        for (int ax = 0; ax < 3; ax++) {
+            d.grid.origin[ax] = (R)grid->origin[ax];
+            d.grid.inv_h[ax] = (R)(1.0 / grid->spacing[ax]);
+            d.grid.hi[ax] = (R)(grid->n[ax] - 3u);
+            d.grid.top[ax] = (R)(grid->n[ax] - 2u);
+        }
+    }
     int rc;
     const uint32_t n0 = s->nobj < (uint32_t)RTGR_MAX_OBJECTS ? s->nobj : (uint32_t)RTGR_MAX_OBJECTS;
     // the device list is REGROUPED (DevScene, rtgr_args.hpp): spheres first, then the rest, both in the caller's order, every object
@@ -554,6 +582,7 @@ void convert_camera(const rtgr_camera* c, DevCamera<R>& d) {
 }
 
 int dispatch(LaunchEnv& E, const TraceArgs<double>& A, bool generic, bool spin, hipStream_t st) {
+    if (A.sc.metric == RTGR_GRID) return launch_f64_grid(E, A, st);
     if (generic || E.user) return launch_f64_generic(E, A, st);   // (a scene with a run-time unit launches the unit's kernels from there)
     switch (A.sc.metric) {
         case RTGR_MINKOWSKI: return launch_f64_mink(E, A, st);
@@ -562,6 +591,7 @@ int dispatch(LaunchEnv& E, const TraceArgs<double>& A, bool generic, bool spin, 
     }
 }
 int dispatch(LaunchEnv& E, const TraceArgs<float>& A, bool generic, bool spin, hipStream_t st) {
+    if (A.sc.metric == RTGR_GRID) return launch_f32_grid(E, A, st);
     if (generic || E.user) return launch_f32_generic(E, A, st);
     return launch_f32_closed(E, A, spin, st);
 }
@@ -620,9 +650,10 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
     if (win) { A.plane_stride = win->plane_stride; A.out_offset = win->out_offset; A.nan_flag = win->nan_flag; }
     A.counters = (unsigned long long*)d_counters;
     const bool spin = scene->a != 0.0;
-    const bool generic = ((scene->metric & RTGR_METRIC_GENERIC) != 0 && A.sc.metric != RTGR_MINKOWSKI) || A.sc.metric == RTGR_USER;
+    const bool generic = ((scene->metric & RTGR_METRIC_GENERIC) != 0 && A.sc.metric != RTGR_MINKOWSKI) || A.sc.metric == RTGR_USER ||
+                         A.sc.metric == RTGR_GRID;
     if ((tl_knobs_override ? tl_knobs_override->tile : D.knobs.tile)) {   // (the probe and the scene check bring their own options: tile = 0)
-        if (generic || user) return fail(RTGR_ERR_BAD_ARG, "RTGR_METRIC_GENERIC and run-time units need the persistent pipeline (option tile = 0)");
+        if (generic || user) return fail(RTGR_ERR_BAD_ARG, "RTGR_METRIC_GENERIC, RTGR_GRID and run-time units need the persistent pipeline (option tile = 0)");
         if (win && (win->plane_stride || win->out_offset)) return fail(RTGR_ERR_BAD_ARG, "the tile kernel writes whole slabs only");
     }
     StreamState* ss = nullptr;

@@ -119,6 +119,15 @@ struct ObjectTable { std::vector<char> content; void* dev = nullptr; };
 constexpr size_t OBJECT_TABLES_MAX = 512;
 constexpr size_t OBJECT_TABLES_BYTES = (size_t)1 << 30;
 
+// A metric sampled on a grid (rtgr_grid_metric_load): the samples on one device, in Float64 and Float32.  Immutable; rtgr_grid_metric_unload
+// moves the table to DeviceCtx::retired_grids (a hipGraph captured earlier may still replay it), rtgr_trim / rtgr_destroy free it.
+struct GridTable {
+    uint64_t id = 0;
+    void* d64 = nullptr;   // n[2] n[1] n[0] x 10 doubles, x fastest (the caller's layout)
+    void* d32 = nullptr;   // … the same as floats
+    uint32_t n[3] = {0, 0, 0};
+    double origin[3] = {0, 0, 0}, spacing[3] = {0, 0, 0};
+};
 // pipeline workspace of one (device, stream)
 struct StreamState {
     void* ws = nullptr;
@@ -136,6 +145,8 @@ struct DeviceCtx {
     std::mutex mu;      // held while a call enqueues its kernels: the enqueue sequences of two host threads never interleave
     std::unordered_map<hipStream_t, StreamState> streams;
     std::vector<UserModule> modules;
+    std::vector<GridTable> grids;           // resident grid metrics, by id
+    std::vector<GridTable> retired_grids;   // unloaded ones: freed by rtgr_trim / rtgr_destroy only
     std::unordered_multimap<uint64_t, ObjectTable> object_tables;   // by FNV-1a of the content
     size_t object_table_bytes = 0;                                   // … and what they hold together
     std::unordered_map<uint64_t, int> checked_scenes;                // auto_scene_check: key of a scene -> the verdict it got (RTGR_OK or the refusal)
@@ -156,6 +167,10 @@ struct DeviceCtx {
         hipEvent_t e = nullptr;
         (void)hipEventCreate(&e);
         return e;
+    }
+    const GridTable* find_grid(uint64_t id) const {
+        for (auto& g : grids) if (g.id == id) return &g;
+        return nullptr;
     }
     const UserModule* find_module(uint64_t id) const {
         for (auto& m : modules) if (m.id == id) return &m;
@@ -209,6 +224,8 @@ int launch_f64_kstrue(LaunchEnv& E, const TraceArgs<double>& A, bool spin, hipSt
 int launch_f64_generic(LaunchEnv& E, const TraceArgs<double>& A, hipStream_t st);  // KS_REF / KS_TRUE / RTGR_USER
 int launch_f32_closed(LaunchEnv& E, const TraceArgs<float>& A, bool spin, hipStream_t st);  // all three built-ins
 int launch_f32_generic(LaunchEnv& E, const TraceArgs<float>& A, hipStream_t st);
+int launch_f64_grid(LaunchEnv& E, const TraceArgs<double>& A, hipStream_t st);   // RTGR_GRID (tu_f64_grid.hip)
+int launch_f32_grid(LaunchEnv& E, const TraceArgs<float>& A, hipStream_t st);
 
 // ---- small kernels (rtgr_misc.hip) -------------------------------------------------------------------------------------
 int misc_canvas_f64(const DevScene<double>& sc, const DevCamera<double>& cam, uint64_t ni, uint64_t nj, uint64_t j0,

@@ -348,6 +348,11 @@ RTGR_DEV void metric_plain(const DevScene<R>& sc, const R x[4], R g[4][4]) {
         return;
     }
 #endif
+    if (sc.metric == (uint32_t)RTGR_GRID) {
+        R dg[4][4][4];   // (not read: the camera needs g only)
+        grid_metric<R>(sc.grid, x, g, dg);
+        return;
+    }
     // built-ins are η + f k k
     R f = R(0), kk[4] = {R(1), R(0), R(0), R(0)};
     if (sc.metric != RTGR_MINKOWSKI) {

@@ -225,6 +225,8 @@ int scene_check(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* o
 int code_object_audit(const char* code_object_path, int* found, char* report, uint64_t report_len);
 int listing_repair(const char* listing_path, const char* repaired_path, int* blocks);
 int user_metric_loaded(rtgr_context* ctx, uint64_t id);
+int grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out);
+int grid_metric_unload(rtgr_context* ctx, uint64_t id);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 

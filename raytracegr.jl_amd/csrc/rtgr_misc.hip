@@ -30,7 +30,8 @@ __global__ __launch_bounds__(256) void eval_metric_kernel(DevScene<R> sc, const 
     if (p >= n) return;
     R xx[4] = {x[4 * p], x[4 * p + 1], x[4 * p + 2], x[4 * p + 3]};
     R gg[4][4], dd[4][4][4];
-    dmetric_dev<R>(sc.metric, sc.M, sc.a, xx, gg, dd);
+    if (sc.metric == (uint32_t)RTGR_GRID) grid_metric<R>(sc.grid, xx, gg, dd);
+    else dmetric_dev<R>(sc.metric, sc.M, sc.a, xx, gg, dd);
     if (g) for (int q = 0; q < 16; q++) g[16 * p + q] = (&gg[0][0])[q];
     if (dg) for (int q = 0; q < 64; q++) dg[64 * p + q] = (&dd[0][0][0])[q];
     if (Gam) {
@@ -60,7 +61,10 @@ __global__ __launch_bounds__(256) void eval_geodesic_kernel(DevScene<R> sc, cons
     if (p >= n) return;
     R si[8], so[8];
     for (int c = 0; c < 8; c++) si[c] = s[8 * p + c];
-    if (path == 1) {
+    if (sc.metric == (uint32_t)RTGR_GRID) {   // every path: the grid RHS (the integrate loop's own, accel<…, GRID>)
+        for (int c = 0; c < 4; c++) so[c] = si[4 + c];
+        grid_accel<R>(sc.grid, si + 1, si + 4, so + 4);
+    } else if (path == 1) {
         generic_rhs<R>(sc.metric, sc.M, sc.a, si, so);
     } else {
         const bool spin = sc.a != R(0);

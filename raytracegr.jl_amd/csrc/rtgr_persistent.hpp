@@ -53,6 +53,15 @@
 #ifndef RTGR_WAVES_PER_SIMD_GENERIC_F32
 #define RTGR_WAVES_PER_SIMD_GENERIC_F32 3  // generic dual-number RHS in Float32: half the register bytes of the f64 kernel
 #endif
+// metric sampled on a grid (RTGR_GRID): the interpolant's 40 accumulators + a row of 40 samples beside the integrator's
+// state want ~400 registers; at the generic kernels' 2 (Float64) / 3 (Float32) waves per SIMD the passes spilled 600-850 / 420-550 bytes
+// per lane to scratch (tests/test_build_checks.py allows 64), at ONE wave they keep everything in VGPRs + AGPRs with no scratch
+#ifndef RTGR_WAVES_PER_SIMD_GRID
+#define RTGR_WAVES_PER_SIMD_GRID 1
+#endif
+#ifndef RTGR_WAVES_PER_SIMD_GRID_F32
+#define RTGR_WAVES_PER_SIMD_GRID_F32 1
+#endif
 #ifndef RTGR_WAVES_PER_SIMD_FAR
 #define RTGR_WAVES_PER_SIMD_FAR 3  // the FAR pass has no sample-point arrays: <=168 registers, three waves per SIMD
 #endif
@@ -159,6 +168,14 @@ RTGR_DEV void flush_early(const IntegrateArgs<R>& A, const uint32_t* buf, uint32
 // ---------------------------------------------------------------------------------------------------------------------
 // The kernel body is a device function so that run-time generated units (user metrics, rtgr_user_unit.hip.in) can
 // wrap it in extern "C" kernels of their own.
+// the wave-uniform metric constants of an instantiation (the grid's descriptor only where the grid RHS reads it)
+template <class R, int METRIC>
+RTGR_DEV MetricK<R> scene_consts(const DevScene<R>& sc) {
+    MetricK<R> k = metric_consts<R>(sc.M, sc.a);
+    if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) k.grid = sc.grid;
+    return k;
+}
+
 template <class R, int METRIC, bool SPIN, bool NPTS10, int MODE, bool LDSK = false>
 RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
     using N = Tsit5N<R>;
@@ -175,7 +192,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
     }
     const uint64_t total = A.n + n_early;
     unsigned long long* const queue = (MODE == MODE_NEAR) ? A.ctrl + 1 : A.ctrl;
-    const MetricK<R> MK = metric_consts<R>(A.sc.M, A.sc.a);
+    const MetricK<R> MK = scene_consts<R, METRIC>(A.sc);
     const R reltol = A.opt.reltol, abstol = A.opt.abstol;
     const R t0 = A.opt.lambda0, t1 = A.opt.lambda1, dtmax = uniform_(A.opt.lambda1 - A.opt.lambda0);
     const float igamma = 1.0f / 0.9f, qmin_inv = 5.0f, qmax_inv = 0.1f;
@@ -486,7 +503,13 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                 bool is_event = false, is_interior = false, handed = false, hand_back = false;
                 R top = R(0);
                 R cc[4][4];  // position polynomial of this step (set when the step is accepted; read only on events)
-                if (EEst2 != EEst2) {
+                // RTGR_GRID: every accepted step that ends outside the grid's valid box ends its ray (below), so a running ray outside
+                // the box is one that STARTED there: it ends as RTGR_RAY_OUTSIDE before its first step
+                bool start_outside = false;
+                if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) start_outside = !grid_inside<R>(MK.grid, x + 1);
+                if (start_outside) {
+                    done = RTGR_RAY_OUTSIDE;
+                } else if (EEst2 != EEst2) {
                     done = RTGR_RAY_NAN;
                 } else {
                     // ---- PI controller in log2 space: q = EEst^β1 / qold^β2 / γ ----------------------
@@ -753,7 +776,10 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                             commit = true;
                             t = tnew;
                             dt = rmin(dtmax, dtnew);
-                            if (!(t < t1)) done = RTGR_RAY_LAMBDA1;
+                            bool outside = false;   // RTGR_GRID: the step ended outside the valid box (the scan found no event in it)
+                            if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) outside = !grid_inside<R>(MK.grid, xn + 1);
+                            if (outside) done = RTGR_RAY_OUTSIDE;
+                            else if (!(t < t1)) done = RTGR_RAY_LAMBDA1;
                             else if (nacc + nrej >= A.opt.max_steps) done = RTGR_RAY_MAXSTEPS;
                             else if (!(t + dt > t)) done = RTGR_RAY_DTMIN;
                             else if (MODE == MODE_NEAR && A.allow_handback && safe_streak >= 2u && (nacc - nacc0) >= A.handback_after) hand_back = true;
@@ -911,7 +937,8 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
 #undef KL
 #undef KSTORE
 template <class R, int METRIC, bool SPIN, bool NPTS10, int MODE>
-__global__ __launch_bounds__(64, METRIC >= RTGR_GENERIC_BASE ? (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GENERIC : RTGR_WAVES_PER_SIMD_GENERIC_F32)
+__global__ __launch_bounds__(64, METRIC == RTGR_GENERIC_BASE + RTGR_GRID ? (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GRID : RTGR_WAVES_PER_SIMD_GRID_F32)
+                                 : METRIC >= RTGR_GENERIC_BASE ? (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GENERIC : RTGR_WAVES_PER_SIMD_GENERIC_F32)
                                  : (MODE == MODE_FAR ? (sizeof(R) == 8 ? (SPIN ? RTGR_WAVES_PER_SIMD_SPIN_FAR : RTGR_WAVES_PER_SIMD_FAR) : 4)
                                                      : (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD : RTGR_WAVES_PER_SIMD_F32)))
 void integrate_kernel(const IntegrateArgs<R> A) {
@@ -938,7 +965,7 @@ template <class R, int METRIC, bool SPIN>
 RTGR_DEV void prepare_body(const IntegrateArgs<R>& A) {
     const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = w < A.n;
-    const MetricK<R> MK = metric_consts<R>(A.sc.M, A.sc.a);
+    const MetricK<R> MK = scene_consts<R, METRIC>(A.sc);
     const R reltol = A.opt.reltol, abstol = A.opt.abstol, dtmax = A.opt.lambda1 - A.opt.lambda0;
     R x[4] = {R(0), R(1), R(0), R(0)}, u[4] = {R(-1), R(0), R(1), R(0)}, k1[4], k2[4];
     if (valid) {
