@@ -474,10 +474,10 @@ int rtgr_user_metric_unload(rtgr_context* ctx, uint64_t id); /* id 0: all */
  * RTGR_RAY_OUTSIDE with 0 accepted steps.  All entry points (device, host-pointer, frames in flight, sharded) and both pass
  * structures (FULL == FAR + NEAR bit for bit) take grid scenes; rtgr_make_canvas_*, the redshift output and rtgr_eval_metric_*
  * evaluate the interpolant (d_t g = 0), rtgr_eval_geodesic_* evaluates the grid RHS for every `path`.  Out of scope: user objects in
- * a grid scene (RTGR_ERR_BAD_ARG), time-dependent grids, several patches.
+ * a grid scene (RTGR_ERR_BAD_ARG), several patches.
  *   Lifetime: rtgr_grid_metric_unload makes the id unknown at once (a scene naming it fails with RTGR_ERR_BAD_ARG), but the device
  * memory is RETIRED, not freed — a hipGraph captured earlier may still replay it — until rtgr_trim / rtgr_destroy. */
-#define RTGR_GRID_MAX_SAMPLES (1ull << 28)   /* n[0]*n[1]*n[2] at most: 21.5 GB in Float64 + 10.7 GB in Float32 per device */
+#define RTGR_GRID_MAX_SAMPLES (1ull << 28)   /* n[0]*n[1]*n[2] (4-D: n[0]*n[1]*n[2]*n[3]) at most: 21.5 GB in Float64 + 10.7 GB in Float32 per device */
 typedef struct rtgr_grid {
     uint32_t n[3];      /* samples along x, y, z; each >= 4 */
     uint32_t pad;       /* 0 */
@@ -486,6 +486,28 @@ typedef struct rtgr_grid {
 } rtgr_grid;            /* 64 bytes */
 int rtgr_grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out);
 int rtgr_grid_metric_unload(rtgr_context* ctx, uint64_t id);
+
+/* A TIME-DEPENDENT metric sampled on a uniform 4-D grid (an evolving spacetime, slice after slice):
+ *   grid->n[4]        samples along t, x, y, z (each >= 4);   grid->origin[4] (t, x, y, z) of sample (0, 0, 0, 0);  grid->spacing[4] > 0
+ *   g                 n[0]*n[3]*n[2]*n[1]*10 doubles, TIME SLOWEST: sample (l, k, j, i) — t, z, y, x — at
+ *                     g[(((l*n_z + k)*n_y + j)*n_x + i)*10 + c]; every time slice is one block in rtgr_grid_metric_load's layout
+ * The same checks as rtgr_grid_metric_load (the flattened index of the first bad sample in rtgr_last_error()), at most
+ * RTGR_GRID_MAX_SAMPLES samples in all (n_t n_x n_y n_z), Float64 and Float32 copies on every device; ids come from the same counter,
+ * a scene selects the grid the same way (metric = RTGR_GRID, user_metric = id) and rtgr_grid_metric_unload unloads either kind.
+ *   Interpolant: the tensor product of the Catmull-Rom weights above on all four axes; d_t g from the time weights' derivatives x 1/h_t,
+ * g and all four first derivatives from the same polynomial.  Summation order: per spatial row, the four time slices are blended first,
+ * relative to the time-centre slice s_1 — b = (s_1 - ref) + sum_l w_t,l (s_l - s_1), b' = sum_l w'_t,l (s_l - s_1) — and b is then
+ * walked like the 3-D stencil (ref = the centre sample of the centre slice).  So a grid whose slices are all equal gives g and
+ * d_x,y,z g bit for bit as the 3-D grid of one slice, and d_t g = 0 exactly.  The VALID BOX is s in [1, n - 2] on all four axes:
+ * an accepted step that ends outside it — in time too — ends the ray as RTGR_RAY_OUTSIDE, and a ray whose start (camera) time is
+ * outside ends as RTGR_RAY_OUTSIDE with 0 accepted steps.  rtgr_make_canvas_*, redshift, rtgr_eval_metric_* and rtgr_eval_geodesic_*
+ * evaluate the interpolant at the point's own t. */
+typedef struct rtgr_grid4 {
+    uint32_t n[4];      /* samples along t, x, y, z; each >= 4 */
+    double origin[4];   /* (t, x, y, z) of sample (0,0,0,0) */
+    double spacing[4];  /* > 0 */
+} rtgr_grid4;           /* 80 bytes: n 0, origin 16, spacing 48 */
+int rtgr_grid4_metric_load(rtgr_context* ctx, const rtgr_grid4* grid, const double* g, uint64_t* id_out);
 
 /* ---- user objects: `Object{T}` is an OPEN abstract type (src/RayTraceGR.jl:374-389) ------------------------------------------
  * The reference's second extension point: any `struct MyThing{T} <: Object{T}` with the two methods

@@ -24,6 +24,7 @@
 #   RtgrCounters     64   rays 0, accepted 8, rejected 16, rhs_evals 24, events 32, events_interior 40, not_finished 48, reserved 56
 #   RtgrRayOutputs   64   state_end 0, lambda_end 8, status 16, hit 24, n_accept 32, n_reject 40, redshift 48, hit32 56
 #   RtgrGrid         64   n 0, pad 12, origin 16, spacing 40
+#   RtgrGrid4        80   n 0, origin 16, spacing 48
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64          (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -88,6 +89,11 @@ struct RtgrGrid                # a metric sampled on a uniform grid (rtgr_grid_m
     pad::UInt32
     origin::NTuple{3,Float64}   # (x, y, z) of sample (0, 0, 0)
     spacing::NTuple{3,Float64}
+end
+struct RtgrGrid4               # a time-dependent metric sampled on a uniform 4-D grid (rtgr_grid4_metric_load)
+    n::NTuple{4,UInt32}         # samples along t, x, y, z; each >= 4
+    origin::NTuple{4,Float64}   # (t, x, y, z) of sample (0, 0, 0, 0)
+    spacing::NTuple{4,Float64}
 end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
@@ -315,16 +321,27 @@ end
 """
     GridMetric(g, origin, spacing)
 
-A stationary metric given as SAMPLES on a uniform grid — a numerically computed spacetime (include/rtgr.h "metrics sampled on
-a grid"): `g` is a 10 x nx x ny x nz Array{Float64} (the upper triangle tt tx ty tz xx xy xz yy yz zz first, then x fastest — the
-C layout, column-major), `origin` and `spacing` 3-tuples.  Uploaded to the context on first use (`rtgr_grid_metric_load`); rays that
-leave the grid's valid box end with status RTGR_RAY_OUTSIDE.  `unload(m, ctx)` releases the id (`rtgr_grid_metric_unload`).
+A metric given as SAMPLES on a uniform grid — a numerically computed spacetime (include/rtgr.h "metrics sampled on a grid"):
+stationary, `g` is a 10 x nx x ny x nz Array{Float64} (the upper triangle tt tx ty tz xx xy xz yy yz zz first, then x fastest — the
+C layout, column-major), `origin` and `spacing` 3-tuples (x, y, z); time-dependent, `g` is 10 x nx x ny x nz x nt (time slowest) and
+`origin` / `spacing` are 4-tuples (t, x, y, z).  Uploaded to the context on first use (`rtgr_grid_metric_load` /
+`rtgr_grid4_metric_load`); rays that leave the grid's valid box — in t too — end with status RTGR_RAY_OUTSIDE.  `unload(m, ctx)`
+releases the id (`rtgr_grid_metric_unload`).
 """
-struct GridMetric
-    g::Array{Float64,4}
-    origin::NTuple{3,Float64}
-    spacing::NTuple{3,Float64}
+struct GridMetric{N,A}         # N = 4: stationary (3 axes), N = 5: time-dependent (A = 4 axes)
+    g::Array{Float64,N}
+    origin::NTuple{A,Float64}
+    spacing::NTuple{A,Float64}
     ids::Dict{Ptr{Cvoid},UInt64}
+end
+function GridMetric(g::AbstractArray{<:Real,5}, origin, spacing)
+    size(g, 1) == 10 || error("GridMetric: g must be 10 x nx x ny x nz x nt")
+    all(size(g)[2:5] .>= 4) || error("GridMetric: at least 4 samples per axis")
+    length(origin) == 4 && length(spacing) == 4 || error("GridMetric: a 4-D grid takes (t, x, y, z) origin and spacing")
+    length(g) <= 10 * (1 << 28) || error("GridMetric: more than RTGR_GRID_MAX_SAMPLES (2^28) samples")
+    all(v -> v - v == 0, g) || error("GridMetric: non-finite sample")
+    all(h -> h > 0, spacing) || error("GridMetric: spacing must be > 0")
+    GridMetric(Array{Float64,5}(g), Tuple(Float64.(origin)), Tuple(Float64.(spacing)), Dict{Ptr{Cvoid},UInt64}())
 end
 function GridMetric(g::AbstractArray{<:Real,4}, origin, spacing)
     size(g, 1) == 10 || error("GridMetric: g must be 10 x nx x ny x nz")
@@ -336,8 +353,13 @@ end
 function module_id(m::GridMetric, ctx)
     id = Ref{UInt64}(get(m.ids, handle(ctx), UInt64(0)))
     if id[] == 0   # first use in this context (or unloaded since): upload
-        desc = Ref(RtgrGrid(UInt32.(size(m.g)[2:4]), UInt32(0), m.origin, m.spacing))
-        check(ccall((:rtgr_grid_metric_load, librtgr), Cint, (Ctx, Ptr{RtgrGrid}, Ptr{Float64}, Ptr{UInt64}), handle(ctx), desc, m.g, id))
+        if length(m.origin) == 4   # time-dependent: n = (nt, nx, ny, nz), the time axis is the array's last
+            desc4 = Ref(RtgrGrid4(UInt32.((size(m.g, 5), size(m.g, 2), size(m.g, 3), size(m.g, 4))), m.origin, m.spacing))
+            check(ccall((:rtgr_grid4_metric_load, librtgr), Cint, (Ctx, Ptr{RtgrGrid4}, Ptr{Float64}, Ptr{UInt64}), handle(ctx), desc4, m.g, id))
+        else
+            desc = Ref(RtgrGrid(UInt32.(size(m.g)[2:4]), UInt32(0), m.origin, m.spacing))
+            check(ccall((:rtgr_grid_metric_load, librtgr), Cint, (Ctx, Ptr{RtgrGrid}, Ptr{Float64}, Ptr{UInt64}), handle(ctx), desc, m.g, id))
+        end
         m.ids[handle(ctx)] = id[]
     end
     id[]

@@ -12,7 +12,7 @@ RTGR_OBJECTS_LIMIT = 1 << 20
 RTGR_ABI_VERSION = 4
 RTGR_MAX_DEVICES = 16
 RTGR_MAX_SOURCES = 16
-RTGR_GRID_MAX_SAMPLES = 1 << 28  # n[0]*n[1]*n[2] of a grid metric at most
+RTGR_GRID_MAX_SAMPLES = 1 << 28  # n[0]*n[1]*n[2] (4-D: n[0]*n[1]*n[2]*n[3]) of a grid metric at most
 
 # enum rtgr_metric
 MINKOWSKI, KS_REF, KS_TRUE, USER, GRID = 0, 1, 2, 3, 4
@@ -77,6 +77,10 @@ class rtgr_grid(C.Structure):
     _fields_ = [("n", C.c_uint32 * 3), ("pad", C.c_uint32), ("origin", C.c_double * 3), ("spacing", C.c_double * 3)]
 
 
+class rtgr_grid4(C.Structure):
+    _fields_ = [("n", C.c_uint32 * 4), ("origin", C.c_double * 4), ("spacing", C.c_double * 4)]   # axes t, x, y, z
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -98,7 +102,7 @@ EXPORTS = [
     "rtgr_user_unit_compile", "rtgr_user_unit_build", "rtgr_user_unit_info", "rtgr_scene_check",
     "rtgr_eval_objects_f64", "rtgr_eval_objects_f32", "rtgr_user_source_join",
     "rtgr_trace_frames_f64", "rtgr_trace_frames_f32", "rtgr_trace_frames_pixels_f64", "rtgr_trace_frames_pixels_f32",
-    "rtgr_grid_metric_load", "rtgr_grid_metric_unload",
+    "rtgr_grid_metric_load", "rtgr_grid_metric_unload", "rtgr_grid4_metric_load",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -169,6 +173,7 @@ def _declare(lib):
     lib.rtgr_user_metric_unload.argtypes = [ctx, u64]
     lib.rtgr_grid_metric_load.argtypes = [ctx, P(rtgr_grid), vp, P(u64)]
     lib.rtgr_grid_metric_unload.argtypes = [ctx, u64]
+    lib.rtgr_grid4_metric_load.argtypes = [ctx, P(rtgr_grid4), vp, P(u64)]
     lib.rtgr_user_metric_loaded.argtypes = [ctx, u64]
     lib.rtgr_code_object_audit.argtypes = [C.c_char_p, P(i32), C.c_char_p, u64]
     lib.rtgr_user_metric_build.argtypes = [C.c_char_p, i32, C.c_char_p]

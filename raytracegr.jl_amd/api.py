@@ -60,27 +60,32 @@ _UPPER = [(0, 0), (0, 1), (0, 2), (0, 3), (1, 1), (1, 2), (1, 3), (2, 2), (2, 3)
 
 
 class GridMetric:
-    """A stationary metric given as SAMPLES on a uniform 3-D grid (RTGR_GRID, include/rtgr.h) — a numerically computed spacetime
-    has no formula.  g: numpy array (nz, ny, nx, 10) of the upper triangle tt tx ty tz xx xy xz yy yz zz, or (nz, ny, nx, 4, 4)
-    (the upper triangle is taken); origin = (x, y, z) of sample [0, 0, 0]; spacing = (hx, hy, hz) (a scalar: the same on every
-    axis).  Values and first derivatives are interpolated on the device (tricubic Catmull-Rom) inside the integrate loop; rays that
-    leave the valid box end with status RAY_OUTSIDE.  Uploaded lazily, once per context; calling it evaluates g on the GPU."""
+    """A metric given as SAMPLES on a uniform grid (RTGR_GRID, include/rtgr.h) — a numerically computed spacetime has no formula.
+    Stationary, 3-D: g is a numpy array (nz, ny, nx, 10) of the upper triangle tt tx ty tz xx xy xz yy yz zz, or (nz, ny, nx, 4, 4)
+    (the upper triangle is taken); origin = (x, y, z) of sample [0, 0, 0]; spacing = (hx, hy, hz) (a scalar: the same on every axis).
+    Time-dependent, 4-D: g is (nt, nz, ny, nx, 10) or (nt, nz, ny, nx, 4, 4), time slowest; origin = (t, x, y, z), spacing =
+    (ht, hx, hy, hz) (rtgr_grid4_metric_load).  Values and first derivatives are interpolated on the device (tri- / tetracubic
+    Catmull-Rom) inside the integrate loop; rays that leave the valid box — in t too — end with status RAY_OUTSIDE.  Uploaded lazily,
+    once per context; calling it evaluates g on the GPU."""
     kind = _abi.GRID
     generic = False   # (grids always take the generic contraction; the scene's metric is plain RTGR_GRID)
     M = a = 0.0
 
     def __init__(self, g, origin, spacing, name="grid"):
         g = np.asarray(g)
-        if g.ndim == 5 and g.shape[3:] == (4, 4):
+        four = g.ndim == 6 or (g.ndim == 5 and g.shape[-1] == 10)   # (nt, nz, ny, nx, 4, 4) or (nt, nz, ny, nx, 10)
+        if g.ndim == (6 if four else 5) and g.shape[-2:] == (4, 4):
             g = np.stack([g[..., p, q] for p, q in _UPPER], axis=-1)
-        if g.ndim != 4 or g.shape[3] != 10:
-            raise ValueError(f"GridMetric: g must have shape (nz, ny, nx, 10) or (nz, ny, nx, 4, 4), got {g.shape}")
-        if min(g.shape[:3]) < 4:
-            raise ValueError(f"GridMetric: at least 4 samples per axis, got (nz, ny, nx) = {g.shape[:3]}")
-        if g.shape[0] * g.shape[1] * g.shape[2] > _abi.RTGR_GRID_MAX_SAMPLES:
+        dims = 4 if four else 3
+        if g.ndim != dims + 1 or g.shape[-1] != 10:
+            raise ValueError(f"GridMetric: g must have shape (nz, ny, nx, 10), (nz, ny, nx, 4, 4), (nt, nz, ny, nx, 10) or "
+                             f"(nt, nz, ny, nx, 4, 4), got {np.shape(g)}")
+        if min(g.shape[:dims]) < 4:
+            raise ValueError(f"GridMetric: at least 4 samples per axis, got {'(nt, nz, ny, nx)' if four else '(nz, ny, nx)'} = {g.shape[:dims]}")
+        if math.prod(g.shape[:dims]) > _abi.RTGR_GRID_MAX_SAMPLES:
             raise ValueError("GridMetric: more than RTGR_GRID_MAX_SAMPLES samples")
-        origin = np.broadcast_to(np.asarray(origin, np.float64), (3,)).copy()
-        spacing = np.broadcast_to(np.asarray(spacing, np.float64), (3,)).copy()
+        origin = np.broadcast_to(np.asarray(origin, np.float64), (dims,)).copy()
+        spacing = np.broadcast_to(np.asarray(spacing, np.float64), (dims,)).copy()
         if not np.all(np.isfinite(origin)) or not np.all(np.isfinite(spacing)) or not np.all(spacing > 0):
             raise ValueError(f"GridMetric: origin must be finite and spacing finite and > 0, got {origin}, {spacing}")
         self.g = np.ascontiguousarray(g, dtype=np.float64)
@@ -88,12 +93,14 @@ class GridMetric:
             bad = int(np.flatnonzero(~np.isfinite(self.g).all(axis=-1).ravel())[0])
             raise ValueError(f"GridMetric: sample {bad} (x fastest) holds a non-finite value")
         self.origin, self.spacing, self.__name__ = origin, spacing, name
-        self.n = (g.shape[2], g.shape[1], g.shape[0])   # (nx, ny, nz)
+        self.time_dependent = four
+        # in the order of origin / spacing: 3-D (nx, ny, nz), 4-D (nt, nx, ny, nz)
+        self.n = ((g.shape[0],) + g.shape[3:0:-1]) if four else g.shape[2::-1]
         self._ids = {}
 
     def box(self):
-        """the valid box ((x0, x1), (y0, y1), (z0, z1)): samples 1 .. n-2 of every axis"""
-        return tuple((self.origin[a] + self.spacing[a], self.origin[a] + (self.n[a] - 2) * self.spacing[a]) for a in range(3))
+        """the valid box, samples 1 .. n-2 of every axis: ((x0, x1), (y0, y1), (z0, z1)), 4-D: ((t0, t1), (x0, x1), (y0, y1), (z0, z1))"""
+        return tuple((self.origin[a] + self.spacing[a], self.origin[a] + (self.n[a] - 2) * self.spacing[a]) for a in range(len(self.n)))
 
     def module_id(self, ctx=None):
         """id of this grid in the context (uploaded on first use)"""
@@ -102,11 +109,17 @@ class GridMetric:
         if gid is not None:
             return gid
         lib = _lib()
-        desc = _abi.rtgr_grid()
-        for a in range(3):
-            desc.n[a], desc.origin[a], desc.spacing[a] = self.n[a], self.origin[a], self.spacing[a]
         out = C.c_uint64(0)
-        _abi.check(lib, lib.rtgr_grid_metric_load(ctx, C.byref(desc), self.g.ctypes.data, C.byref(out)))
+        if self.time_dependent:
+            desc = _abi.rtgr_grid4()
+            for a in range(4):
+                desc.n[a], desc.origin[a], desc.spacing[a] = self.n[a], self.origin[a], self.spacing[a]
+            _abi.check(lib, lib.rtgr_grid4_metric_load(ctx, C.byref(desc), self.g.ctypes.data, C.byref(out)))
+        else:
+            desc = _abi.rtgr_grid()
+            for a in range(3):
+                desc.n[a], desc.origin[a], desc.spacing[a] = self.n[a], self.origin[a], self.spacing[a]
+            _abi.check(lib, lib.rtgr_grid_metric_load(ctx, C.byref(desc), self.g.ctypes.data, C.byref(out)))
         self._ids[key] = out.value
         return out.value
 
@@ -123,21 +136,31 @@ class GridMetric:
         return f"GridMetric({self.__name__}, n={self.n}, origin={tuple(self.origin)}, spacing={tuple(self.spacing)})"
 
 
-def sample_metric(metric, origin, spacing, n, chunk=1 << 20):
+def sample_metric(metric, origin, spacing, n, chunk=1 << 20, t=None):
     """Samples any metric the library evaluates (built-in, UserMetric, GridMetric) on a uniform grid through rtgr_eval_metric_f64:
     n = (nx, ny, nz) points from origin with spacing (scalar or per axis), at t = 0.  Returns the (nz, ny, nx, 10) array GridMetric
-    takes.  Evaluated in chunks of `chunk` points."""
+    takes.  Evaluated in chunks of `chunk` points.
+    t = (t0, ht, nt): a time axis as well — the metric at the 4-D points (t0 + l ht, x, y, z); returns (nt, nz, ny, nx, 10)."""
     nx, ny, nz = (int(v) for v in n)
     origin = np.broadcast_to(np.asarray(origin, np.float64), (3,))
     spacing = np.broadcast_to(np.asarray(spacing, np.float64), (3,))
     z, y, x = np.meshgrid(*(origin[a] + spacing[a] * np.arange(m) for a, m in ((2, nz), (1, ny), (0, nx))), indexing="ij")
-    pts = np.stack([np.zeros(x.size), x.ravel(), y.ravel(), z.ravel()], axis=1)
-    out = np.empty((pts.shape[0], 10))
-    for s0 in range(0, pts.shape[0], chunk):
-        g, _, _ = _eval_metric(metric, pts[s0:s0 + chunk], want=(True, False, False))
-        g = g.reshape(-1, 4, 4)
-        out[s0:s0 + chunk] = np.stack([g[:, p, q] for p, q in _UPPER], axis=1)
-    return out.reshape(nz, ny, nx, 10)
+    times = [0.0]
+    if t is not None:
+        t0, ht, nt = float(t[0]), float(t[1]), int(t[2])
+        if nt < 1 or not np.isfinite(t0) or not np.isfinite(ht):
+            raise ValueError(f"sample_metric: t must be (t0, ht, nt) with nt >= 1, got {t}")
+        times = t0 + ht * np.arange(nt)
+    out = np.empty((len(times), x.size, 10))
+    for l, tl in enumerate(times):
+        pts = np.stack([np.full(x.size, tl), x.ravel(), y.ravel(), z.ravel()], axis=1)
+        for s0 in range(0, pts.shape[0], chunk):
+            g, _, _ = _eval_metric(metric, pts[s0:s0 + chunk], want=(True, False, False))
+            g = g.reshape(-1, 4, 4)
+            out[l, s0:s0 + chunk] = np.stack([g[:, p, q] for p, q in _UPPER], axis=1)
+    if t is None:
+        return out[0].reshape(nz, ny, nx, 10)
+    return out.reshape(len(times), nz, ny, nx, 10)
 
 
 # ---- objects (src/RayTraceGR.jl:374-428) ------------------------------------------------------------------------

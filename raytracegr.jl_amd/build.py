@@ -25,7 +25,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 UNITS = ["tu_f64_ksref.hip", "tu_f64_kstrue.hip", "tu_f64_generic.hip", "tu_f64_mink.hip", "tu_f32_closed.hip",
-         "tu_f32_generic.hip", "tu_f64_grid.hip", "tu_f32_grid.hip", "rtgr_misc.hip", "rtgr_context.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip",
+         "tu_f32_generic.hip", "tu_f64_grid.hip", "tu_f32_grid.hip", "tu_f64_grid4.hip", "tu_f32_grid4.hip", "rtgr_misc.hip", "rtgr_context.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip",
          "rtgr_units.hip", "rtgr_grid.hip", "rtgr_abi.hip"]
 # the device-side headers: what the KERNELS are made of (bench.py keys its roofline profile on their hash)
 KERNEL_HEADERS = ["rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_integrator.hpp", "rtgr_persistent.hpp", "rtgr_packed_f32.hpp",

@@ -58,6 +58,7 @@ int rtgr_user_metric_build(const char* source, int stationary, const char* code_
 int rtgr_user_metric_unload(rtgr_context* ctx, uint64_t id) { return rtgr::api::user_metric_unload(ctx, id); }
 int rtgr_grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out) { return rtgr::api::grid_metric_load(ctx, grid, g, id_out); }
 int rtgr_grid_metric_unload(rtgr_context* ctx, uint64_t id) { return rtgr::api::grid_metric_unload(ctx, id); }
+int rtgr_grid4_metric_load(rtgr_context* ctx, const rtgr_grid4* grid, const double* g, uint64_t* id_out) { return rtgr::api::grid4_metric_load(ctx, grid, g, id_out); }
 int rtgr_user_unit_compile(rtgr_context* ctx, const char* source, int stationary, const rtgr_scene* built_for, uint64_t* id_out) { return rtgr::api::user_unit_compile(ctx, source, stationary, built_for, id_out); }
 int rtgr_user_unit_build(const char* source, int stationary, const rtgr_scene* built_for, const char* code_object_path) { return rtgr::api::user_unit_build(source, stationary, built_for, code_object_path); }
 int rtgr_user_source_join(const char* const* sources, const uint32_t* ntypes, int n, char* out, uint64_t cap, uint64_t* need) { return rtgr::api::user_source_join(sources, ntypes, n, out, cap, need); }

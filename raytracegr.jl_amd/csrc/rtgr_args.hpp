@@ -37,6 +37,20 @@ struct DevGrid {
     R hi[3];            // n - 3: the highest cell index the interpolant clamps to
     R top[3];           // n - 2: upper edge of the valid box in index units (the lower edge is 1)
 };
+// A TIME-DEPENDENT grid (rtgr_grid4_metric_load): the scene's metric is RTGR_GRID, the device scene's RTGR_GRID4 (internal, below).
+// DevGrid describes its spatial axes as for a 3-D grid (g = slice 0); the time axis' descriptor does not travel in the kernel
+// arguments — DevScene's layout is every kernel's, and growing it would move every argument behind it — but in the GRID4_HEADER bytes
+// in front of the samples on the device, where scene_consts / grid4_time (rtgr_physics.hpp) read it once.
+constexpr uint32_t RTGR_GRID4 = 64;           // DevScene::metric of a 4-D grid; the instantiation is RTGR_GENERIC_BASE + RTGR_GRID4
+constexpr uint64_t GRID4_HEADER = 64;         // bytes of the DevGridTime block before the first sample (keeps the samples 64-byte aligned)
+template <class R>
+struct DevGridTime {
+    uint64_t st;        // scalars between neighbouring time slices (10 n_x n_y n_z)
+    R origin;           // t of slice 0
+    R inv_h;            // 1 / h_t
+    R hi;               // n_t - 3
+    R top;              // n_t - 2
+};
 
 template <class R>
 struct DevScene {

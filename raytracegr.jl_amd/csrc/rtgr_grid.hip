@@ -1,4 +1,4 @@
-// rtgr_grid.hip — metrics sampled on a grid (RTGR_GRID, include/rtgr.h): load (checks, upload to every device of the context in
+// rtgr_grid.hip — metrics sampled on a grid (RTGR_GRID, include/rtgr.h; 3-D and time-dependent 4-D): load (checks, upload to every device of the context in
 // Float64 and Float32) and unload (retire: a hipGraph captured earlier may still replay the samples; rtgr_trim frees them).  Host code
 // only: the interpolant is rtgr_physics.hpp's (grid_eval), the kernels are tu_f64_grid.hip's / tu_f32_grid.hip's.
 #include <atomic>
@@ -22,23 +22,25 @@ static long double det_upper(const double* c) {
     return s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
 }
 
-int api::grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
-    if (!grid || !g || !id_out) return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_load: NULL argument");
-    if (grid->pad != 0) return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_load: rtgr_grid.pad must be 0");
+// The load of either kind: n / origin / spacing of the spatial axes (x, y, z), nt = 0 for a 3-D grid or the time axis of a 4-D one.
+// Checks every sample, then uploads Float64 and Float32 copies to every device (a 4-D table behind the GRID4_HEADER bytes of its
+// time axis' descriptor, rtgr_args.hpp) and publishes the table under a fresh id.
+static int grid_load(rtgr_context* c, const char* who, const uint32_t n[3], const double origin[3], const double spacing[3], uint32_t nt,
+                     double origin_t, double spacing_t, const double* g, uint64_t* id_out) {
     uint64_t npts = 1;
-    for (int ax = 0; ax < 3; ax++) {
-        if (grid->n[ax] < 4u || grid->n[ax] > (1u << 20))
-            return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_load: n[" + std::to_string(ax) + "] = " + std::to_string(grid->n[ax]) +
-                                          ": each axis needs 4 .. 2^20 samples");
-        if (!(grid->spacing[ax] > 0.0) || !std::isfinite(grid->spacing[ax]) || !std::isfinite(grid->origin[ax]))
-            return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_load: spacing must be finite and > 0, origin finite (axis " + std::to_string(ax) + ")");
-        npts *= grid->n[ax];
+    for (int ax = 0; ax < 4; ax++) {
+        if (ax == 3 && !nt) break;
+        const uint32_t na = ax < 3 ? n[ax] : nt;
+        const double o = ax < 3 ? origin[ax] : origin_t, h = ax < 3 ? spacing[ax] : spacing_t;
+        const std::string name = nt ? std::to_string(ax < 3 ? ax + 1 : 0) : std::to_string(ax);   // (4-D: axes are numbered t, x, y, z)
+        if (na < 4u || na > (1u << 20))
+            return fail(RTGR_ERR_BAD_ARG, std::string(who) + ": n[" + name + "] = " + std::to_string(na) + ": each axis needs 4 .. 2^20 samples");
+        if (!(h > 0.0) || !std::isfinite(h) || !std::isfinite(o))
+            return fail(RTGR_ERR_BAD_ARG, std::string(who) + ": spacing must be finite and > 0, origin finite (axis " + name + ")");
+        if (npts <= RTGR_GRID_MAX_SAMPLES) npts *= na;   // (stops growing past the cap: <= 2^28 x 2^20, no uint64_t overflow on four axes)
     }
     if (npts > RTGR_GRID_MAX_SAMPLES)
-        return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_load: " + std::to_string(npts) + " samples, more than RTGR_GRID_MAX_SAMPLES");
+        return fail(RTGR_ERR_BAD_ARG, std::string(who) + ": " + std::to_string(npts) + " samples, more than RTGR_GRID_MAX_SAMPLES");
     // every sample finite and Lorentzian-signed (det g < 0; a transposed layout fails this at once), and the Float32 copy
     std::vector<float> g32((size_t)npts * 10);
     for (uint64_t p = 0; p < npts; p++) {
@@ -46,13 +48,27 @@ int api::grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double
         bool finite = true;
         for (int k = 0; k < 10; k++) { finite = finite && std::isfinite(v[k]); g32[p * 10 + k] = (float)v[k]; }
         if (!finite || !(det_upper(v) < 0.0L)) {
-            const uint64_t i = p % grid->n[0], j = (p / grid->n[0]) % grid->n[1], k = p / ((uint64_t)grid->n[0] * grid->n[1]);
-            return fail(RTGR_ERR_BAD_ARG, std::string("rtgr_grid_metric_load: sample ") + std::to_string(p) + " (i, j, k) = (" + std::to_string(i) +
-                                          ", " + std::to_string(j) + ", " + std::to_string(k) + ") " +
-                                          (finite ? "has det g >= 0 (not a Lorentzian metric: components in the order tt tx ty tz xx xy xz yy yz zz, x fastest?)"
+            const uint64_t i = p % n[0], j = (p / n[0]) % n[1], k = (p / ((uint64_t)n[0] * n[1])) % n[2];
+            const uint64_t l = p / ((uint64_t)n[0] * n[1] * n[2]);
+            return fail(RTGR_ERR_BAD_ARG, std::string(who) + ": sample " + std::to_string(p) +
+                                          (nt ? " (l, k, j, i) = (" + std::to_string(l) + ", " : std::string(" (i, j, k) = (")) +
+                                          (nt ? std::to_string(k) + ", " + std::to_string(j) + ", " + std::to_string(i)
+                                              : std::to_string(i) + ", " + std::to_string(j) + ", " + std::to_string(k)) + ") " +
+                                          (finite ? (nt ? "has det g >= 0 (not a Lorentzian metric: components in the order tt tx ty tz xx xy xz yy yz zz, x fastest, t slowest?)"
+                                                        : "has det g >= 0 (not a Lorentzian metric: components in the order tt tx ty tz xx xy xz yy yz zz, x fastest?)")
                                                   : "holds a non-finite value"));
         }
     }
+    // a 4-D table starts with its time axis' descriptor (DevGridTime, read by the kernels), in each scalar type
+    const size_t head = nt ? (size_t)GRID4_HEADER : 0;
+    DevGridTime<double> t64{};
+    DevGridTime<float> t32{};
+    if (nt) {
+        t64.st = t32.st = 10ull * n[0] * n[1] * n[2];
+        t64.origin = origin_t; t64.inv_h = 1.0 / spacing_t; t64.hi = (double)(nt - 3u); t64.top = (double)(nt - 2u);
+        t32.origin = (float)t64.origin; t32.inv_h = (float)t64.inv_h; t32.hi = (float)t64.hi; t32.top = (float)t64.top;
+    }
+    static_assert(sizeof(DevGridTime<double>) <= GRID4_HEADER && sizeof(DevGridTime<float>) <= GRID4_HEADER, "GRID4_HEADER");
     const size_t b64 = (size_t)npts * 10 * sizeof(double), b32 = (size_t)npts * 10 * sizeof(float);
     std::lock_guard<std::mutex> load_lock(c->modules_mu);   // (units and grids are loaded / unloaded under the same lock)
     uint64_t id = 0;
@@ -79,14 +95,17 @@ int api::grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double
         if (!guard.ok) { release(); return fail(RTGR_ERR_HIP, "hipSetDevice failed"); }
         GridTable& t = made[k];
         t.id = id;
-        for (int ax = 0; ax < 3; ax++) { t.n[ax] = grid->n[ax]; t.origin[ax] = grid->origin[ax]; t.spacing[ax] = grid->spacing[ax]; }
-        hipError_t e = hipMalloc(&t.d64, b64);
-        if (e == hipSuccess) e = hipMalloc(&t.d32, b32);
-        if (e == hipSuccess) e = hipMemcpy(t.d64, g, b64, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(t.d32, g32.data(), b32, hipMemcpyHostToDevice);
+        for (int ax = 0; ax < 3; ax++) { t.n[ax] = n[ax]; t.origin[ax] = origin[ax]; t.spacing[ax] = spacing[ax]; }
+        t.nt = nt; t.origin_t = origin_t; t.spacing_t = spacing_t;
+        hipError_t e = hipMalloc(&t.d64, head + b64);
+        if (e == hipSuccess) e = hipMalloc(&t.d32, head + b32);
+        if (e == hipSuccess && nt) e = hipMemcpy(t.d64, &t64, sizeof t64, hipMemcpyHostToDevice);
+        if (e == hipSuccess && nt) e = hipMemcpy(t.d32, &t32, sizeof t32, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy((char*)t.d64 + head, g, b64, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy((char*)t.d32 + head, g32.data(), b32, hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             release();
-            return fail(RTGR_ERR_HIP, std::string("rtgr_grid_metric_load: upload to device ") + std::to_string(k) + ": " + hipGetErrorString(e));
+            return fail(RTGR_ERR_HIP, std::string(who) + ": upload to device " + std::to_string(k) + ": " + hipGetErrorString(e));
         }
     }
     for (size_t k = 0; k < c->devs.size(); k++) {
@@ -95,6 +114,24 @@ int api::grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double
     }
     *id_out = id;
     return RTGR_OK;
+}
+
+int api::grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if (!grid || !g || !id_out) return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_load: NULL argument");
+    if (grid->pad != 0) return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_load: rtgr_grid.pad must be 0");
+    return grid_load(c, "rtgr_grid_metric_load", grid->n, grid->origin, grid->spacing, 0u, 0.0, 0.0, g, id_out);
+}
+
+int api::grid4_metric_load(rtgr_context* ctx, const rtgr_grid4* grid, const double* g, uint64_t* id_out) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if (!grid || !g || !id_out) return fail(RTGR_ERR_BAD_ARG, "rtgr_grid4_metric_load: NULL argument");
+    return grid_load(c, "rtgr_grid4_metric_load", grid->n + 1, grid->origin + 1, grid->spacing + 1, grid->n[0], grid->origin[0],
+                     grid->spacing[0], g, id_out);
 }
 
 int api::grid_metric_unload(rtgr_context* ctx, uint64_t id) {

@@ -127,6 +127,10 @@ struct GridTable {
     void* d32 = nullptr;   // … the same as floats
     uint32_t n[3] = {0, 0, 0};
     double origin[3] = {0, 0, 0}, spacing[3] = {0, 0, 0};
+    // a time-dependent grid (rtgr_grid4_metric_load) when nt > 0: n / origin / spacing above are its spatial axes, and d64 / d32
+    // start with the GRID4_HEADER bytes of the time axis' DevGridTime (rtgr_args.hpp) before the samples (slice after slice)
+    uint32_t nt = 0;
+    double origin_t = 0, spacing_t = 0;
 };
 // pipeline workspace of one (device, stream)
 struct StreamState {
@@ -226,6 +230,8 @@ int launch_f32_closed(LaunchEnv& E, const TraceArgs<float>& A, bool spin, hipStr
 int launch_f32_generic(LaunchEnv& E, const TraceArgs<float>& A, hipStream_t st);
 int launch_f64_grid(LaunchEnv& E, const TraceArgs<double>& A, hipStream_t st);   // RTGR_GRID (tu_f64_grid.hip)
 int launch_f32_grid(LaunchEnv& E, const TraceArgs<float>& A, hipStream_t st);
+int launch_f64_grid4(LaunchEnv& E, const TraceArgs<double>& A, hipStream_t st);   // a time-dependent grid (tu_f64_grid4.hip)
+int launch_f32_grid4(LaunchEnv& E, const TraceArgs<float>& A, hipStream_t st);
 
 // ---- small kernels (rtgr_misc.hip) -------------------------------------------------------------------------------------
 int misc_canvas_f64(const DevScene<double>& sc, const DevCamera<double>& cam, uint64_t ni, uint64_t nj, uint64_t j0,

@@ -227,6 +227,7 @@ int listing_repair(const char* listing_path, const char* repaired_path, int* blo
 int user_metric_loaded(rtgr_context* ctx, uint64_t id);
 int grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out);
 int grid_metric_unload(rtgr_context* ctx, uint64_t id);
+int grid4_metric_load(rtgr_context* ctx, const rtgr_grid4* grid, const double* g, uint64_t* id_out);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 

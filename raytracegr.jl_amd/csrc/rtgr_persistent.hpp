@@ -44,6 +44,9 @@
 #ifndef RTGR_LDSK_GENERIC
 #define RTGR_LDSK_GENERIC 0   // generic RHS kernels keep k[1..5] in LDS (experiment: see DESIGN §4.2 "LDS stage storage")
 #endif
+#ifndef RTGR_LDSK_GRID4
+#define RTGR_LDSK_GRID4 1     // the time-dependent grid's Float64 kernels keep k[1..5] in LDS: beside the 4-D interpolant they spill otherwise (§4.11)
+#endif
 #ifndef RTGR_LDSK_SPIN_FAR
 #define RTGR_LDSK_SPIN_FAR 0  // the a != 0 FAR pass keeps k[1..5] in LDS (experiment, with RTGR_WAVES_PER_SIMD_SPIN_FAR=4)
 #endif
@@ -61,6 +64,13 @@
 #endif
 #ifndef RTGR_WAVES_PER_SIMD_GRID_F32
 #define RTGR_WAVES_PER_SIMD_GRID_F32 1
+#endif
+// time-dependent grid (RTGR_GRID4): four slices of a row in flight and 50 accumulators — one wave per SIMD as well
+#ifndef RTGR_WAVES_PER_SIMD_GRID4
+#define RTGR_WAVES_PER_SIMD_GRID4 1
+#endif
+#ifndef RTGR_WAVES_PER_SIMD_GRID4_F32
+#define RTGR_WAVES_PER_SIMD_GRID4_F32 1
 #endif
 #ifndef RTGR_WAVES_PER_SIMD_FAR
 #define RTGR_WAVES_PER_SIMD_FAR 3  // the FAR pass has no sample-point arrays: <=168 registers, three waves per SIMD
@@ -173,6 +183,12 @@ template <class R, int METRIC>
 RTGR_DEV MetricK<R> scene_consts(const DevScene<R>& sc) {
     MetricK<R> k = metric_consts<R>(sc.M, sc.a);
     if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) k.grid = sc.grid;
+    if constexpr (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) {
+        k.grid = sc.grid;
+        k.gt = grid4_time<R>(sc.grid);
+        k.gt.origin = uniform_(k.gt.origin); k.gt.inv_h = uniform_(k.gt.inv_h); k.gt.hi = uniform_(k.gt.hi); k.gt.top = uniform_(k.gt.top);
+        k.gt.st = uniform64(k.gt.st);
+    }
     return k;
 }
 
@@ -224,7 +240,9 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
     bool first_early = true, early_done = false;  // NEAR: the early list's own cursor (ctrl[7])
     __shared__ uint32_t early_buf[RTGR_EARLY_BUF];  // one wave per workgroup: private to the wave (used by the FAR pass)
     __shared__ R ldsk_mem[LDSK ? 20 * 64 : 1];
-    volatile R* const ldsk = ldsk_mem + lane;   // (volatile: re-read at each use instead of being kept live in registers)
+    // (volatile: re-read at each use instead of being kept live in registers; address space 3: ds_read / ds_write — a generic pointer
+    // would make them flat accesses, which wait on vmcnt behind every outstanding global load)
+    volatile __attribute__((address_space(3))) R* const ldsk = (__attribute__((address_space(3))) R*)(ldsk_mem + lane);
     uint32_t e_cnt = 0;                             // entries in early_buf (wave-uniform)
 #ifdef RTGR_ROOT_STATS
     const unsigned long long dbg_t0 = wall_clock64();
@@ -507,6 +525,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                 // the box is one that STARTED there: it ends as RTGR_RAY_OUTSIDE before its first step
                 bool start_outside = false;
                 if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) start_outside = !grid_inside<R>(MK.grid, x + 1);
+                if constexpr (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) start_outside = !grid4_inside<R>(MK.grid, MK.gt, x);   // (t too)
                 if (start_outside) {
                     done = RTGR_RAY_OUTSIDE;
                 } else if (EEst2 != EEst2) {
@@ -778,6 +797,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                             dt = rmin(dtmax, dtnew);
                             bool outside = false;   // RTGR_GRID: the step ended outside the valid box (the scan found no event in it)
                             if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) outside = !grid_inside<R>(MK.grid, xn + 1);
+                            if constexpr (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) outside = !grid4_inside<R>(MK.grid, MK.gt, xn);
                             if (outside) done = RTGR_RAY_OUTSIDE;
                             else if (!(t < t1)) done = RTGR_RAY_LAMBDA1;
                             else if (nacc + nrej >= A.opt.max_steps) done = RTGR_RAY_MAXSTEPS;
@@ -938,11 +958,13 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
 #undef KSTORE
 template <class R, int METRIC, bool SPIN, bool NPTS10, int MODE>
 __global__ __launch_bounds__(64, METRIC == RTGR_GENERIC_BASE + RTGR_GRID ? (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GRID : RTGR_WAVES_PER_SIMD_GRID_F32)
+                                 : METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4 ? (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GRID4 : RTGR_WAVES_PER_SIMD_GRID4_F32)
                                  : METRIC >= RTGR_GENERIC_BASE ? (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GENERIC : RTGR_WAVES_PER_SIMD_GENERIC_F32)
                                  : (MODE == MODE_FAR ? (sizeof(R) == 8 ? (SPIN ? RTGR_WAVES_PER_SIMD_SPIN_FAR : RTGR_WAVES_PER_SIMD_FAR) : 4)
                                                      : (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD : RTGR_WAVES_PER_SIMD_F32)))
 void integrate_kernel(const IntegrateArgs<R> A) {
-    integrate_body<R, METRIC, SPIN, NPTS10, MODE, (METRIC >= RTGR_GENERIC_BASE ? RTGR_LDSK_GENERIC != 0 : (SPIN && MODE == MODE_FAR && RTGR_LDSK_SPIN_FAR != 0))>(A);
+    integrate_body<R, METRIC, SPIN, NPTS10, MODE, (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4 ? sizeof(R) == 8 && RTGR_LDSK_GRID4 != 0
+                                                   : METRIC >= RTGR_GENERIC_BASE ? RTGR_LDSK_GENERIC != 0 : (SPIN && MODE == MODE_FAR && RTGR_LDSK_SPIN_FAR != 0))>(A);
 }
 
 // The a = 0 FAR pass once more at FOUR waves per SIMD (128 registers: 28 B/lane of scratch for KS_REF, none for KS_TRUE).
@@ -980,7 +1002,7 @@ RTGR_DEV void prepare_body(const IntegrateArgs<R>& A) {
         } else {  // make_canvas (src/RayTraceGR.jl:457-478) for this pixel, straight into registers
             R s[8];
             const uint64_t idx = A.first + w;
-            make_pixel<R>(A.sc, A.cam, A.ni, A.nj, idx % A.ni, A.j0 + (idx / A.ni) * A.jstride, s);
+            make_pixel<R, METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4>(A.sc, A.cam, A.ni, A.nj, idx % A.ni, A.j0 + (idx / A.ni) * A.jstride, s);
 #pragma unroll
             for (int q = 0; q < 4; q++) { x[q] = s[q]; u[q] = s[4 + q]; }
         }

@@ -235,6 +235,7 @@ struct MetricK {
     R a2;    // a²
     R a2x2;  // 2a
     DevGrid<R> grid;   // RTGR_GRID instantiation only (scene_consts): the samples; never set or read by the others
+    DevGridTime<R> gt; // RTGR_GRID4 instantiation only: the time axis of a 4-D grid (grid then describes its spatial axes)
 };
 // A 64-bit value every lane holds, made wave-uniform FOR THE COMPILER (SGPR pair).  __builtin_amdgcn_readfirstlane
 // returns a signed int: each half goes through uint32_t, or a low word with bit 31 set sign-extends over the high word
@@ -435,6 +436,7 @@ RTGR_DEV void accel_spin_true(const R xs[3], const R u[4], const MetricK<R>& C, 
 // acceleration only (the ẋ = u half is handled by the caller):  u̇ = accel(x_spatial, u)
 template <class R> RTGR_DEV void accel_generic(uint32_t metric, R xt, const R xs[3], const R u[4], R M, R a, R ud[4]);
 template <class R> RTGR_DEV void grid_accel(const DevGrid<R>& G, const R xs[3], const R u[4], R ud[4]);
+template <class R> RTGR_DEV void grid4_accel(const DevGrid<R>& G, const DevGridTime<R>& T, R xt, const R xs[3], const R u[4], R ud[4]);
 constexpr int RTGR_GENERIC_BASE = 100;  // METRIC template value 100 + kind selects the generic dual-number RHS
 #ifndef RTGR_USER_NE
 #define RTGR_USER_NE 4   // a user unit built with -DRTGR_USER_NE=3 declares its metric stationary (api.UserMetric(stationary=True))
@@ -442,8 +444,9 @@ constexpr int RTGR_GENERIC_BASE = 100;  // METRIC template value 100 + kind sele
 
 // Does the integrate loop have to carry the stage's TIME coordinate for this metric?  The reference evaluates
 // christoffel(metric, x) at the full 4-position (src/RayTraceGR.jl:358-363); every built-in metric is stationary, so only
-// a user metric that was NOT declared stationary needs x^t at the stages (the other instantiations never form it).
+// a user metric that was NOT declared stationary and a time-dependent grid need x^t at the stages (the others never form it).
 template <int METRIC> constexpr bool needs_stage_time() {
+    if (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) return true;
 #ifdef RTGR_USER_METRIC
     return METRIC == RTGR_GENERIC_BASE + RTGR_USER && RTGR_USER_NE == 4;
 #else
@@ -456,6 +459,8 @@ template <class R, int METRIC, bool SPIN, bool FAST>
 RTGR_DEV void accel(const R xs[3], const R u[4], const MetricK<R>& C, R ud[4], R xt = R(0)) {
     if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) {
         grid_accel<R>(C.grid, xs, u, ud);
+    } else if constexpr (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) {
+        grid4_accel<R>(C.grid, C.gt, xt, xs, u, ud);
     } else if constexpr (METRIC >= RTGR_GENERIC_BASE) {
         accel_generic<R>((uint32_t)(METRIC - RTGR_GENERIC_BASE), xt, xs, u, C.M, C.a, ud);
     } else if constexpr (METRIC == RTGR_MINKOWSKI) {
@@ -890,6 +895,125 @@ RTGR_DEV void grid_metric(const DevGrid<R>& G, const R x[4], R g[4][4], R dg[4][
             dg[p][q][0] = R(0);
 #pragma unroll
             for (int j = 0; j < 3; j++) dg[p][q][1 + j] = d[j][c];
+        }
+}
+
+// ---- time-dependent grid (rtgr_grid4_metric_load): the tensor product of the same weights on t, x, y, z --------------------------
+// the time axis' descriptor: GRID4_HEADER bytes in front of the samples (rtgr_args.hpp), one wave-uniform read
+template <class R>
+RTGR_DEV DevGridTime<R> grid4_time(const DevGrid<R>& G) {
+    return *(const DevGridTime<R>*)((const char*)G.g - GRID4_HEADER);
+}
+// the time axis: weights on slices l−1 … l+2 of the clamped cell and their derivatives × 1/h_t (grid_axis on the time descriptor)
+template <class R>
+RTGR_DEV uint64_t grid4_taxis(const DevGridTime<R>& T, R x, R w[4], R dw[4]) {
+    const R s = (x - T.origin) * T.inv_h;
+    R c = rfloor(s);
+    c = c > T.hi ? T.hi : c;
+    c = c >= R(1) ? c : R(1);
+    const R t = s - c, t2 = t * t, t3 = t2 * t, ih = R(0.5) * T.inv_h;
+    w[0] = R(0.5) * rfma(R(2), t2, -t3 - t);
+    w[1] = R(0.5) * rfma(R(3), t3, rfma(R(-5), t2, R(2)));
+    w[2] = R(0.5) * rfma(R(-3), t3, rfma(R(4), t2, t));
+    w[3] = R(0.5) * (t3 - t2);
+    dw[0] = ih * rfma(R(-3), t2, rfma(R(4), t, R(-1)));
+    dw[1] = ih * rfma(R(9), t2, R(-10) * t);
+    dw[2] = ih * rfma(R(-9), t2, rfma(R(8), t, R(1)));
+    dw[3] = ih * rfma(R(3), t2, R(-2) * t);
+    return (uint64_t)c - 1u;
+}
+// g (upper triangle) and d[0] = ∂_t g, d[1..3] = ∂_x,y,z g at (xt, xs).  The stencil is 4 slices x the 16 spatial rows of grid_eval,
+// walked as grid_eval walks them: 16 trips, each loading the four slices' copies of one row together (160 scalars, 4x the bytes in
+// flight of a 3-D trip).  Per row the slices are blended FIRST, relative to the time-centre slice s₁:
+//     b = (s₁ − ref) + Σ_l w_t,l (s_l − s₁),    b' = Σ_l w'_t,l (s_l − s₁)        (l = 0, 2, 3: the l = 1 term is exactly 0)
+// with ref the centre sample of the centre slice; b then goes through grid_eval's x-weights / y·z-weights exactly, and b' through
+// the same x- and y·z-weights into ∂_t g.  A grid whose slices are all equal therefore gives b = s₁ − ref, i.e. g and ∂_x,y,z g
+// bit for bit as grid_eval on one slice, and ∂_t g = 0 exactly.
+template <class R>
+RTGR_DEV void grid4_eval(const DevGrid<R>& G, const DevGridTime<R>& T, R xt, const R xs[3], R v[10], R d[4][10]) {
+    R wx[4], dwx[4], ty, tz, wt[4], dwt[4];
+    const uint64_t ix = grid_axis<R>(G, 0, xs[0], wx, dwx);
+    const uint64_t iy = grid_cell<R>(G, 1, xs[1], ty);
+    const uint64_t iz = grid_cell<R>(G, 2, xs[2], tz);
+    const uint64_t it = grid4_taxis<R>(T, xt, wt, dwt);
+    const uint64_t st = T.st;
+    const R* base = G.g + it * st + iz * G.sz + iy * G.sy + ix * 10u;   // slice 0 of the stencil; slice l is l·st further
+    R ref[10];
+    const R* centre = base + st + G.sz + G.sy + 10u;
+#pragma unroll
+    for (int c = 0; c < 10; c++) {
+        ref[c] = centre[c];
+        v[c] = R(0);
+#pragma unroll
+        for (int j = 0; j < 4; j++) d[j][c] = R(0);
+    }
+#pragma unroll 1
+    for (int r = 0; r < 16; r++) {
+        const int ky = r & 3, kz = r >> 2;
+        R wyk, dwyk, wzk, dwzk;
+        grid_weight<R>(ky, ty, G.inv_h[1], wyk, dwyk);
+        grid_weight<R>(kz, tz, G.inv_h[2], wzk, dwzk);
+        const R wv = wyk * wzk, wdy = dwyk * wzk, wdz = wyk * dwzk;
+        const R* row = base + (uint64_t)kz * G.sz + (uint64_t)ky * G.sy;
+#pragma unroll
+        for (int c = 0; c < 10; c++) {
+            R b[4], bt[4];
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                const R s1 = row[st + 10 * m + c];
+                const R e0 = row[10 * m + c] - s1, e2 = row[2 * st + 10 * m + c] - s1, e3 = row[3 * st + 10 * m + c] - s1;
+                b[m] = (s1 - ref[c]) + rfma(wt[3], e3, rfma(wt[2], e2, wt[0] * e0));
+                bt[m] = rfma(dwt[3], e3, rfma(dwt[2], e2, dwt[0] * e0));
+            }
+            const R rv = rfma(wx[3], b[3], rfma(wx[2], b[2], rfma(wx[1], b[1], wx[0] * b[0])));
+            const R rd = rfma(dwx[3], b[3], rfma(dwx[2], b[2], rfma(dwx[1], b[1], dwx[0] * b[0])));
+            const R rt = rfma(wx[3], bt[3], rfma(wx[2], bt[2], rfma(wx[1], bt[1], wx[0] * bt[0])));
+            v[c] = rfma(wv, rv, v[c]);
+            d[0][c] = rfma(wv, rt, d[0][c]);
+            d[1][c] = rfma(wv, rd, d[1][c]);
+            d[2][c] = rfma(wdy, rv, d[2][c]);
+            d[3][c] = rfma(wdz, rv, d[3][c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 10; c++) v[c] = v[c] + ref[c];
+}
+// inside the valid box of a 4-D grid: s in [1, n − 2] on t, x, y, z (false for NaN)
+template <class R>
+RTGR_DEV bool grid4_inside(const DevGrid<R>& G, const DevGridTime<R>& T, const R x[4]) {
+    const R s = (x[0] - T.origin) * T.inv_h;
+    return grid_inside<R>(G, x + 1) && s >= R(1) && s <= T.top;
+}
+// the geodesic acceleration of a 4-D grid: g and its four partials into the generic contraction (NE = 4)
+template <class R>
+RTGR_DEV void grid4_accel(const DevGrid<R>& G, const DevGridTime<R>& T, R xt, const R xs[3], const R u[4], R ud[4]) {
+    R v[10], d[4][10];
+    grid4_eval<R>(G, T, xt, xs, v, d);
+    DDual<R, 4, true> gd[4][4];
+#pragma unroll
+    for (int p = 0; p < 4; p++)
+#pragma unroll
+        for (int q = p; q < 4; q++) {
+            const int c = grid_comp(p, q);
+            gd[p][q].v = v[c];
+#pragma unroll
+            for (int j = 0; j < 4; j++) gd[p][q].e[j] = d[j][c];
+        }
+    generic_contract<R, 4, true>(gd, u, ud);
+}
+// g and dg[a][b][c] = ∂_c g_ab (∂_t g included) at a 4-position: rtgr_eval_metric_*, make_canvas, redshift
+template <class R>
+RTGR_DEV void grid4_metric(const DevGrid<R>& G, const R x[4], R g[4][4], R dg[4][4][4]) {
+    R v[10], d[4][10];
+    grid4_eval<R>(G, grid4_time<R>(G), x[0], x + 1, v, d);
+#pragma unroll
+    for (int p = 0; p < 4; p++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int c = p <= q ? grid_comp(p, q) : grid_comp(q, p);
+            g[p][q] = v[c];
+#pragma unroll
+            for (int j = 0; j < 4; j++) dg[p][q][j] = d[j][c];
         }
 }
 
