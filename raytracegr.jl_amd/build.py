@@ -27,9 +27,13 @@ CSRC = os.path.join(HERE, "csrc")
 UNITS = ["tu_f64_ksref.hip", "tu_f64_kstrue.hip", "tu_f64_generic.hip", "tu_f64_mink.hip", "tu_f32_closed.hip",
          "tu_f32_generic.hip", "tu_f64_grid.hip", "tu_f32_grid.hip", "tu_f64_grid4.hip", "tu_f32_grid4.hip", "rtgr_misc.hip", "rtgr_context.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip",
          "rtgr_units.hip", "rtgr_grid.hip", "rtgr_abi.hip"]
-# the device-side headers: what the KERNELS are made of (bench.py keys its roofline profile on their hash)
-KERNEL_HEADERS = ["rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_integrator.hpp", "rtgr_persistent.hpp", "rtgr_packed_f32.hpp",
+# THE list of device headers (csrc/): what every kernel — the library's and a run-time unit's — is made of.  A new device header goes
+# here and into rtgr_units.hip header_hash_of (the C++ build route of a unit, which runs without Python; tests/test_build_checks.py
+# holds the two lists against each other and against the #include lines).
+DEVICE_HEADERS = ["rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_grid_interp.hpp", "rtgr_integrator.hpp", "rtgr_persistent.hpp",
                   "rtgr_tsit5_tables.hpp"]
+# … plus what only the library's own kernels include (bench.py keys its roofline profile on the hash of these)
+KERNEL_HEADERS = DEVICE_HEADERS + ["rtgr_packed_f32.hpp"]
 HEADERS = KERNEL_HEADERS + ["rtgr_host.hpp", "rtgr_internal.hpp", "rtgr_pipeline.hpp", "rtgr_isa_audit.hpp", "rtgr_isa_repair.hpp", "rtgr_unit_build.hpp"]
 DEPS = [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(HERE, "..", "include", "rtgr.h")]
 OUT = os.path.join(HERE, "librtgr_hip.so")
@@ -57,9 +61,9 @@ def kernel_source_hash(out=None):
     return h.hexdigest()[:16]
 
 
-# the headers a run-time unit is compiled against (user_metric._HEADERS, rtgr_units.hip header_hash_of: same files, same order)
-UNIT_HEADERS = ["rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_integrator.hpp", "rtgr_persistent.hpp", "rtgr_tsit5_tables.hpp",
-                os.path.join("..", "..", "include", "rtgr.h")]
+# … and what a run-time unit is compiled against, relative to csrc/ (user_metric.py hashes these; rtgr_units.hip header_hash_of: same
+# files, same order)
+UNIT_HEADERS = DEVICE_HEADERS + [os.path.join("..", "..", "include", "rtgr.h")]
 
 
 def header_hash():

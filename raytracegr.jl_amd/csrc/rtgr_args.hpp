@@ -40,9 +40,13 @@ struct DevGrid {
 // A TIME-DEPENDENT grid (rtgr_grid4_metric_load): the scene's metric is RTGR_GRID, the device scene's RTGR_GRID4 (internal, below).
 // DevGrid describes its spatial axes as for a 3-D grid (g = slice 0); the time axis' descriptor does not travel in the kernel
 // arguments — DevScene's layout is every kernel's, and growing it would move every argument behind it — but in the GRID4_HEADER bytes
-// in front of the samples on the device, where scene_consts / grid4_time (rtgr_physics.hpp) read it once.
+// in front of the samples on the device, where Sampled::fill / grid4_time (rtgr_grid_interp.hpp) read it once.
 constexpr uint32_t RTGR_GRID4 = 64;           // DevScene::metric of a 4-D grid; the instantiation is RTGR_GENERIC_BASE + RTGR_GRID4
 constexpr uint64_t GRID4_HEADER = 64;         // bytes of the DevGridTime block before the first sample (keeps the samples 64-byte aligned)
+// "is DevScene::metric given as samples, and on how many axes": 3 (RTGR_GRID), 4 (RTGR_GRID4), 0 for every other kind.  Host and device,
+// compile time and run time: the one place that names the sampled kinds (the device side builds on it in rtgr_grid_interp.hpp).
+constexpr bool sampled_on(uint32_t metric, int dims) { return metric == (dims == 4 ? RTGR_GRID4 : (uint32_t)RTGR_GRID); }
+constexpr int sampled_dims(uint32_t metric) { return sampled_on(metric, 3) ? 3 : sampled_on(metric, 4) ? 4 : 0; }
 template <class R>
 struct DevGridTime {
     uint64_t st;        // scalars between neighbouring time slices (10 n_x n_y n_z)

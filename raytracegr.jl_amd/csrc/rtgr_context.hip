@@ -509,19 +509,8 @@ int convert_scene(DeviceCtx& D, const rtgr_scene* s, DevScene<R>& d, const UserM
     d.M = (R)s->M;
     d.a = (R)s->a;
     if (grid) {
-        d.grid.g = (const R*)(sizeof(R) == 8 ? grid->d64 : grid->d32);
-        if (grid->nt) {   // a time-dependent grid: its own kernels and hooks; the samples follow the time axis' descriptor
-            d.metric = RTGR_GRID4;
-            d.grid.g = (const R*)((const char*)d.grid.g + GRID4_HEADER);
-        }
-        d.grid.sy = 10ull * grid->n[0];
-        d.grid.sz = 10ull * grid->n[0] * grid->n[1];
-        for (int ax = 0; ax < 3; ax++) {
-            d.grid.origin[ax] = (R)grid->origin[ax];
-            d.grid.inv_h[ax] = (R)(1.0 / grid->spacing[ax]);
-            d.grid.hi[ax] = (R)(grid->n[ax] - 3u);
-            d.grid.top[ax] = (R)(grid->n[ax] - 2u);
-        }
+        if (grid->axes.dims == 4) d.metric = RTGR_GRID4;   // a time-dependent grid: its own kernels and hooks
+        d.grid = dev_grid<R>(*grid);
     }
     int rc;
     const uint32_t n0 = s->nobj < (uint32_t)RTGR_MAX_OBJECTS ? s->nobj : (uint32_t)RTGR_MAX_OBJECTS;
@@ -586,8 +575,7 @@ void convert_camera(const rtgr_camera* c, DevCamera<R>& d) {
 }
 
 int dispatch(LaunchEnv& E, const TraceArgs<double>& A, bool generic, bool spin, hipStream_t st) {
-    if (A.sc.metric == RTGR_GRID) return launch_f64_grid(E, A, st);
-    if (A.sc.metric == RTGR_GRID4) return launch_f64_grid4(E, A, st);
+    if (const int dims = sampled_dims(A.sc.metric)) return dims == 4 ? launch_f64_grid4(E, A, st) : launch_f64_grid(E, A, st);
     if (generic || E.user) return launch_f64_generic(E, A, st);   // (a scene with a run-time unit launches the unit's kernels from there)
     switch (A.sc.metric) {
         case RTGR_MINKOWSKI: return launch_f64_mink(E, A, st);
@@ -596,8 +584,7 @@ int dispatch(LaunchEnv& E, const TraceArgs<double>& A, bool generic, bool spin, 
     }
 }
 int dispatch(LaunchEnv& E, const TraceArgs<float>& A, bool generic, bool spin, hipStream_t st) {
-    if (A.sc.metric == RTGR_GRID) return launch_f32_grid(E, A, st);
-    if (A.sc.metric == RTGR_GRID4) return launch_f32_grid4(E, A, st);
+    if (const int dims = sampled_dims(A.sc.metric)) return dims == 4 ? launch_f32_grid4(E, A, st) : launch_f32_grid(E, A, st);
     if (generic || E.user) return launch_f32_generic(E, A, st);
     return launch_f32_closed(E, A, spin, st);
 }
@@ -657,7 +644,7 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
     A.counters = (unsigned long long*)d_counters;
     const bool spin = scene->a != 0.0;
     const bool generic = ((scene->metric & RTGR_METRIC_GENERIC) != 0 && A.sc.metric != RTGR_MINKOWSKI) || A.sc.metric == RTGR_USER ||
-                         A.sc.metric == RTGR_GRID || A.sc.metric == RTGR_GRID4;
+                         sampled_dims(A.sc.metric) != 0;
     if ((tl_knobs_override ? tl_knobs_override->tile : D.knobs.tile)) {   // (the probe and the scene check bring their own options: tile = 0)
         if (generic || user) return fail(RTGR_ERR_BAD_ARG, "RTGR_METRIC_GENERIC, RTGR_GRID and run-time units need the persistent pipeline (option tile = 0)");
         if (win && (win->plane_stride || win->out_offset)) return fail(RTGR_ERR_BAD_ARG, "the tile kernel writes whole slabs only");

@@ -1,6 +1,7 @@
 // rtgr_grid.hip — metrics sampled on a grid (RTGR_GRID, include/rtgr.h; 3-D and time-dependent 4-D): load (checks, upload to every device of the context in
 // Float64 and Float32) and unload (retire: a hipGraph captured earlier may still replay the samples; rtgr_trim frees them).  Host code
-// only: the interpolant is rtgr_physics.hpp's (grid_eval), the kernels are tu_f64_grid.hip's / tu_f32_grid.hip's.
+// only: the interpolant is rtgr_grid_interp.hpp's (grid_eval, grid4_eval), the kernels are tu_f64_grid.hip's / tu_f32_grid.hip's and
+// tu_f64_grid4.hip's / tu_f32_grid4.hip's; what the kernels read of the axes is built from GridAxes in rtgr_host.hpp (dev_grid, dev_grid_time).
 #include <atomic>
 #include <cmath>
 #include "rtgr_internal.hpp"
@@ -22,17 +23,17 @@ static long double det_upper(const double* c) {
     return s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
 }
 
-// The load of either kind: n / origin / spacing of the spatial axes (x, y, z), nt = 0 for a 3-D grid or the time axis of a 4-D one.
-// Checks every sample, then uploads Float64 and Float32 copies to every device (a 4-D table behind the GRID4_HEADER bytes of its
-// time axis' descriptor, rtgr_args.hpp) and publishes the table under a fresh id.
-static int grid_load(rtgr_context* c, const char* who, const uint32_t n[3], const double origin[3], const double spacing[3], uint32_t nt,
-                     double origin_t, double spacing_t, const double* g, uint64_t* id_out) {
+// The load of either kind.  Checks the axes and every sample, then uploads Float64 and Float32 copies to every device (a 4-D table
+// behind the GRID4_HEADER bytes of its time axis' descriptor, rtgr_args.hpp) and publishes the table under a fresh id.
+static int grid_load(rtgr_context* c, const char* who, const GridAxes& A, const double* g, uint64_t* id_out) {
+    const bool nt = A.dims == 4;
+    const uint32_t* n = A.n + 1;   // the spatial axes
     uint64_t npts = 1;
-    for (int ax = 0; ax < 4; ax++) {
-        if (ax == 3 && !nt) break;
-        const uint32_t na = ax < 3 ? n[ax] : nt;
-        const double o = ax < 3 ? origin[ax] : origin_t, h = ax < 3 ? spacing[ax] : spacing_t;
-        const std::string name = nt ? std::to_string(ax < 3 ? ax + 1 : 0) : std::to_string(ax);   // (4-D: axes are numbered t, x, y, z)
+    for (int k = 0; k < A.dims; k++) {
+        const int ax = k < 3 ? k + 1 : 0;   // x, y, z, then t
+        const uint32_t na = A.n[ax];
+        const double o = A.origin[ax], h = A.spacing[ax];
+        const std::string name = std::to_string(nt ? ax : ax - 1);   // (the caller's numbering: t, x, y, z of rtgr_grid4; x, y, z of rtgr_grid)
         if (na < 4u || na > (1u << 20))
             return fail(RTGR_ERR_BAD_ARG, std::string(who) + ": n[" + name + "] = " + std::to_string(na) + ": each axis needs 4 .. 2^20 samples");
         if (!(h > 0.0) || !std::isfinite(h) || !std::isfinite(o))
@@ -61,13 +62,8 @@ static int grid_load(rtgr_context* c, const char* who, const uint32_t n[3], cons
     }
     // a 4-D table starts with its time axis' descriptor (DevGridTime, read by the kernels), in each scalar type
     const size_t head = nt ? (size_t)GRID4_HEADER : 0;
-    DevGridTime<double> t64{};
-    DevGridTime<float> t32{};
-    if (nt) {
-        t64.st = t32.st = 10ull * n[0] * n[1] * n[2];
-        t64.origin = origin_t; t64.inv_h = 1.0 / spacing_t; t64.hi = (double)(nt - 3u); t64.top = (double)(nt - 2u);
-        t32.origin = (float)t64.origin; t32.inv_h = (float)t64.inv_h; t32.hi = (float)t64.hi; t32.top = (float)t64.top;
-    }
+    const DevGridTime<double> t64 = dev_grid_time<double>(A);
+    const DevGridTime<float> t32 = dev_grid_time<float>(A);
     static_assert(sizeof(DevGridTime<double>) <= GRID4_HEADER && sizeof(DevGridTime<float>) <= GRID4_HEADER, "GRID4_HEADER");
     const size_t b64 = (size_t)npts * 10 * sizeof(double), b32 = (size_t)npts * 10 * sizeof(float);
     std::lock_guard<std::mutex> load_lock(c->modules_mu);   // (units and grids are loaded / unloaded under the same lock)
@@ -95,8 +91,7 @@ static int grid_load(rtgr_context* c, const char* who, const uint32_t n[3], cons
         if (!guard.ok) { release(); return fail(RTGR_ERR_HIP, "hipSetDevice failed"); }
         GridTable& t = made[k];
         t.id = id;
-        for (int ax = 0; ax < 3; ax++) { t.n[ax] = n[ax]; t.origin[ax] = origin[ax]; t.spacing[ax] = spacing[ax]; }
-        t.nt = nt; t.origin_t = origin_t; t.spacing_t = spacing_t;
+        t.axes = A;
         hipError_t e = hipMalloc(&t.d64, head + b64);
         if (e == hipSuccess) e = hipMalloc(&t.d32, head + b32);
         if (e == hipSuccess && nt) e = hipMemcpy(t.d64, &t64, sizeof t64, hipMemcpyHostToDevice);
@@ -122,7 +117,9 @@ int api::grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double
     if (rc) return rc;
     if (!grid || !g || !id_out) return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_load: NULL argument");
     if (grid->pad != 0) return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_load: rtgr_grid.pad must be 0");
-    return grid_load(c, "rtgr_grid_metric_load", grid->n, grid->origin, grid->spacing, 0u, 0.0, 0.0, g, id_out);
+    GridAxes A;
+    for (int ax = 0; ax < 3; ax++) { A.n[1 + ax] = grid->n[ax]; A.origin[1 + ax] = grid->origin[ax]; A.spacing[1 + ax] = grid->spacing[ax]; }
+    return grid_load(c, "rtgr_grid_metric_load", A, g, id_out);
 }
 
 int api::grid4_metric_load(rtgr_context* ctx, const rtgr_grid4* grid, const double* g, uint64_t* id_out) {
@@ -130,8 +127,10 @@ int api::grid4_metric_load(rtgr_context* ctx, const rtgr_grid4* grid, const doub
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
     if (!grid || !g || !id_out) return fail(RTGR_ERR_BAD_ARG, "rtgr_grid4_metric_load: NULL argument");
-    return grid_load(c, "rtgr_grid4_metric_load", grid->n + 1, grid->origin + 1, grid->spacing + 1, grid->n[0], grid->origin[0],
-                     grid->spacing[0], g, id_out);
+    GridAxes A;
+    A.dims = 4;
+    for (int ax = 0; ax < 4; ax++) { A.n[ax] = grid->n[ax]; A.origin[ax] = grid->origin[ax]; A.spacing[ax] = grid->spacing[ax]; }
+    return grid_load(c, "rtgr_grid4_metric_load", A, g, id_out);
 }
 
 int api::grid_metric_unload(rtgr_context* ctx, uint64_t id) {

@@ -121,17 +121,41 @@ constexpr size_t OBJECT_TABLES_BYTES = (size_t)1 << 30;
 
 // A metric sampled on a grid (rtgr_grid_metric_load): the samples on one device, in Float64 and Float32.  Immutable; rtgr_grid_metric_unload
 // moves the table to DeviceCtx::retired_grids (a hipGraph captured earlier may still replay it), rtgr_trim / rtgr_destroy free it.
+// The axes of either kind, described once: t, x, y, z as in rtgr_grid4 (include/rtgr.h); a 3-D grid has dims = 3 and no axis 0.
+struct GridAxes {
+    int dims = 3;   // 3: RTGR_GRID as loaded by rtgr_grid_metric_load; 4: time-dependent (rtgr_grid4_metric_load; RTGR_GRID4 on the device)
+    uint32_t n[4] = {0, 0, 0, 0};
+    double origin[4] = {0, 0, 0, 0}, spacing[4] = {0, 0, 0, 0};
+};
 struct GridTable {
     uint64_t id = 0;
-    void* d64 = nullptr;   // n[2] n[1] n[0] x 10 doubles, x fastest (the caller's layout)
-    void* d32 = nullptr;   // … the same as floats
-    uint32_t n[3] = {0, 0, 0};
-    double origin[3] = {0, 0, 0}, spacing[3] = {0, 0, 0};
-    // a time-dependent grid (rtgr_grid4_metric_load) when nt > 0: n / origin / spacing above are its spatial axes, and d64 / d32
-    // start with the GRID4_HEADER bytes of the time axis' DevGridTime (rtgr_args.hpp) before the samples (slice after slice)
-    uint32_t nt = 0;
-    double origin_t = 0, spacing_t = 0;
+    GridAxes axes;
+    // n_z n_y n_x x 10 doubles / floats, x fastest (the caller's layout); a time-dependent grid: slice after slice, behind the
+    // GRID4_HEADER bytes of the time axis' DevGridTime (rtgr_args.hpp)
+    void* d64 = nullptr, *d32 = nullptr;
 };
+// what the kernels read of a grid's axes, in their scalar type: the time axis' descriptor (uploaded in front of the samples) …
+template <class R> inline DevGridTime<R> dev_grid_time(const GridAxes& A) {
+    DevGridTime<R> T{};
+    if (A.dims == 4) {
+        T.st = 10ull * A.n[1] * A.n[2] * A.n[3];
+        T.origin = (R)A.origin[0]; T.inv_h = (R)(1.0 / A.spacing[0]); T.hi = (R)(A.n[0] - 3u); T.top = (R)(A.n[0] - 2u);
+    }
+    return T;
+}
+// … and the spatial axes with the samples' address (DevScene::grid)
+template <class R> inline DevGrid<R> dev_grid(const GridTable& t) {
+    const GridAxes& A = t.axes;
+    DevGrid<R> G{};
+    G.g = (const R*)((const char*)(sizeof(R) == 8 ? t.d64 : t.d32) + (A.dims == 4 ? GRID4_HEADER : 0));
+    G.sy = 10ull * A.n[1];
+    G.sz = 10ull * A.n[1] * A.n[2];
+    for (int ax = 0; ax < 3; ax++) {
+        G.origin[ax] = (R)A.origin[1 + ax]; G.inv_h[ax] = (R)(1.0 / A.spacing[1 + ax]);
+        G.hi[ax] = (R)(A.n[1 + ax] - 3u); G.top[ax] = (R)(A.n[1 + ax] - 2u);
+    }
+    return G;
+}
 // pipeline workspace of one (device, stream)
 struct StreamState {
     void* ws = nullptr;

@@ -338,14 +338,15 @@ RTGR_DEV void eval_objects_body(const DevScene<R>& sc, const DevSolver<R>& opt, 
     if (rgb) for (int c = 0; c < 3; c++) rgb[3 * p + c] = col[c];
 }
 
-// metric(x) with plain scalars (no duals): what make_canvas calls (:469).  GRID4: the scene is a time-dependent grid (chosen at compile
-// time, so that no other instantiation carries the 4-D interpolant)
-template <class R, bool GRID4 = false>
+// metric(x) with plain scalars (no duals): what make_canvas calls (:469).  NE says which sampled metric this instantiation can meet
+// (Sampled<R, METRIC>::NE where the metric is a template parameter, by sampled_on(sc.metric, ·) where it is read at run time): 4 is the
+// instantiation FOR a time-dependent grid — no other carries the 4-D interpolant —, 3 every other one, which finds a 3-D grid like a built-in.
+template <class R, int NE = 3>
 RTGR_DEV void metric_plain(const DevScene<R>& sc, const R x[4], R g[4][4]) {
 #pragma clang fp contract(off)   // see make_pixel
-    if constexpr (GRID4) {
+    if constexpr (NE == 4) {
         R dg[4][4][4];   // (not read)
-        grid4_metric<R>(sc.grid, x, g, dg);
+        sampled_metric<R, 4>(sc.grid, x, g, dg);
         return;
     }
 #ifdef RTGR_USER_METRIC
@@ -354,9 +355,9 @@ RTGR_DEV void metric_plain(const DevScene<R>& sc, const R x[4], R g[4][4]) {
         return;
     }
 #endif
-    if (sc.metric == (uint32_t)RTGR_GRID) {
+    if (sampled_on(sc.metric, NE)) {
         R dg[4][4][4];   // (not read: the camera needs g only)
-        grid_metric<R>(sc.grid, x, g, dg);
+        sampled_metric<R, NE>(sc.grid, x, g, dg);
         return;
     }
     // built-ins are η + f k k
@@ -374,7 +375,7 @@ RTGR_DEV void metric_plain(const DevScene<R>& sc, const R x[4], R g[4][4]) {
 }
 
 // ---- make_canvas pixel (src/RayTraceGR.jl:464-476): state (x, u) of pixel (i, j), 0-based -------------------------
-template <class R, bool GRID4 = false>
+template <class R, int NE = 3>
 RTGR_DEV void make_pixel(const DevScene<R>& sc, const DevCamera<R>& cam, uint64_t ni, uint64_t nj, uint64_t i0,
                          uint64_t j0, R s[8]) {
     // No implicit contraction in the camera (here, metric_plain, ks_field, inv4sym): this function is inlined into
@@ -392,7 +393,7 @@ RTGR_DEV void make_pixel(const DevScene<R>& sc, const DevCamera<R>& cam, uint64_
         n[c] = cam.normal[c] + dx * cam.widthx[c] + dy * cam.widthy[c];               // :468
     }
     R g[4][4];
-    metric_plain<R, GRID4>(sc, x, g);                                                 // :469
+    metric_plain<R, NE>(sc, x, g);                                                 // :469
     R gu[4][4];
     inv4sym<R>(g, gu);                                                                // :470
     R t[4];
@@ -445,7 +446,7 @@ RTGR_DEV R inner(const R g[4][4], const R a[4], const R b[4]) {
 }
 // one thread per ray; a body function so that run-time compiled metric units wrap it in kernels of their own (metric_plain
 // dispatches to the unit's rtgr_user_metric there)
-template <class R, bool GRID4 = false>
+template <class R, int NE = 3>
 RTGR_DEV void redshift_body(const DevScene<R>& sc, const DevCamera<R>& cam, const R* state0, uint64_t ni, uint64_t nj, uint64_t j0,
                             uint64_t jstride, uint64_t n, uint64_t out_offset, const R* state_end, const uint8_t* hit, const uint32_t* hit32, R* red) {
     const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -456,13 +457,13 @@ RTGR_DEV void redshift_body(const DevScene<R>& sc, const DevCamera<R>& cam, cons
     if (h == 0 || h > sc.nobj) { red[idx] = nan; return; }
     R s0[8], se[8];
     if (state0) for (int c = 0; c < 8; c++) s0[c] = state0[w * 8 + c];
-    else make_pixel<R, GRID4>(sc, cam, ni, nj, w % ni, j0 + (w / ni) * jstride, s0);
+    else make_pixel<R, NE>(sc, cam, ni, nj, w % ni, j0 + (w / ni) * jstride, s0);
     for (int c = 0; c < 8; c++) se[c] = state_end[idx * 8 + c];
     R g0[4][4], ge[4][4], tobs[4], uem[4];
     bool ok0, oke;
-    metric_plain<R, GRID4>(sc, s0, g0);
+    metric_plain<R, NE>(sc, s0, g0);
     static_observer<R>(g0, tobs, ok0);
-    metric_plain<R, GRID4>(sc, se, ge);
+    metric_plain<R, NE>(sc, se, ge);
     uint32_t pos = 0;                      // the hit map holds indices of the CALLER's list: find the object in the regrouped one
     for_each_object<R>(sc, [&](const DevObject<R>& o_, uint32_t o) { if (o_.orig + 1u == h) pos = o; });
     const DevObject<R>& ob = object_at<R>(sc, pos);

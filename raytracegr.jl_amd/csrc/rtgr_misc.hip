@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void canvas_kernel(DevScene<R> sc, DevCamera<R
     if (w >= count) return;
     const uint64_t idx = first + w;  // linear index inside the slab: i + k * ni, image row j = j0 + k * jstride
     R s[8];
-    if (sc.metric == RTGR_GRID4) make_pixel<R, true>(sc, cam, ni, nj, idx % ni, j0 + (idx / ni) * jstride, s);   // (a time-dependent grid)
+    if (sampled_on(sc.metric, 4)) make_pixel<R, 4>(sc, cam, ni, nj, idx % ni, j0 + (idx / ni) * jstride, s);   // (a time-dependent grid)
     else make_pixel<R>(sc, cam, ni, nj, idx % ni, j0 + (idx / ni) * jstride, s);
 #pragma unroll
     for (int c = 0; c < 8; c++) state0[w * 8 + c] = s[c];
@@ -31,8 +31,8 @@ __global__ __launch_bounds__(256) void eval_metric_kernel(DevScene<R> sc, const 
     if (p >= n) return;
     R xx[4] = {x[4 * p], x[4 * p + 1], x[4 * p + 2], x[4 * p + 3]};
     R gg[4][4], dd[4][4][4];
-    if (sc.metric == (uint32_t)RTGR_GRID) grid_metric<R>(sc.grid, xx, gg, dd);
-    else if (sc.metric == RTGR_GRID4) grid4_metric<R>(sc.grid, xx, gg, dd);
+    if (sampled_on(sc.metric, 3)) sampled_metric<R, 3>(sc.grid, xx, gg, dd);   // a metric given as samples: its interpolant, else the duals
+    else if (sampled_on(sc.metric, 4)) sampled_metric<R, 4>(sc.grid, xx, gg, dd);
     else dmetric_dev<R>(sc.metric, sc.M, sc.a, xx, gg, dd);
     if (g) for (int q = 0; q < 16; q++) g[16 * p + q] = (&gg[0][0])[q];
     if (dg) for (int q = 0; q < 64; q++) dg[64 * p + q] = (&dd[0][0][0])[q];
@@ -63,12 +63,12 @@ __global__ __launch_bounds__(256) void eval_geodesic_kernel(DevScene<R> sc, cons
     if (p >= n) return;
     R si[8], so[8];
     for (int c = 0; c < 8; c++) si[c] = s[8 * p + c];
-    if (sc.metric == (uint32_t)RTGR_GRID) {   // every path: the grid RHS (the integrate loop's own, accel<…, GRID>)
+    if (sampled_on(sc.metric, 3)) {          // a sampled metric, every path: the integrate loop's own RHS (accel<…> of a sampled METRIC)
         for (int c = 0; c < 4; c++) so[c] = si[4 + c];
-        grid_accel<R>(sc.grid, si + 1, si + 4, so + 4);
-    } else if (sc.metric == RTGR_GRID4) {     // … and of a time-dependent grid, at the state's own t
+        sampled_accel<R, 3>(sc.grid, DevGridTime<R>{}, si[0], si + 1, si + 4, so + 4);
+    } else if (sampled_on(sc.metric, 4)) {   // … of a time-dependent one, at the state's own t
         for (int c = 0; c < 4; c++) so[c] = si[4 + c];
-        grid4_accel<R>(sc.grid, grid4_time<R>(sc.grid), si[0], si + 1, si + 4, so + 4);
+        sampled_accel<R, 4>(sc.grid, grid4_time<R>(sc.grid), si[0], si + 1, si + 4, so + 4);
     } else if (path == 1) {
         generic_rhs<R>(sc.metric, sc.M, sc.a, si, so);
     } else {
@@ -131,7 +131,7 @@ template <class R>
 __global__ __launch_bounds__(256) void redshift_kernel(DevScene<R> sc, DevCamera<R> cam, const R* state0, uint64_t ni, uint64_t nj,
                                                        uint64_t j0, uint64_t jstride, uint64_t n, uint64_t out_offset,
                                                        const R* state_end, const uint8_t* hit, const uint32_t* hit32, R* red) {
-    if (sc.metric == RTGR_GRID4) redshift_body<R, true>(sc, cam, state0, ni, nj, j0, jstride, n, out_offset, state_end, hit, hit32, red);
+    if (sampled_on(sc.metric, 4)) redshift_body<R, 4>(sc, cam, state0, ni, nj, j0, jstride, n, out_offset, state_end, hit, hit32, red);
     else redshift_body<R>(sc, cam, state0, ni, nj, j0, jstride, n, out_offset, state_end, hit, hit32, red);
 }
 

@@ -84,6 +84,21 @@
 
 namespace rtgr {
 
+// What integrate_kernel<…> is BUILT for (its __launch_bounds__) and what the host sizes its launches by (rtgr_pipeline.hpp), in one place
+template <class R, int METRIC, bool SPIN = false> constexpr int waves_per_simd_of(int mode) {
+    if (Sampled<R, METRIC>::time_dependent) return sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GRID4 : RTGR_WAVES_PER_SIMD_GRID4_F32;
+    if (Sampled<R, METRIC>::is) return sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GRID : RTGR_WAVES_PER_SIMD_GRID_F32;
+    if (METRIC >= RTGR_GENERIC_BASE) return sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GENERIC : RTGR_WAVES_PER_SIMD_GENERIC_F32;
+    if (mode == MODE_FAR) return sizeof(R) == 8 ? (SPIN ? RTGR_WAVES_PER_SIMD_SPIN_FAR : RTGR_WAVES_PER_SIMD_FAR) : 4;
+    return sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD : RTGR_WAVES_PER_SIMD_F32;
+}
+// … and whether it keeps the stage accelerations k[1..5] in LDS (integrate_body's LDSK)
+template <class R, int METRIC, bool SPIN> constexpr bool ldsk_of(int mode) {
+    if (Sampled<R, METRIC>::time_dependent) return sizeof(R) == 8 && RTGR_LDSK_GRID4 != 0;
+    if (METRIC >= RTGR_GENERIC_BASE) return RTGR_LDSK_GENERIC != 0;
+    return SPIN && mode == MODE_FAR && RTGR_LDSK_SPIN_FAR != 0;
+}
+
 // fast f32 helpers for the step-size machinery
 // (uniform_(), rtgr_physics.hpp: a wave-uniform value computed with vector instructions — there is no scalar f64 ALU —
 //  lives in a VGPR and, in a kernel squeezed to 127 registers, gets spilled to scratch and reloaded in the loop; through
@@ -182,13 +197,7 @@ RTGR_DEV void flush_early(const IntegrateArgs<R>& A, const uint32_t* buf, uint32
 template <class R, int METRIC>
 RTGR_DEV MetricK<R> scene_consts(const DevScene<R>& sc) {
     MetricK<R> k = metric_consts<R>(sc.M, sc.a);
-    if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) k.grid = sc.grid;
-    if constexpr (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) {
-        k.grid = sc.grid;
-        k.gt = grid4_time<R>(sc.grid);
-        k.gt.origin = uniform_(k.gt.origin); k.gt.inv_h = uniform_(k.gt.inv_h); k.gt.hi = uniform_(k.gt.hi); k.gt.top = uniform_(k.gt.top);
-        k.gt.st = uniform64(k.gt.st);
-    }
+    Sampled<R, METRIC>::fill(k, sc);
     return k;
 }
 
@@ -524,8 +533,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                 // RTGR_GRID: every accepted step that ends outside the grid's valid box ends its ray (below), so a running ray outside
                 // the box is one that STARTED there: it ends as RTGR_RAY_OUTSIDE before its first step
                 bool start_outside = false;
-                if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) start_outside = !grid_inside<R>(MK.grid, x + 1);
-                if constexpr (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) start_outside = !grid4_inside<R>(MK.grid, MK.gt, x);   // (t too)
+                if constexpr (Sampled<R, METRIC>::is) start_outside = !Sampled<R, METRIC>::inside(MK, x);   // (a time-dependent grid: t too)
                 if (start_outside) {
                     done = RTGR_RAY_OUTSIDE;
                 } else if (EEst2 != EEst2) {
@@ -796,8 +804,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                             t = tnew;
                             dt = rmin(dtmax, dtnew);
                             bool outside = false;   // RTGR_GRID: the step ended outside the valid box (the scan found no event in it)
-                            if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) outside = !grid_inside<R>(MK.grid, xn + 1);
-                            if constexpr (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) outside = !grid4_inside<R>(MK.grid, MK.gt, xn);
+                            if constexpr (Sampled<R, METRIC>::is) outside = !Sampled<R, METRIC>::inside(MK, xn);
                             if (outside) done = RTGR_RAY_OUTSIDE;
                             else if (!(t < t1)) done = RTGR_RAY_LAMBDA1;
                             else if (nacc + nrej >= A.opt.max_steps) done = RTGR_RAY_MAXSTEPS;
@@ -957,14 +964,9 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
 #undef KL
 #undef KSTORE
 template <class R, int METRIC, bool SPIN, bool NPTS10, int MODE>
-__global__ __launch_bounds__(64, METRIC == RTGR_GENERIC_BASE + RTGR_GRID ? (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GRID : RTGR_WAVES_PER_SIMD_GRID_F32)
-                                 : METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4 ? (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GRID4 : RTGR_WAVES_PER_SIMD_GRID4_F32)
-                                 : METRIC >= RTGR_GENERIC_BASE ? (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GENERIC : RTGR_WAVES_PER_SIMD_GENERIC_F32)
-                                 : (MODE == MODE_FAR ? (sizeof(R) == 8 ? (SPIN ? RTGR_WAVES_PER_SIMD_SPIN_FAR : RTGR_WAVES_PER_SIMD_FAR) : 4)
-                                                     : (sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD : RTGR_WAVES_PER_SIMD_F32)))
+__global__ __launch_bounds__(64, (waves_per_simd_of<R, METRIC, SPIN>(MODE)))
 void integrate_kernel(const IntegrateArgs<R> A) {
-    integrate_body<R, METRIC, SPIN, NPTS10, MODE, (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4 ? sizeof(R) == 8 && RTGR_LDSK_GRID4 != 0
-                                                   : METRIC >= RTGR_GENERIC_BASE ? RTGR_LDSK_GENERIC != 0 : (SPIN && MODE == MODE_FAR && RTGR_LDSK_SPIN_FAR != 0))>(A);
+    integrate_body<R, METRIC, SPIN, NPTS10, MODE, ldsk_of<R, METRIC, SPIN>(MODE)>(A);
 }
 
 // The a = 0 FAR pass once more at FOUR waves per SIMD (128 registers: 28 B/lane of scratch for KS_REF, none for KS_TRUE).
@@ -1002,7 +1004,7 @@ RTGR_DEV void prepare_body(const IntegrateArgs<R>& A) {
         } else {  // make_canvas (src/RayTraceGR.jl:457-478) for this pixel, straight into registers
             R s[8];
             const uint64_t idx = A.first + w;
-            make_pixel<R, METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4>(A.sc, A.cam, A.ni, A.nj, idx % A.ni, A.j0 + (idx / A.ni) * A.jstride, s);
+            make_pixel<R, Sampled<R, METRIC>::NE>(A.sc, A.cam, A.ni, A.nj, idx % A.ni, A.j0 + (idx / A.ni) * A.jstride, s);
 #pragma unroll
             for (int q = 0; q < 4; q++) { x[q] = s[q]; u[q] = s[4 + q]; }
         }

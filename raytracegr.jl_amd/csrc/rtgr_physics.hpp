@@ -234,8 +234,8 @@ struct MetricK {
     R M2;    // 2M
     R a2;    // a²
     R a2x2;  // 2a
-    DevGrid<R> grid;   // RTGR_GRID instantiation only (scene_consts): the samples; never set or read by the others
-    DevGridTime<R> gt; // RTGR_GRID4 instantiation only: the time axis of a 4-D grid (grid then describes its spatial axes)
+    DevGrid<R> grid;   // instantiations on a sampled metric only (Sampled<R, METRIC>::fill): the samples; never set or read by the others
+    DevGridTime<R> gt; // … on a time-dependent one only: the time axis of a 4-D grid (grid then describes its spatial axes)
 };
 // A 64-bit value every lane holds, made wave-uniform FOR THE COMPILER (SGPR pair).  __builtin_amdgcn_readfirstlane
 // returns a signed int: each half goes through uint32_t, or a low word with bit 31 set sign-extends over the high word
@@ -435,8 +435,7 @@ RTGR_DEV void accel_spin_true(const R xs[3], const R u[4], const MetricK<R>& C, 
 
 // acceleration only (the ẋ = u half is handled by the caller):  u̇ = accel(x_spatial, u)
 template <class R> RTGR_DEV void accel_generic(uint32_t metric, R xt, const R xs[3], const R u[4], R M, R a, R ud[4]);
-template <class R> RTGR_DEV void grid_accel(const DevGrid<R>& G, const R xs[3], const R u[4], R ud[4]);
-template <class R> RTGR_DEV void grid4_accel(const DevGrid<R>& G, const DevGridTime<R>& T, R xt, const R xs[3], const R u[4], R ud[4]);
+template <class R, int METRIC> struct Sampled;   // metrics given as samples: rtgr_grid_interp.hpp (included below)
 constexpr int RTGR_GENERIC_BASE = 100;  // METRIC template value 100 + kind selects the generic dual-number RHS
 #ifndef RTGR_USER_NE
 #define RTGR_USER_NE 4   // a user unit built with -DRTGR_USER_NE=3 declares its metric stationary (api.UserMetric(stationary=True))
@@ -446,7 +445,7 @@ constexpr int RTGR_GENERIC_BASE = 100;  // METRIC template value 100 + kind sele
 // christoffel(metric, x) at the full 4-position (src/RayTraceGR.jl:358-363); every built-in metric is stationary, so only
 // a user metric that was NOT declared stationary and a time-dependent grid need x^t at the stages (the others never form it).
 template <int METRIC> constexpr bool needs_stage_time() {
-    if (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) return true;
+    if (Sampled<double, METRIC>::time_dependent) return true;
 #ifdef RTGR_USER_METRIC
     return METRIC == RTGR_GENERIC_BASE + RTGR_USER && RTGR_USER_NE == 4;
 #else
@@ -457,10 +456,8 @@ template <int METRIC> constexpr bool needs_stage_time() {
 // xt: the time coordinate of the evaluation point (read only when needs_stage_time<METRIC>())
 template <class R, int METRIC, bool SPIN, bool FAST>
 RTGR_DEV void accel(const R xs[3], const R u[4], const MetricK<R>& C, R ud[4], R xt = R(0)) {
-    if constexpr (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) {
-        grid_accel<R>(C.grid, xs, u, ud);
-    } else if constexpr (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) {
-        grid4_accel<R>(C.grid, C.gt, xt, xs, u, ud);
+    if constexpr (Sampled<R, METRIC>::is) {
+        Sampled<R, METRIC>::accel(C, xt, xs, u, ud);
     } else if constexpr (METRIC >= RTGR_GENERIC_BASE) {
         accel_generic<R>((uint32_t)(METRIC - RTGR_GENERIC_BASE), xt, xs, u, C.M, C.a, ud);
     } else if constexpr (METRIC == RTGR_MINKOWSKI) {
@@ -733,7 +730,7 @@ RTGR_DEV void dmetric_dev(uint32_t metric, R M, R a, const R x[4], R g[4][4], R 
 //     ∂_b g_dc u^b u^c = Σ_j u^j (v_j)_d        and        ∂_d g_bc u^b u^c = u · v_d
 // — 20 FMA per direction instead of the 2 x 16 x 2 of the two double sums over (b, c).  Only the upper triangle of the
 // metric function's output is read.  NE = 3: directions x, y, z only (stationary metric: ∂_t g = 0 exactly).
-// (the contraction on its own: g and ∂_j g as duals, upper triangle read — shared with the grid metric's RHS, grid_accel)
+// (the contraction on its own: g and ∂_j g as duals, upper triangle read — shared with the RHS of a sampled metric, sampled_accel)
 template <class R, int NE, bool FAST>
 RTGR_DEV void generic_contract(const DDual<R, NE, FAST> gd[4][4], const R u[4], R ud[4]) {
     constexpr int J0 = 4 - NE;  // first seeded coordinate
@@ -773,249 +770,9 @@ RTGR_DEV void generic_accel(uint32_t metric, R M, R a, const R x[4], const R u[4
     generic_contract<R, NE, FAST>(gd, u, ud);
 }
 
-// ---- metric sampled on a grid (RTGR_GRID, include/rtgr.h) ----------------------------------------------------------------------
-// Tricubic Catmull-Rom (cubic convolution, a = −1/2), separable.  Per axis: s = (x − origin)/h, i = clamp(floor(s), 1, n − 3),
-// t = s − i, weights on samples i−1 … i+2 and their t-derivatives (× 1/h).  The clamp is written with comparisons that are false for
-// NaN, so a non-finite coordinate still reads samples inside the table (its value is then NaN, and so is the ray: RTGR_RAY_NAN).
-// the cell of coordinate x on axis ax: returns the stencil's first sample, t = s − i
-template <class R>
-RTGR_DEV uint64_t grid_cell(const DevGrid<R>& G, int ax, R x, R& t) {
-    const R s = (x - G.origin[ax]) * G.inv_h[ax];
-    R c = rfloor(s);
-    c = c > G.hi[ax] ? G.hi[ax] : c;
-    c = c >= R(1) ? c : R(1);
-    t = s - c;
-    return (uint64_t)c - 1u;                                      // first sample of the stencil
-}
-// weight k (0..3: samples i−1 … i+2) and its derivative × 1/h; k is wave-uniform where it is used (the row loop's counter)
-template <class R>
-RTGR_DEV void grid_weight(int k, R t, R ih, R& w, R& dw) {
-    const R t2 = t * t, t3 = t2 * t;
-    ih = R(0.5) * ih;
-    if (k == 0) { w = R(0.5) * rfma(R(2), t2, -t3 - t); dw = ih * rfma(R(-3), t2, rfma(R(4), t, R(-1))); }
-    else if (k == 1) { w = R(0.5) * rfma(R(3), t3, rfma(R(-5), t2, R(2))); dw = ih * rfma(R(9), t2, R(-10) * t); }
-    else if (k == 2) { w = R(0.5) * rfma(R(-3), t3, rfma(R(4), t2, t)); dw = ih * rfma(R(-9), t2, rfma(R(8), t, R(1))); }
-    else { w = R(0.5) * (t3 - t2); dw = ih * rfma(R(3), t2, R(-2) * t); }
-}
-template <class R>
-RTGR_DEV uint64_t grid_axis(const DevGrid<R>& G, int ax, R x, R w[4], R dw[4]) {
-    R t;
-    const uint64_t i = grid_cell<R>(G, ax, x, t);
-    const R t2 = t * t, t3 = t2 * t, ih = R(0.5) * G.inv_h[ax];
-    w[0] = R(0.5) * rfma(R(2), t2, -t3 - t);                      // (−t³ + 2t² − t)/2
-    w[1] = R(0.5) * rfma(R(3), t3, rfma(R(-5), t2, R(2)));        // (3t³ − 5t² + 2)/2
-    w[2] = R(0.5) * rfma(R(-3), t3, rfma(R(4), t2, t));           // (−3t³ + 4t² + t)/2
-    w[3] = R(0.5) * (t3 - t2);                                    // (t³ − t²)/2
-    dw[0] = ih * rfma(R(-3), t2, rfma(R(4), t, R(-1)));           // (−3t² + 4t − 1)/2h
-    dw[1] = ih * rfma(R(9), t2, R(-10) * t);                      // (9t² − 10t)/2h
-    dw[2] = ih * rfma(R(-9), t2, rfma(R(8), t, R(1)));            // (−9t² + 8t + 1)/2h
-    dw[3] = ih * rfma(R(3), t2, R(-2) * t);                       // (3t² − 2t)/2h
-    return i;
-}
-// g (the 10 components of the upper triangle, tt tx ty tz xx xy xz yy yz zz) and ∂_x g, ∂_y g, ∂_z g at a spatial point.  The stencil
-// is 16 rows of 4 consecutive x-samples (40 contiguous scalars each, the caller's layout), walked row by row (a loop, not unrolled: the
-// 640 loads of a fully unrolled stencil were hoisted ahead of the arithmetic, ~5 KB of spills per lane); per row the x-weights are combined first, then the
-// row's y·z weights.  Everything is summed RELATIVE to the stencil's centre sample s₁₁₁: g = s₁₁₁ + Σ W (s − s₁₁₁), ∂g = Σ W' (s − s₁₁₁)
-// — the same polynomials (Σ W = 1, Σ W' = 0), and exact where the samples are constant: a flat stretch of the table gives g to the bit
-// and ∂g = 0 exactly, not a few ulp of rounding through weights that sum to 1 − ε.
-template <class R>
-RTGR_DEV void grid_eval(const DevGrid<R>& G, const R xs[3], R v[10], R d[3][10]) {
-    R wx[4], dwx[4], ty, tz;   // (the y and z weights are formed per row from t: 16 fewer live registers)
-    const uint64_t ix = grid_axis<R>(G, 0, xs[0], wx, dwx);
-    const uint64_t iy = grid_cell<R>(G, 1, xs[1], ty);
-    const uint64_t iz = grid_cell<R>(G, 2, xs[2], tz);
-    const R* base = G.g + iz * G.sz + iy * G.sy + ix * 10u;
-    R ref[10];
-    const R* centre = base + G.sz + G.sy + 10u;
-#pragma unroll
-    for (int c = 0; c < 10; c++) { ref[c] = centre[c]; v[c] = R(0); d[0][c] = R(0); d[1][c] = R(0); d[2][c] = R(0); }
-#pragma unroll 1
-    for (int r = 0; r < 16; r++) {
-        const int ky = r & 3, kz = r >> 2;
-        R wyk, dwyk, wzk, dwzk;
-        grid_weight<R>(ky, ty, G.inv_h[1], wyk, dwyk);
-        grid_weight<R>(kz, tz, G.inv_h[2], wzk, dwzk);
-        const R wv = wyk * wzk, wdy = dwyk * wzk, wdz = wyk * dwzk;
-        const R* row = base + (uint64_t)kz * G.sz + (uint64_t)ky * G.sy;
-#pragma unroll
-        for (int c = 0; c < 10; c++) {
-            const R a0 = row[c] - ref[c], a1 = row[10 + c] - ref[c], a2 = row[20 + c] - ref[c], a3 = row[30 + c] - ref[c];
-            const R rv = rfma(wx[3], a3, rfma(wx[2], a2, rfma(wx[1], a1, wx[0] * a0)));
-            const R rd = rfma(dwx[3], a3, rfma(dwx[2], a2, rfma(dwx[1], a1, dwx[0] * a0)));
-            v[c] = rfma(wv, rv, v[c]);
-            d[0][c] = rfma(wv, rd, d[0][c]);
-            d[1][c] = rfma(wdy, rv, d[1][c]);
-            d[2][c] = rfma(wdz, rv, d[2][c]);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 10; c++) v[c] = v[c] + ref[c];
-}
-// index of component (p, q), p <= q, in the 10-vector
-RTGR_DEV constexpr int grid_comp(int p, int q) { return p == 0 ? q : (p == 1 ? 3 + q : (p == 2 ? 5 + q : 9)); }
-// inside the valid box: s in [1, n − 2] on every axis (false for NaN)
-template <class R>
-RTGR_DEV bool grid_inside(const DevGrid<R>& G, const R xs[3]) {
-    bool in = true;
-#pragma unroll
-    for (int ax = 0; ax < 3; ax++) {
-        const R s = (xs[ax] - G.origin[ax]) * G.inv_h[ax];
-        in = in && s >= R(1) && s <= G.top[ax];
-    }
-    return in;
-}
-// the geodesic acceleration of a grid metric: the interpolant's g and ∂_j g (j = x, y, z; stationary) into the generic contraction
-template <class R>
-RTGR_DEV void grid_accel(const DevGrid<R>& G, const R xs[3], const R u[4], R ud[4]) {
-    R v[10], d[3][10];
-    grid_eval<R>(G, xs, v, d);
-    DDual<R, 3, true> gd[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; p++)
-#pragma unroll
-        for (int q = p; q < 4; q++) {
-            const int c = grid_comp(p, q);
-            gd[p][q].v = v[c];
-#pragma unroll
-            for (int j = 0; j < 3; j++) gd[p][q].e[j] = d[j][c];
-        }
-    generic_contract<R, 3, true>(gd, u, ud);
-}
-// g and dg[a][b][c] = ∂_c g_ab (∂_t = 0) at a 4-position: rtgr_eval_metric_*, make_canvas, redshift
-template <class R>
-RTGR_DEV void grid_metric(const DevGrid<R>& G, const R x[4], R g[4][4], R dg[4][4][4]) {
-    R v[10], d[3][10];
-    grid_eval<R>(G, x + 1, v, d);
-#pragma unroll
-    for (int p = 0; p < 4; p++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int c = p <= q ? grid_comp(p, q) : grid_comp(q, p);
-            g[p][q] = v[c];
-            dg[p][q][0] = R(0);
-#pragma unroll
-            for (int j = 0; j < 3; j++) dg[p][q][1 + j] = d[j][c];
-        }
-}
-
-// ---- time-dependent grid (rtgr_grid4_metric_load): the tensor product of the same weights on t, x, y, z --------------------------
-// the time axis' descriptor: GRID4_HEADER bytes in front of the samples (rtgr_args.hpp), one wave-uniform read
-template <class R>
-RTGR_DEV DevGridTime<R> grid4_time(const DevGrid<R>& G) {
-    return *(const DevGridTime<R>*)((const char*)G.g - GRID4_HEADER);
-}
-// the time axis: weights on slices l−1 … l+2 of the clamped cell and their derivatives × 1/h_t (grid_axis on the time descriptor)
-template <class R>
-RTGR_DEV uint64_t grid4_taxis(const DevGridTime<R>& T, R x, R w[4], R dw[4]) {
-    const R s = (x - T.origin) * T.inv_h;
-    R c = rfloor(s);
-    c = c > T.hi ? T.hi : c;
-    c = c >= R(1) ? c : R(1);
-    const R t = s - c, t2 = t * t, t3 = t2 * t, ih = R(0.5) * T.inv_h;
-    w[0] = R(0.5) * rfma(R(2), t2, -t3 - t);
-    w[1] = R(0.5) * rfma(R(3), t3, rfma(R(-5), t2, R(2)));
-    w[2] = R(0.5) * rfma(R(-3), t3, rfma(R(4), t2, t));
-    w[3] = R(0.5) * (t3 - t2);
-    dw[0] = ih * rfma(R(-3), t2, rfma(R(4), t, R(-1)));
-    dw[1] = ih * rfma(R(9), t2, R(-10) * t);
-    dw[2] = ih * rfma(R(-9), t2, rfma(R(8), t, R(1)));
-    dw[3] = ih * rfma(R(3), t2, R(-2) * t);
-    return (uint64_t)c - 1u;
-}
-// g (upper triangle) and d[0] = ∂_t g, d[1..3] = ∂_x,y,z g at (xt, xs).  The stencil is 4 slices x the 16 spatial rows of grid_eval,
-// walked as grid_eval walks them: 16 trips, each loading the four slices' copies of one row together (160 scalars, 4x the bytes in
-// flight of a 3-D trip).  Per row the slices are blended FIRST, relative to the time-centre slice s₁:
-//     b = (s₁ − ref) + Σ_l w_t,l (s_l − s₁),    b' = Σ_l w'_t,l (s_l − s₁)        (l = 0, 2, 3: the l = 1 term is exactly 0)
-// with ref the centre sample of the centre slice; b then goes through grid_eval's x-weights / y·z-weights exactly, and b' through
-// the same x- and y·z-weights into ∂_t g.  A grid whose slices are all equal therefore gives b = s₁ − ref, i.e. g and ∂_x,y,z g
-// bit for bit as grid_eval on one slice, and ∂_t g = 0 exactly.
-template <class R>
-RTGR_DEV void grid4_eval(const DevGrid<R>& G, const DevGridTime<R>& T, R xt, const R xs[3], R v[10], R d[4][10]) {
-    R wx[4], dwx[4], ty, tz, wt[4], dwt[4];
-    const uint64_t ix = grid_axis<R>(G, 0, xs[0], wx, dwx);
-    const uint64_t iy = grid_cell<R>(G, 1, xs[1], ty);
-    const uint64_t iz = grid_cell<R>(G, 2, xs[2], tz);
-    const uint64_t it = grid4_taxis<R>(T, xt, wt, dwt);
-    const uint64_t st = T.st;
-    const R* base = G.g + it * st + iz * G.sz + iy * G.sy + ix * 10u;   // slice 0 of the stencil; slice l is l·st further
-    R ref[10];
-    const R* centre = base + st + G.sz + G.sy + 10u;
-#pragma unroll
-    for (int c = 0; c < 10; c++) {
-        ref[c] = centre[c];
-        v[c] = R(0);
-#pragma unroll
-        for (int j = 0; j < 4; j++) d[j][c] = R(0);
-    }
-#pragma unroll 1
-    for (int r = 0; r < 16; r++) {
-        const int ky = r & 3, kz = r >> 2;
-        R wyk, dwyk, wzk, dwzk;
-        grid_weight<R>(ky, ty, G.inv_h[1], wyk, dwyk);
-        grid_weight<R>(kz, tz, G.inv_h[2], wzk, dwzk);
-        const R wv = wyk * wzk, wdy = dwyk * wzk, wdz = wyk * dwzk;
-        const R* row = base + (uint64_t)kz * G.sz + (uint64_t)ky * G.sy;
-#pragma unroll
-        for (int c = 0; c < 10; c++) {
-            R b[4], bt[4];
-#pragma unroll
-            for (int m = 0; m < 4; m++) {
-                const R s1 = row[st + 10 * m + c];
-                const R e0 = row[10 * m + c] - s1, e2 = row[2 * st + 10 * m + c] - s1, e3 = row[3 * st + 10 * m + c] - s1;
-                b[m] = (s1 - ref[c]) + rfma(wt[3], e3, rfma(wt[2], e2, wt[0] * e0));
-                bt[m] = rfma(dwt[3], e3, rfma(dwt[2], e2, dwt[0] * e0));
-            }
-            const R rv = rfma(wx[3], b[3], rfma(wx[2], b[2], rfma(wx[1], b[1], wx[0] * b[0])));
-            const R rd = rfma(dwx[3], b[3], rfma(dwx[2], b[2], rfma(dwx[1], b[1], dwx[0] * b[0])));
-            const R rt = rfma(wx[3], bt[3], rfma(wx[2], bt[2], rfma(wx[1], bt[1], wx[0] * bt[0])));
-            v[c] = rfma(wv, rv, v[c]);
-            d[0][c] = rfma(wv, rt, d[0][c]);
-            d[1][c] = rfma(wv, rd, d[1][c]);
-            d[2][c] = rfma(wdy, rv, d[2][c]);
-            d[3][c] = rfma(wdz, rv, d[3][c]);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 10; c++) v[c] = v[c] + ref[c];
-}
-// inside the valid box of a 4-D grid: s in [1, n − 2] on t, x, y, z (false for NaN)
-template <class R>
-RTGR_DEV bool grid4_inside(const DevGrid<R>& G, const DevGridTime<R>& T, const R x[4]) {
-    const R s = (x[0] - T.origin) * T.inv_h;
-    return grid_inside<R>(G, x + 1) && s >= R(1) && s <= T.top;
-}
-// the geodesic acceleration of a 4-D grid: g and its four partials into the generic contraction (NE = 4)
-template <class R>
-RTGR_DEV void grid4_accel(const DevGrid<R>& G, const DevGridTime<R>& T, R xt, const R xs[3], const R u[4], R ud[4]) {
-    R v[10], d[4][10];
-    grid4_eval<R>(G, T, xt, xs, v, d);
-    DDual<R, 4, true> gd[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; p++)
-#pragma unroll
-        for (int q = p; q < 4; q++) {
-            const int c = grid_comp(p, q);
-            gd[p][q].v = v[c];
-#pragma unroll
-            for (int j = 0; j < 4; j++) gd[p][q].e[j] = d[j][c];
-        }
-    generic_contract<R, 4, true>(gd, u, ud);
-}
-// g and dg[a][b][c] = ∂_c g_ab (∂_t g included) at a 4-position: rtgr_eval_metric_*, make_canvas, redshift
-template <class R>
-RTGR_DEV void grid4_metric(const DevGrid<R>& G, const R x[4], R g[4][4], R dg[4][4][4]) {
-    R v[10], d[4][10];
-    grid4_eval<R>(G, grid4_time<R>(G), x[0], x + 1, v, d);
-#pragma unroll
-    for (int p = 0; p < 4; p++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int c = p <= q ? grid_comp(p, q) : grid_comp(q, p);
-            g[p][q] = v[c];
-#pragma unroll
-            for (int j = 0; j < 4; j++) dg[p][q][j] = d[j][c];
-        }
-}
+}  // namespace rtgr
+#include "rtgr_grid_interp.hpp"   // metrics given as samples on a grid: the interpolant and the Sampled<R, METRIC> trait accel<> reads
+namespace rtgr {
 
 // generic RHS as a function of the 8-vector state (parity hook rtgr_eval_geodesic path 1: IEEE division, all four
 // coordinates seeded — the reference's formulation to the letter)

@@ -83,14 +83,6 @@ __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs<R> A) {
     }
 }
 
-template <class R, int METRIC, bool SPIN = false> constexpr int waves_per_simd_of(int mode) {
-    if (METRIC == RTGR_GENERIC_BASE + RTGR_GRID) return sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GRID : RTGR_WAVES_PER_SIMD_GRID_F32;
-    if (METRIC == RTGR_GENERIC_BASE + (int)RTGR_GRID4) return sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GRID4 : RTGR_WAVES_PER_SIMD_GRID4_F32;
-    if (METRIC >= RTGR_GENERIC_BASE) return sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD_GENERIC : RTGR_WAVES_PER_SIMD_GENERIC_F32;
-    if (mode == MODE_FAR) return sizeof(R) == 8 ? (SPIN ? RTGR_WAVES_PER_SIMD_SPIN_FAR : RTGR_WAVES_PER_SIMD_FAR) : 4;
-    return sizeof(R) == 8 ? RTGR_WAVES_PER_SIMD : RTGR_WAVES_PER_SIMD_F32;
-}
-
 template <class R, int METRIC, bool SPIN>
 static int launch_integrate(LaunchEnv& E, const IntegrateArgs<R>& IA, bool npts10, bool split, uint64_t waves, hipStream_t st) {
     constexpr bool USER = (METRIC == RTGR_GENERIC_BASE + RTGR_USER);

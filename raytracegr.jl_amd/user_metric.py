@@ -27,9 +27,7 @@ from . import isa_exec as _isa
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 TEMPLATE = os.path.join(CSRC, "rtgr_user_unit.hip.in")
-_HEADERS = [os.path.join(CSRC, f) for f in ("rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_integrator.hpp",
-                                            "rtgr_persistent.hpp", "rtgr_tsit5_tables.hpp")] + \
-           [os.path.join(HERE, "..", "include", "rtgr.h")]
+_HEADERS = [os.path.join(CSRC, f) for f in _build.UNIT_HEADERS]   # (the one list of device headers: build.py)
 FLAGS = ["--cuda-device-only", "--no-gpu-bundle-output", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wall", "-Wno-unused-function"]
 LLVM_BIN = os.path.join(os.path.dirname(os.path.realpath(_build.HIPCC)), "..", "lib", "llvm", "bin")
 _ids = {}  # (context handle value or None, code object path) -> module id returned by rtgr_user_metric_load

@@ -221,6 +221,40 @@ def test_the_library_in_the_tree_was_built_from_the_headers_in_the_tree():
     assert fn() == _build_module("rtgr_build_t3").header_hash(), "stale librtgr_hip.so: python -c 'import __graft_entry__ as g; g.build()'"
 
 
+def test_the_device_header_lists_name_the_same_files():
+    """The device headers exist as ONE Python list (build.py; user_metric.py takes it from there) and one C++ list (rtgr_units.hip
+    header_hash_of: the route that builds a unit without Python).  A header on one side only — or one the kernels #include that
+    neither side hashes — lets a cached unit built from stale device code load silently; say which file."""
+    import re
+    from scenes import rt
+    b = _build_module("rtgr_build_t4")
+    um = sys.modules[rt.__name__ + ".user_metric"]
+    src = open(os.path.join(CSRC, "rtgr_units.hip")).read()
+    body = re.search(r"static int header_hash_of\(.*?\n}\n", src, re.S).group(0)
+    cxx = re.findall(r'"([^"]+\.(?:hpp|h))"', body)
+    for f in b.UNIT_HEADERS:
+        assert f.replace(os.sep, "/") in cxx, f"{f}: in build.py UNIT_HEADERS, missing from rtgr_units.hip header_hash_of"
+    for f in cxx:
+        assert f in [g.replace(os.sep, "/") for g in b.UNIT_HEADERS], f"{f}: in rtgr_units.hip header_hash_of, missing from build.py UNIT_HEADERS"
+    assert cxx == [g.replace(os.sep, "/") for g in b.UNIT_HEADERS], "same files, but not in the same order: the two hashes differ"
+    assert [os.path.normpath(f) for f in um._HEADERS] == [os.path.normpath(os.path.join(CSRC, f)) for f in b.UNIT_HEADERS]
+    for f in b.UNIT_HEADERS[:-1]:
+        assert f in b.KERNEL_HEADERS, f"{f}: a run-time unit is built from it, but kernel_source_hash does not cover it"
+    # … and every project header the device code reaches by #include is on the lists
+    seen, todo = set(), ["rtgr_user_unit.hip.in", "rtgr_pipeline.hpp"]
+    while todo:
+        f = todo.pop()
+        for inc in re.findall(r'^#include "([^"]+)"', open(os.path.join(CSRC, f)).read(), re.M):
+            inc = os.path.basename(inc)
+            if inc not in seen and os.path.exists(os.path.join(CSRC, inc)):
+                seen.add(inc)
+                todo.append(inc)
+    for f in sorted(seen - {"rtgr_host.hpp", "rtgr_pipeline.hpp"}):
+        assert f in b.KERNEL_HEADERS, f"{f}: #included by the kernels, missing from build.py KERNEL_HEADERS"
+        if f != "rtgr_packed_f32.hpp":
+            assert f in b.UNIT_HEADERS, f"{f}: #included by run-time units, missing from build.py UNIT_HEADERS"
+
+
 def test_no_kernel_of_the_library_keeps_its_arguments_in_scratch(tmp_path):
     """A kernel's argument block (ResolveArgs / IntegrateArgs with the scene's 16 inline objects: 1.4 KB) is read with scalar loads
     from the kernarg segment.  One unlucky access pattern — a per-lane index into the inline objects next to a walk over the device
