@@ -636,8 +636,7 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
         if (out->redshift) {
             if (A.sc.metric == RTGR_USER && !(sizeof(R) == 8 ? user->redshift : user->redshift_f32))
                 return fail(RTGR_ERR_BAD_ARG, "rtgr_ray_outputs.redshift: this user-metric code object carries no rtgr_user_redshift kernel (rebuild the unit)");
-            if (!out->state_end || !(out->hit || out->hit32))
-                return fail(RTGR_ERR_BAD_ARG, "rtgr_ray_outputs.redshift needs state_end and hit (or hit32) in the same call");
+            if ((rc = check_redshift_outputs(out))) return rc;
         }
     }
     if (win) { A.plane_stride = win->plane_stride; A.out_offset = win->out_offset; A.nan_flag = win->nan_flag; }
@@ -660,12 +659,8 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
             HIP_TRY(launch_module(sizeof(R) == 8 ? user->redshift : user->redshift_f32, (unsigned)((nr + 255) / 256), 256, st, A.sc, A.cam,
                                   A.state0, ni, nj, j0, jstride, nr, A.out_offset, (const R*)A.state_end, (const uint8_t*)A.hit,
                                   (const uint32_t*)A.hit32, (R*)out->redshift));
-        } else if constexpr (sizeof(R) == 8) {
-            rc = misc_redshift_f64(A.sc, A.cam, (const double*)A.state0, ni, nj, j0, jstride, nr, A.out_offset,
-                                   (const double*)A.state_end, A.hit, A.hit32, (double*)out->redshift, st);
         } else {
-            rc = misc_redshift_f32(A.sc, A.cam, (const float*)A.state0, ni, nj, j0, jstride, nr, A.out_offset,
-                                   (const float*)A.state_end, A.hit, A.hit32, (float*)out->redshift, st);
+            rc = misc_redshift<R>(A.sc, A.cam, A.state0, ni, nj, j0, jstride, nr, A.out_offset, A.state_end, A.hit, A.hit32, (R*)out->redshift, st);
         }
         if (rc) return rc;
     }
@@ -881,36 +876,25 @@ int api::reserve_workspace(rtgr_context* ctx, const void* d_any, void* stream, u
     return ensure_workspace(*D, *ss, bytes, (hipStream_t)stream);
 }
 
-int api::trace_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double* d_state0,
-                          const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, double* d_rgb,
-                          const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream) {
+template <class R>
+int api::trace_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R* d_state0, const rtgr_camera* cam,
+                      uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* d_counters,
+                      void* stream) {
     if (!d_rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     RESOLVE_DEVICE(d_rgb);
-    return trace_device<double>(*D, scene, opt, d_state0, cam, ni, nj, j0, j1, d_rgb, out, d_counters, (hipStream_t)stream);
+    return rtgr::trace_device<R>(*D, scene, opt, d_state0, cam, ni, nj, j0, j1, d_rgb, out, d_counters, (hipStream_t)stream);
 }
-int api::trace_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float* d_state0,
-                          const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, float* d_rgb,
-                          const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream) {
-    if (!d_rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
-    RESOLVE_DEVICE(d_rgb);
-    return trace_device<float>(*D, scene, opt, d_state0, cam, ni, nj, j0, j1, d_rgb, out, d_counters, (hipStream_t)stream);
-}
-int api::trace_rows_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam,
-                               uint64_t ni, uint64_t nj, uint64_t j0, uint64_t jstride, uint64_t nrows, double* d_rgb,
-                               const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream) {
+template <class R>
+int api::trace_rows_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                           uint64_t nj, uint64_t j0, uint64_t jstride, uint64_t nrows, R* d_rgb, const rtgr_ray_outputs* out,
+                           rtgr_counters* d_counters, void* stream) {
     if (!cam) return fail(RTGR_ERR_BAD_ARG, "camera is NULL");
     if (!d_rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     RESOLVE_DEVICE(d_rgb);
-    return trace_device<double>(*D, scene, opt, nullptr, cam, ni, nj, j0, j0 + 1, d_rgb, out, d_counters, (hipStream_t)stream, jstride, nrows);
+    return rtgr::trace_device<R>(*D, scene, opt, nullptr, cam, ni, nj, j0, j0 + 1, d_rgb, out, d_counters, (hipStream_t)stream, jstride, nrows);
 }
-int api::trace_rows_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam,
-                               uint64_t ni, uint64_t nj, uint64_t j0, uint64_t jstride, uint64_t nrows, float* d_rgb,
-                               const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream) {
-    if (!cam) return fail(RTGR_ERR_BAD_ARG, "camera is NULL");
-    if (!d_rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
-    RESOLVE_DEVICE(d_rgb);
-    return trace_device<float>(*D, scene, opt, nullptr, cam, ni, nj, j0, j0 + 1, d_rgb, out, d_counters, (hipStream_t)stream, jstride, nrows);
-}
+RTGR_INSTANTIATE_F64_F32(api::trace_device);
+RTGR_INSTANTIATE_F64_F32(api::trace_rows_device);
 
 }  // namespace rtgr
 

@@ -7,8 +7,8 @@ namespace rtgr {
 
 // ---- camera / hooks ------------------------------------------------------------------------------------------------------
 template <class R>
-static int make_canvas_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
-                              uint64_t j0, uint64_t j1, R* d_state0, void* stream) {
+int api::make_canvas_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                            uint64_t j0, uint64_t j1, R* d_state0, void* stream) {
     if (!cam || !d_state0) return fail(RTGR_ERR_BAD_ARG, "NULL argument");
     RESOLVE_DEVICE(d_state0);
     if (ni == 0 || nj == 0 || j1 <= j0 || j1 > nj) return fail(RTGR_ERR_BAD_ARG, "bad canvas range");
@@ -27,12 +27,11 @@ static int make_canvas_device(rtgr_context* ctx, const rtgr_scene* scene, const 
                               (uint64_t)0, n, d_state0));
         return RTGR_OK;
     }
-    if constexpr (sizeof(R) == 8) return misc_canvas_f64(sc, cm, ni, nj, j0, n, d_state0, (hipStream_t)stream);
-    else return misc_canvas_f32(sc, cm, ni, nj, j0, n, d_state0, (hipStream_t)stream);
+    return misc_canvas<R>(sc, cm, ni, nj, j0, n, d_state0, (hipStream_t)stream);
 }
 template <class R>
-static int make_canvas_host(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0,
-                            uint64_t j1, R* state0) {
+int api::make_canvas(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0,
+                     uint64_t j1, R* state0) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
@@ -47,25 +46,11 @@ static int make_canvas_host(rtgr_context* ctx, const rtgr_scene* scene, const rt
     HIP_TRY(hipMemcpy(state0, b.p, n * 8 * sizeof(R), hipMemcpyDeviceToHost));
     return RTGR_OK;
 }
-int api::make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
-                                uint64_t j0, uint64_t j1, double* d_state0, void* stream) {
-    return make_canvas_device<double>(ctx, scene, cam, ni, nj, j0, j1, d_state0, stream);
-}
-int api::make_canvas_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
-                                uint64_t j0, uint64_t j1, float* d_state0, void* stream) {
-    return make_canvas_device<float>(ctx, scene, cam, ni, nj, j0, j1, d_state0, stream);
-}
-int api::make_canvas_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0,
-                         uint64_t j1, double* state0) {
-    return make_canvas_host<double>(ctx, scene, cam, ni, nj, j0, j1, state0);
-}
-int api::make_canvas_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0,
-                         uint64_t j1, float* state0) {
-    return make_canvas_host<float>(ctx, scene, cam, ni, nj, j0, j1, state0);
-}
+RTGR_INSTANTIATE_F64_F32(api::make_canvas_device);
+RTGR_INSTANTIATE_F64_F32(api::make_canvas);
 
 template <class R>
-static int eval_metric_host(rtgr_context* ctx, const rtgr_scene* scene, const R* x, uint64_t n, R* g, R* dg, R* Gam) {
+int api::eval_metric(rtgr_context* ctx, const rtgr_scene* scene, const R* x, uint64_t n, R* g, R* dg, R* Gam) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
@@ -88,10 +73,8 @@ static int eval_metric_host(rtgr_context* ctx, const rtgr_scene* scene, const R*
         if (sizeof(R) != 8) return fail(RTGR_ERR_BAD_ARG, "user metrics are evaluated in Float64");
         HIP_TRY(launch_module(user->eval_metric, (unsigned)((n + 255) / 256), 256, (hipStream_t) nullptr, sc, (const R*)bx.p, n,
                               (R*)bg.p, (R*)bd.p, (R*)bG.p));
-    } else if constexpr (sizeof(R) == 8) {
-        if ((rc = misc_eval_metric_f64(sc, (const double*)bx.p, n, (double*)bg.p, (double*)bd.p, (double*)bG.p, nullptr))) return rc;
     } else {
-        if ((rc = misc_eval_metric_f32(sc, (const float*)bx.p, n, (float*)bg.p, (float*)bd.p, (float*)bG.p, nullptr))) return rc;
+        if ((rc = misc_eval_metric<R>(sc, (const R*)bx.p, n, (R*)bg.p, (R*)bd.p, (R*)bG.p, nullptr))) return rc;
     }
     HIP_TRY(hipDeviceSynchronize());
     if (g) HIP_TRY(hipMemcpy(g, bg.p, n * 16 * sizeof(R), hipMemcpyDeviceToHost));
@@ -99,15 +82,10 @@ static int eval_metric_host(rtgr_context* ctx, const rtgr_scene* scene, const R*
     if (Gam) HIP_TRY(hipMemcpy(Gam, bG.p, n * 64 * sizeof(R), hipMemcpyDeviceToHost));
     return RTGR_OK;
 }
-int api::eval_metric_f64(rtgr_context* ctx, const rtgr_scene* scene, const double* x, uint64_t n, double* g, double* dg, double* Gam) {
-    return eval_metric_host<double>(ctx, scene, x, n, g, dg, Gam);
-}
-int api::eval_metric_f32(rtgr_context* ctx, const rtgr_scene* scene, const float* x, uint64_t n, float* g, float* dg, float* Gam) {
-    return eval_metric_host<float>(ctx, scene, x, n, g, dg, Gam);
-}
+RTGR_INSTANTIATE_F64_F32(api::eval_metric);
 
 template <class R>
-static int eval_geodesic_host(rtgr_context* ctx, const rtgr_scene* scene, const R* s, uint64_t n, int path, R* ds) {
+int api::eval_geodesic(rtgr_context* ctx, const rtgr_scene* scene, const R* s, uint64_t n, int path, R* ds) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
@@ -131,17 +109,15 @@ static int eval_geodesic_host(rtgr_context* ctx, const rtgr_scene* scene, const 
         if (path == 2 && !user->eval_accel) return fail(RTGR_ERR_BAD_ARG, "this user-metric code object carries no rtgr_user_eval_accel");
         HIP_TRY(launch_module(path == 2 ? user->eval_accel : user->eval_geodesic, (unsigned)((n + 255) / 256), 256,
                               (hipStream_t) nullptr, sc, (const R*)bi.p, n, (R*)bo.p));
-    } else if constexpr (sizeof(R) == 8) {
-        if ((rc = misc_eval_geodesic_f64(sc, (const double*)bi.p, n, path, (double*)bo.p, nullptr))) return rc;
     } else {
-        if ((rc = misc_eval_geodesic_f32(sc, (const float*)bi.p, n, path, (float*)bo.p, nullptr))) return rc;
+        if ((rc = misc_eval_geodesic<R>(sc, (const R*)bi.p, n, path, (R*)bo.p, nullptr))) return rc;
     }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(ds, bo.p, n * 8 * sizeof(R), hipMemcpyDeviceToHost));
     return RTGR_OK;
 }
 template <class R>
-static int eval_objects_host(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R* x, uint64_t n, R* d, R* dmin, uint8_t* hit, R* rgb) {
+int api::eval_objects(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R* x, uint64_t n, R* d, R* dmin, uint8_t* hit, R* rgb) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
@@ -168,10 +144,8 @@ static int eval_objects_host(rtgr_context* ctx, const rtgr_scene* scene, const r
         hipFunction_t f = sizeof(R) == 8 ? user->eval_objects : user->eval_objects_f32;
         if (!f) return fail(RTGR_ERR_BAD_ARG, "this unit carries no rtgr_user_eval_objects kernel (rebuild the unit)");
         HIP_TRY(launch_module(f, (unsigned)((n + 255) / 256), 256, (hipStream_t) nullptr, sc, so, (const R*)bx.p, n, (R*)bd.p, (R*)bm.p, (uint8_t*)bh.p, (R*)bc.p));
-    } else if constexpr (sizeof(R) == 8) {
-        if ((rc = misc_eval_objects_f64(sc, so, (const double*)bx.p, n, (double*)bd.p, (double*)bm.p, (uint8_t*)bh.p, (double*)bc.p, nullptr))) return rc;
     } else {
-        if ((rc = misc_eval_objects_f32(sc, so, (const float*)bx.p, n, (float*)bd.p, (float*)bm.p, (uint8_t*)bh.p, (float*)bc.p, nullptr))) return rc;
+        if ((rc = misc_eval_objects<R>(sc, so, (const R*)bx.p, n, (R*)bd.p, (R*)bm.p, (uint8_t*)bh.p, (R*)bc.p, nullptr))) return rc;
     }
     HIP_TRY(hipDeviceSynchronize());
     if (d) HIP_TRY(hipMemcpy(d, bd.p, nd * sizeof(R), hipMemcpyDeviceToHost));
@@ -180,20 +154,9 @@ static int eval_objects_host(rtgr_context* ctx, const rtgr_scene* scene, const r
     if (rgb) HIP_TRY(hipMemcpy(rgb, bc.p, n * 3 * sizeof(R), hipMemcpyDeviceToHost));
     return RTGR_OK;
 }
-int api::eval_objects_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double* x, uint64_t n, double* d, double* dmin,
-                          uint8_t* hit, double* rgb) {
-    return eval_objects_host<double>(ctx, scene, opt, x, n, d, dmin, hit, rgb);
-}
-int api::eval_objects_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float* x, uint64_t n, float* d, float* dmin,
-                          uint8_t* hit, float* rgb) {
-    return eval_objects_host<float>(ctx, scene, opt, x, n, d, dmin, hit, rgb);
-}
-int api::eval_geodesic_f64(rtgr_context* ctx, const rtgr_scene* scene, const double* s, uint64_t n, int path, double* ds) {
-    return eval_geodesic_host<double>(ctx, scene, s, n, path, ds);
-}
-int api::eval_geodesic_f32(rtgr_context* ctx, const rtgr_scene* scene, const float* s, uint64_t n, int path, float* ds) {
-    return eval_geodesic_host<float>(ctx, scene, s, n, path, ds);
-}
+RTGR_INSTANTIATE_F64_F32(api::eval_geodesic);
+RTGR_INSTANTIATE_F64_F32(api::eval_objects);
+
 int api::eval_fastmath_f64(rtgr_context* ctx, const double* x, uint64_t n, double* rcp, double* rsq) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);

@@ -258,33 +258,25 @@ int launch_f64_grid4(LaunchEnv& E, const TraceArgs<double>& A, hipStream_t st); 
 int launch_f32_grid4(LaunchEnv& E, const TraceArgs<float>& A, hipStream_t st);
 
 // ---- small kernels (rtgr_misc.hip) -------------------------------------------------------------------------------------
-int misc_canvas_f64(const DevScene<double>& sc, const DevCamera<double>& cam, uint64_t ni, uint64_t nj, uint64_t j0,
-                    uint64_t n, double* d_state0, hipStream_t st);
-int misc_canvas_f32(const DevScene<float>& sc, const DevCamera<float>& cam, uint64_t ni, uint64_t nj, uint64_t j0,
-                    uint64_t n, float* d_state0, hipStream_t st);
-int misc_eval_metric_f64(const DevScene<double>& sc, const double* d_x, uint64_t n, double* g, double* dg, double* Gam, hipStream_t st);
-int misc_eval_metric_f32(const DevScene<float>& sc, const float* d_x, uint64_t n, float* g, float* dg, float* Gam, hipStream_t st);
-int misc_eval_geodesic_f64(const DevScene<double>& sc, const double* d_s, uint64_t n, int path, double* d_ds, hipStream_t st);
-int misc_eval_geodesic_f32(const DevScene<float>& sc, const float* d_s, uint64_t n, int path, float* d_ds, hipStream_t st);
-int misc_eval_objects_f64(const DevScene<double>& sc, const DevSolver<double>& opt, const double* d_x, uint64_t n, double* d, double* dmin, uint8_t* hit,
-                          double* rgb, hipStream_t st);
-int misc_eval_objects_f32(const DevScene<float>& sc, const DevSolver<float>& opt, const float* d_x, uint64_t n, float* d, float* dmin, uint8_t* hit,
-                          float* rgb, hipStream_t st);
+// (templates over the scalar type: defined and instantiated for double and float in rtgr_misc.hip)
+#define RTGR_INSTANTIATE_F64_F32(fn) template decltype(fn<double>) fn<double>; template decltype(fn<float>) fn<float>
+template <class R>
+int misc_canvas(const DevScene<R>& sc, const DevCamera<R>& cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t n, R* d_state0, hipStream_t st);
+template <class R>
+int misc_eval_metric(const DevScene<R>& sc, const R* d_x, uint64_t n, R* g, R* dg, R* Gam, hipStream_t st);
+template <class R>
+int misc_eval_geodesic(const DevScene<R>& sc, const R* d_s, uint64_t n, int path, R* d_ds, hipStream_t st);
+template <class R>
+int misc_eval_objects(const DevScene<R>& sc, const DevSolver<R>& opt, const R* d_x, uint64_t n, R* d, R* dmin, uint8_t* hit, R* rgb, hipStream_t st);
+template <class R>
+int misc_redshift(const DevScene<R>& sc, const DevCamera<R>& cam, const R* d_state0, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t jstride,
+                  uint64_t n, uint64_t out_offset, const R* d_state_end, const uint8_t* d_hit, const uint32_t* d_hit32, R* d_red, hipStream_t st);
 int misc_eval_fastmath_f64(const double* d_x, uint64_t n, double* d_rcp, double* d_rsq, hipStream_t st);
-int misc_redshift_f64(const DevScene<double>& sc, const DevCamera<double>& cam, const double* d_state0, uint64_t ni, uint64_t nj,
-                      uint64_t j0, uint64_t jstride, uint64_t n, uint64_t out_offset, const double* d_state_end,
-                      const uint8_t* d_hit, const uint32_t* d_hit32, double* d_red, hipStream_t st);
-int misc_redshift_f32(const DevScene<float>& sc, const DevCamera<float>& cam, const float* d_state0, uint64_t ni, uint64_t nj,
-                      uint64_t j0, uint64_t jstride, uint64_t n, uint64_t out_offset, const float* d_state_end,
-                      const uint8_t* d_hit, const uint32_t* d_hit32, float* d_red, hipStream_t st);
 int misc_quantize(const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, hipStream_t st);
-// multi-device gather on device 0: rows of rank r (cyclic over nranks) back into place
-int misc_place_rows_f64(const double* d_part, uint64_t ni, uint64_t nj, uint64_t rank, uint64_t nranks, uint64_t planes,
-                        double* d_full, hipStream_t st);
-int misc_place_rows_f32(const float* d_part, uint64_t ni, uint64_t nj, uint64_t rank, uint64_t nranks, uint64_t planes,
-                        float* d_full, hipStream_t st);
-int misc_place_rows_u8(const uint8_t* d_part, uint64_t ni, uint64_t nj, uint64_t rank, uint64_t nranks, uint64_t elem,
-                       uint8_t* d_full, hipStream_t st);
+// multi-device gather on device 0: rows of rank r (cyclic over nranks) back into place; `planes` planes of `elem` T per ray
+// (T = double / float / uint8_t)
+template <class T>
+int misc_place_rows(const T* d_part, uint64_t ni, uint64_t nj, uint64_t rank, uint64_t nranks, uint64_t planes, uint64_t elem, T* d_full, hipStream_t st);
 int misc_poison_registers(int n_cu, unsigned pattern, hipStream_t st);   // the load-time probe's scrubber (rtgr_misc.hip)
 
 }  // namespace rtgr

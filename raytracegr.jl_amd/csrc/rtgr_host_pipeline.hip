@@ -32,9 +32,6 @@ void parallel_rows(uint64_t n, size_t bytes_per_item, F&& body) {  // body(first
     for (auto& t : th) t.join();
 }
 
-// One output array of a host-pointer call: `planes` planes (rgb: 3, else 1) of `elem` bytes per ray.
-struct OutArray { void* host; size_t elem; int planes; size_t dev_off; };
-
 // The host-pointer hot path (rtgr_trace_f64 / _f32 / _pixels_f64 / _one_f64).  Rays [0, n) are rows [j0, j1) of the
 // canvas; the job is cut into compute chunks of whole rows (~2^22 rays: big enough that the persistent kernels lose
 // nothing, SURVEY §6 / DESIGN §4.2) and each chunk's input into transfer pieces (~2^20 rays).  Three streams:
@@ -84,27 +81,9 @@ int trace_host_pipelined(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solve
     };
 
     // ---- output arrays ---------------------------------------------------------------------------------------------
-    std::vector<OutArray> outs;
-    size_t dev_bytes = 0;
-    auto add = [&](void* host, size_t elem, int planes) {
-        outs.push_back({host, elem, planes, dev_bytes});
-        dev_bytes += align256((size_t)n * elem * planes);
-    };
-    add(px_in ? nullptr : (void*)rgb, sizeof(R), 3);  // [0] = rgb, always (pixels: unpacked into px_out)
-    rtgr_ray_outputs dout;
-    std::memset(&dout, 0, sizeof dout);
-    if (out) {
-        if (out->redshift && (!out->state_end || !(out->hit || out->hit32)))
-            return fail(RTGR_ERR_BAD_ARG, "rtgr_ray_outputs.redshift needs state_end and hit (or hit32) in the same call");
-        if (out->state_end) add(out->state_end, 8 * sizeof(R), 1);
-        if (out->lambda_end) add(out->lambda_end, sizeof(R), 1);
-        if (out->status) add(out->status, 1, 1);
-        if (out->hit) add(out->hit, 1, 1);
-        if (out->n_accept) add(out->n_accept, 4, 1);
-        if (out->n_reject) add(out->n_reject, 4, 1);
-        if (out->redshift) add(out->redshift, sizeof(R), 1);
-        if (out->hit32) add(out->hit32, 4, 1);
-    }
+    if ((rc = check_redshift_outputs(out))) return rc;
+    std::vector<RayArray> outs = ray_arrays(px_in ? nullptr : (void*)rgb, out, sizeof(R));  // (pixels: rgb is unpacked into px_out)
+    const size_t dev_bytes = ray_arrays_layout(outs, n);
     size_t out_bytes_per_ray = 0;
     for (auto& o : outs) out_bytes_per_ray += o.elem * o.planes;
 
@@ -176,20 +155,8 @@ int trace_host_pipelined(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solve
     uint32_t* d_nan = (uint32_t*)(dsmall + 128);
     HIP_TRY(hipMemsetAsync(dsmall, 0, 256, S->s_comp));
     char* dob = (char*)S->d_out.p;
-    R* d_rgb = (R*)(dob + outs[0].dev_off);
-    {
-        size_t k = 1;
-        if (out) {
-            if (out->state_end) dout.state_end = dob + outs[k++].dev_off;
-            if (out->lambda_end) dout.lambda_end = dob + outs[k++].dev_off;
-            if (out->status) dout.status = (uint8_t*)(dob + outs[k++].dev_off);
-            if (out->hit) dout.hit = (uint8_t*)(dob + outs[k++].dev_off);
-            if (out->n_accept) dout.n_accept = (uint32_t*)(dob + outs[k++].dev_off);
-            if (out->n_reject) dout.n_reject = (uint32_t*)(dob + outs[k++].dev_off);
-            if (out->redshift) dout.redshift = dob + outs[k++].dev_off;
-            if (out->hit32) dout.hit32 = (uint32_t*)(dob + outs[k++].dev_off);
-        }
-    }
+    R* d_rgb = (R*)(dob + outs[0].off);
+    const rtgr_ray_outputs dout = ray_outputs_at(dob, outs, out);
     R* d_in = (R*)S->d_in.p;
 
     std::vector<hipEvent_t> ev_comp(nchunks), ev_down(nchunks), ev_setup(nchunks);
@@ -224,7 +191,7 @@ int trace_host_pipelined(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solve
             const char* src = (const char*)S->pin_out[c % Staging::OUT_SLOTS].p;
             size_t off = 0;
             for (size_t k = 0; k < outs.size(); k++) {
-                const OutArray& o = outs[k];
+                const RayArray& o = outs[k];
                 if (k == 0 && px_in) {  // Pixel(p.pos, p.normal, col)  (:532)
                     const R* pr = (const R*)(src + off);
                     parallel_rows(m, 11 * sizeof(R), [&](uint64_t a, uint64_t cnt) {
@@ -240,7 +207,7 @@ int trace_host_pipelined(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solve
                     });
                 } else {
                     for (int pl = 0; pl < o.planes; pl++) {
-                        char* dst = (char*)o.host + (size_t)pl * n_slab * o.elem;
+                        char* dst = (char*)o.ptr + (size_t)pl * n_slab * o.elem;
                         const char* s2 = src + off + (size_t)pl * m * o.elem;
                         parallel_rows(m, o.elem, [&](uint64_t a, uint64_t cnt) {
                             for_runs(r0 + a, cnt, [&](uint64_t l0, uint64_t g0, uint64_t len) {
@@ -272,7 +239,7 @@ int trace_host_pipelined(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solve
         size_t off = 0;
         for (auto& o : outs) {
             for (int pl = 0; pl < o.planes; pl++)
-                HIP_TRY(hipMemcpyAsync(dst + off + (size_t)pl * m * o.elem, dob + o.dev_off + ((size_t)pl * n + r0) * o.elem,
+                HIP_TRY(hipMemcpyAsync(dst + off + (size_t)pl * m * o.elem, dob + o.off + ((size_t)pl * n + r0) * o.elem,
                                        (size_t)m * o.elem, hipMemcpyDeviceToHost, S->s_down));
             off += align256((size_t)m * o.elem * o.planes);
         }
@@ -383,17 +350,13 @@ int trace_host_all_devices(rtgr_context* c, const rtgr_scene* scene, const rtgr_
         if (rcs[k]) return fail(rcs[k], "device " + std::to_string(c->devs[k]->dev) + " (entry " + std::to_string(k) + " of the context): " + errs[k]);
     if (ctr) {
         std::memset(ctr, 0, sizeof *ctr);
-        for (uint64_t k = 0; k < N; k++) {
-            const uint64_t* p = (const uint64_t*)&ctrs[k];
-            uint64_t* q = (uint64_t*)ctr;
-            for (int w = 0; w < 8; w++) q[w] = (w == 7) ? (q[w] > p[w] ? q[w] : p[w]) : q[w] + p[w];   // [7] is a maximum (diagnostics)
-        }
+        for (uint64_t k = 0; k < N; k++) merge_counters(*ctr, ctrs[k]);
     }
     return RTGR_OK;
 }
 
 template <class R>
-int trace_host(rtgr_context* ctx_in, const rtgr_scene* scene, const rtgr_solver* opt, const R* state0, const rtgr_camera* cam,
+int api::trace(rtgr_context* ctx_in, const rtgr_scene* scene, const rtgr_solver* opt, const R* state0, const rtgr_camera* cam,
                uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx_in, &c);
@@ -405,25 +368,11 @@ int trace_host(rtgr_context* ctx_in, const rtgr_scene* scene, const rtgr_solver*
     return trace_host_all_devices<R>(c, scene, opt, state0, nullptr, nullptr, cam, ni, nj, j0, j1, rgb, out, ctr);
 }
 
-template int trace_host<double>(rtgr_context*, const rtgr_scene*, const rtgr_solver*, const double*, const rtgr_camera*, uint64_t, uint64_t, uint64_t,
-                                uint64_t, double*, const rtgr_ray_outputs*, rtgr_counters*);
-template int trace_host<float>(rtgr_context*, const rtgr_scene*, const rtgr_solver*, const float*, const rtgr_camera*, uint64_t, uint64_t, uint64_t,
-                               uint64_t, float*, const rtgr_ray_outputs*, rtgr_counters*);
-
-int api::trace_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double* state0,
-                   const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, double* rgb,
-                   const rtgr_ray_outputs* out, rtgr_counters* ctr) {
-    return trace_host<double>(ctx, scene, opt, state0, cam, ni, nj, j0, j1, rgb, out, ctr);
-}
-int api::trace_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float* state0,
-                   const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, float* rgb,
-                   const rtgr_ray_outputs* out, rtgr_counters* ctr) {
-    return trace_host<float>(ctx, scene, opt, state0, cam, ni, nj, j0, j1, rgb, out, ctr);
-}
+RTGR_INSTANTIATE_F64_F32(api::trace);
 
 template <class R>
-static int trace_pixels(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R* pixels_in, uint64_t ni,
-                        uint64_t nj, R* pixels_out, rtgr_counters* ctr) {
+int api::trace_pixels(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R* pixels_in, uint64_t ni,
+                      uint64_t nj, R* pixels_out, rtgr_counters* ctr) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
@@ -433,8 +382,8 @@ static int trace_pixels(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_s
     return trace_host_all_devices<R>(c, scene, opt, nullptr, pixels_in, pixels_out, nullptr, ni, nj, 0, nj, nullptr, nullptr, ctr);
 }
 template <class R>
-static int trace_one(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R pos[4], const R normal[4],
-                     R rgb[3], R state_end[8], uint8_t* status) {
+int api::trace_one(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R pos[4], const R normal[4],
+                   R rgb[3], R state_end[8], uint8_t* status) {
     if (!pos || !normal || !rgb) return fail(RTGR_ERR_BAD_ARG, "NULL argument");
     R s0[8];
     for (int q = 0; q < 4; q++) { s0[q] = pos[q]; s0[4 + q] = normal[q]; }
@@ -442,24 +391,10 @@ static int trace_one(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solv
     std::memset(&out, 0, sizeof out);
     out.state_end = state_end;
     out.status = status;
-    return trace_host<R>(ctx, scene, opt, s0, nullptr, 1, 1, 0, 1, rgb, &out, nullptr);
+    return trace<R>(ctx, scene, opt, s0, nullptr, 1, 1, 0, 1, rgb, &out, nullptr);
 }
-int api::trace_pixels_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double* pixels_in,
-                          uint64_t ni, uint64_t nj, double* pixels_out, rtgr_counters* ctr) {
-    return trace_pixels<double>(ctx, scene, opt, pixels_in, ni, nj, pixels_out, ctr);
-}
-int api::trace_pixels_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float* pixels_in,
-                          uint64_t ni, uint64_t nj, float* pixels_out, rtgr_counters* ctr) {
-    return trace_pixels<float>(ctx, scene, opt, pixels_in, ni, nj, pixels_out, ctr);
-}
-int api::trace_one_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double pos[4],
-                       const double normal[4], double rgb[3], double state_end[8], uint8_t* status) {
-    return trace_one<double>(ctx, scene, opt, pos, normal, rgb, state_end, status);
-}
-int api::trace_one_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float pos[4],
-                       const float normal[4], float rgb[3], float state_end[8], uint8_t* status) {
-    return trace_one<float>(ctx, scene, opt, pos, normal, rgb, state_end, status);
-}
+RTGR_INSTANTIATE_F64_F32(api::trace_pixels);
+RTGR_INSTANTIATE_F64_F32(api::trace_one);
 
 // ---------------------------------------------------------------------------------------------------------------------
 // several frames in one call, two in flight (an extension: the reference renders one frame per call, :560, :596)
@@ -473,9 +408,9 @@ int api::trace_one_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_so
 // thread through its second, every frame over ALL devices of the context exactly as rtgr_trace_f64 / rtgr_trace_pixels_f64 deal
 // it.  Frame k's results are those of the single call, bit for bit (tests).
 template <class R>
-static int trace_frames(rtgr_context* ctx_in, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const rtgr_camera* cams,
-                        const R* const* state0s, const R* const* px_in, R* const* px_out, uint64_t ni, uint64_t nj, R* const* rgb,
-                        const rtgr_ray_outputs* outs, rtgr_counters* ctrs) {
+static int trace_frames_any(rtgr_context* ctx_in, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const rtgr_camera* cams,
+                            const R* const* state0s, const R* const* px_in, R* const* px_out, uint64_t ni, uint64_t nj, R* const* rgb,
+                            const rtgr_ray_outputs* outs, rtgr_counters* ctrs) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx_in, &c);
     if (rc) return rc;
@@ -515,21 +450,17 @@ static int trace_frames(rtgr_context* ctx_in, const rtgr_scene* scene, const rtg
     if (rc2) return fail(rc2, "frame " + std::to_string(bad2) + ": " + err2);
     return RTGR_OK;
 }
-int api::trace_frames_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const rtgr_camera* cams,
-                          const double* const* state0s, uint64_t ni, uint64_t nj, double* const* rgb, const rtgr_ray_outputs* outs, rtgr_counters* ctrs) {
-    return trace_frames<double>(ctx, scene, opt, nframes, cams, state0s, nullptr, nullptr, ni, nj, rgb, outs, ctrs);
+template <class R>
+int api::trace_frames(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const rtgr_camera* cams,
+                      const R* const* state0s, uint64_t ni, uint64_t nj, R* const* rgb, const rtgr_ray_outputs* outs, rtgr_counters* ctrs) {
+    return trace_frames_any<R>(ctx, scene, opt, nframes, cams, state0s, nullptr, nullptr, ni, nj, rgb, outs, ctrs);
 }
-int api::trace_frames_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const rtgr_camera* cams,
-                          const float* const* state0s, uint64_t ni, uint64_t nj, float* const* rgb, const rtgr_ray_outputs* outs, rtgr_counters* ctrs) {
-    return trace_frames<float>(ctx, scene, opt, nframes, cams, state0s, nullptr, nullptr, ni, nj, rgb, outs, ctrs);
+template <class R>
+int api::trace_frames_pixels(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const R* const* pixels_in,
+                             uint64_t ni, uint64_t nj, R* const* pixels_out, rtgr_counters* ctrs) {
+    return trace_frames_any<R>(ctx, scene, opt, nframes, nullptr, nullptr, pixels_in, pixels_out, ni, nj, nullptr, nullptr, ctrs);
 }
-int api::trace_frames_pixels_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const double* const* pixels_in,
-                                 uint64_t ni, uint64_t nj, double* const* pixels_out, rtgr_counters* ctrs) {
-    return trace_frames<double>(ctx, scene, opt, nframes, nullptr, nullptr, pixels_in, pixels_out, ni, nj, nullptr, nullptr, ctrs);
-}
-int api::trace_frames_pixels_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const float* const* pixels_in,
-                                 uint64_t ni, uint64_t nj, float* const* pixels_out, rtgr_counters* ctrs) {
-    return trace_frames<float>(ctx, scene, opt, nframes, nullptr, nullptr, pixels_in, pixels_out, ni, nj, nullptr, nullptr, ctrs);
-}
+RTGR_INSTANTIATE_F64_F32(api::trace_frames);
+RTGR_INSTANTIATE_F64_F32(api::trace_frames_pixels);
 
 }  // namespace rtgr

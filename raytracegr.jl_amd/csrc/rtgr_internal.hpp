@@ -6,7 +6,8 @@
 //   rtgr_sharded.hip        one call over every device of a context: cyclic rows, peer copies to device 0
 //   rtgr_hooks.hip          make_canvas and the parity hooks (rtgr_eval_*), image quantisation
 //   rtgr_units.hip          run-time compiled units: build, audit, load-time probe, load, scene check
-//   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name>
+//   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
+//                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
 // Everything here is internal to the library: nothing in this header crosses the C ABI.
 #pragma once
@@ -134,11 +135,6 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
                  rtgr_counters* d_counters, hipStream_t st, uint64_t jstride = 1, uint64_t nrows_strided = 0,
                  const Window* win = nullptr);
 
-// ---- the host-pointer path (rtgr_host_pipeline.hip) ---------------------------------------------------------------------------
-template <class R>
-int trace_host(rtgr_context* ctx_in, const rtgr_scene* scene, const rtgr_solver* opt, const R* state0, const rtgr_camera* cam,
-               uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
-
 // scratch device buffers of the small host-pointer hooks (eval_*, make_canvas, the probe): RAII, synchronous
 struct DevBuf {
     void* p = nullptr;
@@ -157,6 +153,62 @@ int host_has_nan(const R* v, uint64_t count) {
     return 0;
 }
 
+// ---- the per-ray output arrays of a call: rgb plus what rtgr_ray_outputs asks for ------------------------------------------------
+// THE list of the optional arrays, in the order the staging buffers hold them: where the pointer sits in rtgr_ray_outputs, and the
+// bytes per ray — `scalars` of the entry point's type (sizeof(R)) plus `bytes` — in `planes` planes.  A new output is a new row here
+// (and a member of the kernels' TraceArgs, which trace_device copies by name).
+struct RayOutputField { size_t pos, scalars, bytes; int planes; };
+constexpr RayOutputField RAY_OUTPUT_FIELDS[] = {
+    {offsetof(rtgr_ray_outputs, state_end), 8, 0, 1}, {offsetof(rtgr_ray_outputs, lambda_end), 1, 0, 1},
+    {offsetof(rtgr_ray_outputs, status), 0, 1, 1},    {offsetof(rtgr_ray_outputs, hit), 0, 1, 1},
+    {offsetof(rtgr_ray_outputs, n_accept), 0, 4, 1},  {offsetof(rtgr_ray_outputs, n_reject), 0, 4, 1},
+    {offsetof(rtgr_ray_outputs, redshift), 1, 0, 1},  {offsetof(rtgr_ray_outputs, hit32), 0, 4, 1},
+};
+static_assert(sizeof(rtgr_ray_outputs) == sizeof(RAY_OUTPUT_FIELDS) / sizeof(RAY_OUTPUT_FIELDS[0]) * sizeof(void*), "a row per member of rtgr_ray_outputs");
+inline void* ray_output(const rtgr_ray_outputs& o, const RayOutputField& f) {
+    void* p;
+    std::memcpy(&p, (const char*)&o + f.pos, sizeof p);
+    return p;
+}
+// One requested array: `planes` planes (rgb: 3, else 1) of `elem` bytes per ray; `ptr` is the caller's array (host, or the full frame
+// on device 0), `off` its place in a staging buffer (ray_arrays_layout).
+struct RayArray { void* ptr; size_t elem; int planes; size_t off; };
+// [0] = rgb, always; then the arrays `out` asks for.  `scalar` = sizeof(R).
+inline std::vector<RayArray> ray_arrays(void* rgb, const rtgr_ray_outputs* out, size_t scalar) {
+    std::vector<RayArray> arrs{{rgb, scalar, 3, 0}};
+    if (out)
+        for (const RayOutputField& f : RAY_OUTPUT_FIELDS)
+            if (void* p = ray_output(*out, f)) arrs.push_back({p, f.scalars * scalar + f.bytes, f.planes, 0});
+    return arrs;
+}
+// their places in a buffer that holds `m` rays of each; returns the bytes of the buffer
+inline size_t ray_arrays_layout(std::vector<RayArray>& arrs, uint64_t m) {
+    size_t bytes = 0;
+    for (RayArray& a : arrs) { a.off = bytes; bytes += align256((size_t)m * a.elem * a.planes); }
+    return bytes;
+}
+// what `out` asks for, pointing into the buffer at `base` that `arrs` (= ray_arrays(…, out, …), laid out) describes
+inline rtgr_ray_outputs ray_outputs_at(char* base, const std::vector<RayArray>& arrs, const rtgr_ray_outputs* out) {
+    rtgr_ray_outputs o;
+    std::memset(&o, 0, sizeof o);
+    size_t k = 1;
+    if (out)
+        for (const RayOutputField& f : RAY_OUTPUT_FIELDS)
+            if (ray_output(*out, f)) { void* p = base + arrs[k++].off; std::memcpy((char*)&o + f.pos, &p, sizeof p); }
+    return o;
+}
+inline int check_redshift_outputs(const rtgr_ray_outputs* out) {
+    if (out && out->redshift && (!out->state_end || !(out->hit || out->hit32)))
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_ray_outputs.redshift needs state_end and hit (or hit32) in the same call");
+    return RTGR_OK;
+}
+// the counters of one device's share into those of the call: sums, except [7], a maximum (diagnostics)
+inline void merge_counters(rtgr_counters& into, const rtgr_counters& part) {
+    const uint64_t* p = (const uint64_t*)&part;
+    uint64_t* q = (uint64_t*)&into;
+    for (int w = 0; w < 8; w++) q[w] = (w == 7) ? (q[w] > p[w] ? q[w] : p[w]) : q[w] + p[w];
+}
+
 // ---- run-time units (rtgr_units.hip) ---------------------------------------------------------------------------------------------
 int unload_locked(rtgr_context* c, uint64_t id);   // drop unit `id` (0: all) from every device; the caller holds c->modules_mu
 // The scene check nobody has to remember: called by trace_device ahead of every enqueue, answers from the device's
@@ -165,7 +217,8 @@ template <class R>
 int auto_scene_check(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const R* d_state0, const rtgr_camera* cam,
                      uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, uint64_t jstride, uint64_t nrows_strided, hipStream_t st);
 
-// ---- the entry points of include/rtgr.h, by the name behind the rtgr_ prefix (rtgr_abi.hip holds the extern "C" shims) ----------
+// ---- the entry points of include/rtgr.h, by the name behind the rtgr_ prefix (rtgr_abi.hip holds the extern "C" shims); an
+// _f64 / _f32 pair is one template over the scalar type -------------------------------------------------------------------------
 namespace api {
 int create(const int* device_ids, int n_devices, rtgr_context** ctx_out);
 int destroy(rtgr_context* ctx);
@@ -184,34 +237,20 @@ int timing_enable(rtgr_context* ctx, int index, int on);
 int timing_read(rtgr_context* ctx, int index, double ms[4], uint64_t launches[4]);
 int timing_read_exchange(rtgr_context* ctx, int index, double ms[2], uint64_t launches[2]);
 int peer_access(rtgr_context* ctx, int index, char* why, uint64_t why_len);
-int trace_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double* d_state0, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, double* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream);
-int trace_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float* d_state0, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, float* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream);
-int trace_rows_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t jstride, uint64_t nrows, double* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream);
-int trace_rows_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t jstride, uint64_t nrows, float* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream);
-int trace_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double* state0, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, double* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
-int trace_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float* state0, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, float* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
-int trace_pixels_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double* pixels_in, uint64_t ni, uint64_t nj, double* pixels_out, rtgr_counters* ctr);
-int trace_pixels_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float* pixels_in, uint64_t ni, uint64_t nj, float* pixels_out, rtgr_counters* ctr);
-int trace_frames_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const rtgr_camera* cams, const double* const* state0s, uint64_t ni, uint64_t nj, double* const* rgb, const rtgr_ray_outputs* outs, rtgr_counters* ctrs);
-int trace_frames_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const rtgr_camera* cams, const float* const* state0s, uint64_t ni, uint64_t nj, float* const* rgb, const rtgr_ray_outputs* outs, rtgr_counters* ctrs);
-int trace_frames_pixels_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const double* const* pixels_in, uint64_t ni, uint64_t nj, double* const* pixels_out, rtgr_counters* ctrs);
-int trace_frames_pixels_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const float* const* pixels_in, uint64_t ni, uint64_t nj, float* const* pixels_out, rtgr_counters* ctrs);
-int trace_one_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double pos[4], const double normal[4], double rgb[3], double state_end[8], uint8_t* status);
-int trace_one_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float pos[4], const float normal[4], float rgb[3], float state_end[8], uint8_t* status);
-int trace_sharded_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, double* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
-int trace_sharded_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, double* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
-int trace_sharded_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, float* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
-int trace_sharded_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, float* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
-int make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, double* d_state0, void* stream);
-int make_canvas_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, double* state0);
-int make_canvas_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, float* d_state0, void* stream);
-int make_canvas_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, float* state0);
-int eval_metric_f64(rtgr_context* ctx, const rtgr_scene* scene, const double* x , uint64_t n, double* g, double* dg, double* Gam);
-int eval_metric_f32(rtgr_context* ctx, const rtgr_scene* scene, const float* x , uint64_t n, float* g, float* dg, float* Gam);
-int eval_geodesic_f64(rtgr_context* ctx, const rtgr_scene* scene, const double* s , uint64_t n, int path, double* ds);
-int eval_geodesic_f32(rtgr_context* ctx, const rtgr_scene* scene, const float* s , uint64_t n, int path, float* ds);
-int eval_objects_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const double* x , uint64_t n, double* d, double* dmin, uint8_t* hit, double* rgb);
-int eval_objects_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const float* x , uint64_t n, float* d, float* dmin, uint8_t* hit, float* rgb);
+template <class R> int trace_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R* d_state0, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream);
+template <class R> int trace_rows_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t jstride, uint64_t nrows, R* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* d_counters, void* stream);
+template <class R> int trace(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R* state0, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
+template <class R> int trace_pixels(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R* pixels_in, uint64_t ni, uint64_t nj, R* pixels_out, rtgr_counters* ctr);
+template <class R> int trace_frames(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const rtgr_camera* cams, const R* const* state0s, uint64_t ni, uint64_t nj, R* const* rgb, const rtgr_ray_outputs* outs, rtgr_counters* ctrs);
+template <class R> int trace_frames_pixels(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, uint32_t nframes, const R* const* pixels_in, uint64_t ni, uint64_t nj, R* const* pixels_out, rtgr_counters* ctrs);
+template <class R> int trace_one(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R pos[4], const R normal[4], R rgb[3], R state_end[8], uint8_t* status);
+template <class R> int trace_sharded(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, R* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
+template <class R> int trace_sharded_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, R* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
+template <class R> int make_canvas_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* d_state0, void* stream);
+template <class R> int make_canvas(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* state0);
+template <class R> int eval_metric(rtgr_context* ctx, const rtgr_scene* scene, const R* x, uint64_t n, R* g, R* dg, R* Gam);
+template <class R> int eval_geodesic(rtgr_context* ctx, const rtgr_scene* scene, const R* s, uint64_t n, int path, R* ds);
+template <class R> int eval_objects(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R* x, uint64_t n, R* d, R* dmin, uint8_t* hit, R* rgb);
 int eval_fastmath_f64(rtgr_context* ctx, const double* x, uint64_t n, double* rcp, double* rsq);
 int user_metric_load(rtgr_context* ctx, const char* code_object_path, uint64_t* id_out);
 int user_metric_compile(rtgr_context* ctx, const char* source, int stationary, uint64_t* id_out);

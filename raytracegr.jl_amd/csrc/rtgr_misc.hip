@@ -141,50 +141,53 @@ __global__ __launch_bounds__(256) void redshift_kernel(DevScene<R> sc, DevCamera
         if (e_ != hipSuccess) return fail(RTGR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
     } while (0)
 
-int misc_canvas_f64(const DevScene<double>& sc, const DevCamera<double>& cam, uint64_t ni, uint64_t nj, uint64_t j0,
-                    uint64_t n, double* d_state0, hipStream_t st) {
-    hipLaunchKernelGGL(canvas_kernel<double>, dim3(nblk(n)), dim3(256), 0, st, sc, cam, ni, nj, j0, (uint64_t)1, (uint64_t)0, n, d_state0);
+template <class R>
+int misc_canvas(const DevScene<R>& sc, const DevCamera<R>& cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t n, R* d_state0, hipStream_t st) {
+    hipLaunchKernelGGL(canvas_kernel<R>, dim3(nblk(n)), dim3(256), 0, st, sc, cam, ni, nj, j0, (uint64_t)1, (uint64_t)0, n, d_state0);
     CHECK_LAUNCH();
     return RTGR_OK;
 }
-int misc_canvas_f32(const DevScene<float>& sc, const DevCamera<float>& cam, uint64_t ni, uint64_t nj, uint64_t j0,
-                    uint64_t n, float* d_state0, hipStream_t st) {
-    hipLaunchKernelGGL(canvas_kernel<float>, dim3(nblk(n)), dim3(256), 0, st, sc, cam, ni, nj, j0, (uint64_t)1, (uint64_t)0, n, d_state0);
+template <class R>
+int misc_eval_metric(const DevScene<R>& sc, const R* d_x, uint64_t n, R* g, R* dg, R* Gam, hipStream_t st) {
+    hipLaunchKernelGGL(eval_metric_kernel<R>, dim3(nblk(n)), dim3(256), 0, st, sc, d_x, n, g, dg, Gam);
     CHECK_LAUNCH();
     return RTGR_OK;
 }
-int misc_eval_metric_f64(const DevScene<double>& sc, const double* d_x, uint64_t n, double* g, double* dg, double* Gam, hipStream_t st) {
-    hipLaunchKernelGGL(eval_metric_kernel<double>, dim3(nblk(n)), dim3(256), 0, st, sc, d_x, n, g, dg, Gam);
+template <class R>
+int misc_eval_objects(const DevScene<R>& sc, const DevSolver<R>& opt, const R* d_x, uint64_t n, R* d, R* dmin, uint8_t* hit, R* rgb, hipStream_t st) {
+    hipLaunchKernelGGL(eval_objects_kernel<R>, dim3(nblk(n)), dim3(256), 0, st, sc, opt, d_x, n, d, dmin, hit, rgb);
     CHECK_LAUNCH();
     return RTGR_OK;
 }
-int misc_eval_metric_f32(const DevScene<float>& sc, const float* d_x, uint64_t n, float* g, float* dg, float* Gam, hipStream_t st) {
-    hipLaunchKernelGGL(eval_metric_kernel<float>, dim3(nblk(n)), dim3(256), 0, st, sc, d_x, n, g, dg, Gam);
+template <class R>
+int misc_eval_geodesic(const DevScene<R>& sc, const R* d_s, uint64_t n, int path, R* d_ds, hipStream_t st) {
+    hipLaunchKernelGGL(eval_geodesic_kernel<R>, dim3(nblk(n)), dim3(256), 0, st, sc, d_s, n, path, d_ds);
     CHECK_LAUNCH();
     return RTGR_OK;
 }
-int misc_eval_objects_f64(const DevScene<double>& sc, const DevSolver<double>& opt, const double* d_x, uint64_t n, double* d, double* dmin, uint8_t* hit,
-                          double* rgb, hipStream_t st) {
-    hipLaunchKernelGGL(eval_objects_kernel<double>, dim3(nblk(n)), dim3(256), 0, st, sc, opt, d_x, n, d, dmin, hit, rgb);
+template <class T>
+int misc_place_rows(const T* d_part, uint64_t ni, uint64_t nj, uint64_t rank, uint64_t nranks, uint64_t planes, uint64_t elem, T* d_full, hipStream_t st) {
+    const uint64_t nrows = (nj - rank + nranks - 1) / nranks;
+    hipLaunchKernelGGL(place_rows_kernel<T>, dim3(nblk(ni * nrows * planes * elem)), dim3(256), 0, st, d_part, ni, nj, rank, nranks, planes, elem, d_full);
     CHECK_LAUNCH();
     return RTGR_OK;
 }
-int misc_eval_objects_f32(const DevScene<float>& sc, const DevSolver<float>& opt, const float* d_x, uint64_t n, float* d, float* dmin, uint8_t* hit,
-                          float* rgb, hipStream_t st) {
-    hipLaunchKernelGGL(eval_objects_kernel<float>, dim3(nblk(n)), dim3(256), 0, st, sc, opt, d_x, n, d, dmin, hit, rgb);
+template <class R>
+int misc_redshift(const DevScene<R>& sc, const DevCamera<R>& cam, const R* d_state0, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t jstride,
+                  uint64_t n, uint64_t out_offset, const R* d_state_end, const uint8_t* d_hit, const uint32_t* d_hit32, R* d_red, hipStream_t st) {
+    hipLaunchKernelGGL(redshift_kernel<R>, dim3(nblk(n)), dim3(256), 0, st, sc, cam, d_state0, ni, nj, j0, jstride, n, out_offset,
+                       d_state_end, d_hit, d_hit32, d_red);
     CHECK_LAUNCH();
     return RTGR_OK;
 }
-int misc_eval_geodesic_f64(const DevScene<double>& sc, const double* d_s, uint64_t n, int path, double* d_ds, hipStream_t st) {
-    hipLaunchKernelGGL(eval_geodesic_kernel<double>, dim3(nblk(n)), dim3(256), 0, st, sc, d_s, n, path, d_ds);
-    CHECK_LAUNCH();
-    return RTGR_OK;
-}
-int misc_eval_geodesic_f32(const DevScene<float>& sc, const float* d_s, uint64_t n, int path, float* d_ds, hipStream_t st) {
-    hipLaunchKernelGGL(eval_geodesic_kernel<float>, dim3(nblk(n)), dim3(256), 0, st, sc, d_s, n, path, d_ds);
-    CHECK_LAUNCH();
-    return RTGR_OK;
-}
+RTGR_INSTANTIATE_F64_F32(misc_canvas);
+RTGR_INSTANTIATE_F64_F32(misc_eval_metric);
+RTGR_INSTANTIATE_F64_F32(misc_eval_objects);
+RTGR_INSTANTIATE_F64_F32(misc_eval_geodesic);
+RTGR_INSTANTIATE_F64_F32(misc_place_rows);
+template decltype(misc_place_rows<uint8_t>) misc_place_rows<uint8_t>;
+RTGR_INSTANTIATE_F64_F32(misc_redshift);
+
 int misc_eval_fastmath_f64(const double* d_x, uint64_t n, double* d_rcp, double* d_rsq, hipStream_t st) {
     hipLaunchKernelGGL(eval_fastmath_kernel, dim3(nblk(n)), dim3(256), 0, st, d_x, n, d_rcp, d_rsq);
     CHECK_LAUNCH();
@@ -192,50 +195,6 @@ int misc_eval_fastmath_f64(const double* d_x, uint64_t n, double* d_rcp, double*
 }
 int misc_quantize(const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, hipStream_t st) {
     hipLaunchKernelGGL(quantize_kernel, dim3(nblk(ni * nj)), dim3(256), 0, st, d_rgb, ni, nj, d_img);
-    CHECK_LAUNCH();
-    return RTGR_OK;
-}
-int misc_place_rows_f64(const double* d_part, uint64_t ni, uint64_t nj, uint64_t rank, uint64_t nranks, uint64_t planes,
-                        double* d_full, hipStream_t st) {
-    const uint64_t nrows = (nj - rank + nranks - 1) / nranks;
-    hipLaunchKernelGGL(place_rows_kernel<double>, dim3(nblk(ni * nrows * planes)), dim3(256), 0, st, d_part, ni, nj, rank, nranks,
-                       planes, (uint64_t)1, d_full);
-    CHECK_LAUNCH();
-    return RTGR_OK;
-}
-int misc_place_rows_f32(const float* d_part, uint64_t ni, uint64_t nj, uint64_t rank, uint64_t nranks, uint64_t planes,
-                        float* d_full, hipStream_t st) {
-    const uint64_t nrows = (nj - rank + nranks - 1) / nranks;
-    hipLaunchKernelGGL(place_rows_kernel<float>, dim3(nblk(ni * nrows * planes)), dim3(256), 0, st, d_part, ni, nj, rank, nranks,
-                       planes, (uint64_t)1, d_full);
-    CHECK_LAUNCH();
-    return RTGR_OK;
-}
-int misc_place_rows_u8(const uint8_t* d_part, uint64_t ni, uint64_t nj, uint64_t rank, uint64_t nranks, uint64_t elem,
-                       uint8_t* d_full, hipStream_t st) {
-    const uint64_t nrows = (nj - rank + nranks - 1) / nranks;
-    hipLaunchKernelGGL(place_rows_kernel<uint8_t>, dim3(nblk(ni * nrows * elem)), dim3(256), 0, st, d_part, ni, nj, rank, nranks,
-                       (uint64_t)1, elem, d_full);
-    CHECK_LAUNCH();
-    return RTGR_OK;
-}
-
-}  // namespace rtgr
-
-namespace rtgr {
-int misc_redshift_f64(const DevScene<double>& sc, const DevCamera<double>& cam, const double* d_state0, uint64_t ni, uint64_t nj,
-                      uint64_t j0, uint64_t jstride, uint64_t n, uint64_t out_offset, const double* d_state_end,
-                      const uint8_t* d_hit, const uint32_t* d_hit32, double* d_red, hipStream_t st) {
-    hipLaunchKernelGGL(redshift_kernel<double>, dim3(nblk(n)), dim3(256), 0, st, sc, cam, d_state0, ni, nj, j0, jstride, n, out_offset,
-                       d_state_end, d_hit, d_hit32, d_red);
-    CHECK_LAUNCH();
-    return RTGR_OK;
-}
-int misc_redshift_f32(const DevScene<float>& sc, const DevCamera<float>& cam, const float* d_state0, uint64_t ni, uint64_t nj,
-                      uint64_t j0, uint64_t jstride, uint64_t n, uint64_t out_offset, const float* d_state_end,
-                      const uint8_t* d_hit, const uint32_t* d_hit32, float* d_red, hipStream_t st) {
-    hipLaunchKernelGGL(redshift_kernel<float>, dim3(nblk(n)), dim3(256), 0, st, sc, cam, d_state0, ni, nj, j0, jstride, n, out_offset,
-                       d_state_end, d_hit, d_hit32, d_red);
     CHECK_LAUNCH();
     return RTGR_OK;
 }

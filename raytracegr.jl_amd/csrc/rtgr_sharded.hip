@@ -9,36 +9,22 @@ namespace rtgr {
 // per-device scratch of the sharded path lives in the device's Staging: d_out = this rank's rows (all requested arrays),
 // d_small = counters; device 0 additionally d_recv = the peers' rows as they arrive.
 template <class R>
-static int trace_sharded(rtgr_context* c, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
-                         uint64_t nj, R* d_rgb0, const rtgr_ray_outputs* out0, rtgr_counters* ctr) {
+static int trace_sharded_gather(rtgr_context* c, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                                uint64_t nj, R* d_rgb0, const rtgr_ray_outputs* out0, rtgr_counters* ctr) {
     const uint64_t N = c->devs.size();
     if (!scene || !opt || !cam) return fail(RTGR_ERR_BAD_ARG, "NULL argument");
     if (ni == 0 || nj == 0) return fail(RTGR_ERR_BAD_ARG, "empty canvas");
     if (c->devs[0]->knobs.tile) return fail(RTGR_ERR_BAD_ARG, "the multi-device path needs the persistent pipeline (option tile = 0)");
-    if (out0 && out0->redshift && (!out0->state_end || !(out0->hit || out0->hit32)))
-        return fail(RTGR_ERR_BAD_ARG, "rtgr_ray_outputs.redshift needs state_end and hit (or hit32) in the same call");
-    struct Arr { size_t elem; int planes; void* full; size_t off; };  // one per requested array
-    std::vector<Arr> arrs;
-    arrs.push_back({sizeof(R), 3, d_rgb0, 0});
-    if (out0) {
-        if (out0->state_end) arrs.push_back({8 * sizeof(R), 1, out0->state_end, 0});
-        if (out0->lambda_end) arrs.push_back({sizeof(R), 1, out0->lambda_end, 0});
-        if (out0->status) arrs.push_back({1, 1, out0->status, 0});
-        if (out0->hit) arrs.push_back({1, 1, out0->hit, 0});
-        if (out0->n_accept) arrs.push_back({4, 1, out0->n_accept, 0});
-        if (out0->n_reject) arrs.push_back({4, 1, out0->n_reject, 0});
-        if (out0->redshift) arrs.push_back({sizeof(R), 1, out0->redshift, 0});
-        if (out0->hit32) arrs.push_back({4, 1, out0->hit32, 0});
-    }
+    int rc;
+    if ((rc = check_redshift_outputs(out0))) return rc;
+    std::vector<RayArray> arrs = ray_arrays(d_rgb0, out0, sizeof(R));   // one per requested array; ptr: the full frame's on device 0
     const uint64_t nrows_max = (nj + N - 1) / N, nmax = ni * nrows_max;
-    size_t part_bytes = 0;
-    for (auto& a : arrs) { a.off = part_bytes; part_bytes += align256((size_t)nmax * a.elem * a.planes); }
+    const size_t part_bytes = ray_arrays_layout(arrs, nmax);
     std::vector<Staging*> S(N, nullptr);
     std::vector<uint64_t> nrows(N, 0);
     std::vector<hipEvent_t> ev(N, nullptr);
     std::vector<char> via_host(N, 0);
     struct EvFree { std::vector<hipEvent_t>& e; ~EvFree() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } evfree{ev};
-    int rc;
     // the part / counter / receive buffers are shared by consecutive sharded calls: one such call at a time per context
     // (lock order: device 0's staging mutex first)
     std::vector<std::unique_lock<std::mutex>> locks;
@@ -93,19 +79,7 @@ static int trace_sharded(rtgr_context* c, const rtgr_scene* scene, const rtgr_so
         DeviceGuard g(D.dev);
         char* pb = (char*)S[k]->d_out.p;
         HIP_TRY(hipMemsetAsync(S[k]->d_small.p, 0, 256, S[k]->s_comp));
-        rtgr_ray_outputs po;
-        std::memset(&po, 0, sizeof po);
-        size_t q = 1;
-        if (out0) {
-            if (out0->state_end) po.state_end = pb + arrs[q++].off;
-            if (out0->lambda_end) po.lambda_end = pb + arrs[q++].off;
-            if (out0->status) po.status = (uint8_t*)(pb + arrs[q++].off);
-            if (out0->hit) po.hit = (uint8_t*)(pb + arrs[q++].off);
-            if (out0->n_accept) po.n_accept = (uint32_t*)(pb + arrs[q++].off);
-            if (out0->n_reject) po.n_reject = (uint32_t*)(pb + arrs[q++].off);
-            if (out0->redshift) po.redshift = pb + arrs[q++].off;
-            if (out0->hit32) po.hit32 = (uint32_t*)(pb + arrs[q++].off);
-        }
+        const rtgr_ray_outputs po = ray_outputs_at(pb, arrs, out0);
         rc = trace_device<R>(D, scene, opt, nullptr, cam, ni, nj, k, k + 1, (R*)pb, &po, (rtgr_counters*)S[k]->d_small.p,
                                   S[k]->s_comp, N, nrows[k]);
         if (rc) return rc;
@@ -157,9 +131,8 @@ static int trace_sharded(rtgr_context* c, const rtgr_scene* scene, const rtgr_so
             const char* src = k == 0 ? (const char*)S[0]->d_out.p : (const char*)S[0]->d_recv.p + (k - 1) * part_bytes;
             for (auto& a : arrs) {
                 if (a.planes == 3) {  // rgb: the part's planes are ni*nrows[k] apart
-                    if constexpr (sizeof(R) == 8) { if ((rc = misc_place_rows_f64((const double*)(src + a.off), ni, nj, k, N, 3, (double*)a.full, s0))) return rc; }
-                    else if ((rc = misc_place_rows_f32((const float*)(src + a.off), ni, nj, k, N, 3, (float*)a.full, s0))) return rc;
-                } else if ((rc = misc_place_rows_u8((const uint8_t*)(src + a.off), ni, nj, k, N, a.elem, (uint8_t*)a.full, s0))) return rc;
+                    if ((rc = misc_place_rows<R>((const R*)(src + a.off), ni, nj, k, N, 3, 1, (R*)a.ptr, s0))) return rc;
+                } else if ((rc = misc_place_rows<uint8_t>((const uint8_t*)(src + a.off), ni, nj, k, N, 1, a.elem, (uint8_t*)a.ptr, s0))) return rc;
             }
         }
         HIP_TRY(hipStreamSynchronize(s0));
@@ -170,9 +143,7 @@ static int trace_sharded(rtgr_context* c, const rtgr_scene* scene, const rtgr_so
         if (nrows[k] == 0) continue;
         DeviceGuard g(c->devs[k]->dev);
         HIP_TRY(hipStreamSynchronize(S[k]->s_comp));
-        const uint64_t* p = (const uint64_t*)S[k]->pin_small.p;
-        uint64_t* q = (uint64_t*)&sum;
-        for (int w = 0; w < 8; w++) q[w] = (w == 7) ? (q[w] > p[w] ? q[w] : p[w]) : q[w] + p[w];   // [7] is a maximum (diagnostics)
+        merge_counters(sum, *(const rtgr_counters*)S[k]->pin_small.p);
     }
     if (ctr) *ctr = sum;
     drain.armed = false;   // every stream used above has been synchronised
@@ -182,35 +153,21 @@ static int trace_sharded(rtgr_context* c, const rtgr_scene* scene, const rtgr_so
 // Host destination: no gather on device 0 is needed — every device downloads its own rows straight into the caller's
 // arrays (trace_host_all_devices), which is what rtgr_trace_f64 does on a multi-device context.
 template <class R>
-static int trace_sharded_host(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
-                              uint64_t nj, R* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr) {
+int api::trace_sharded(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                       R* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr) {
     if (!cam) return fail(RTGR_ERR_BAD_ARG, "camera is NULL");
-    return trace_host<R>(ctx, scene, opt, nullptr, cam, ni, nj, 0, nj, rgb, out, ctr);
+    return trace<R>(ctx, scene, opt, nullptr, cam, ni, nj, 0, nj, rgb, out, ctr);
 }
 template <class R>
-static int trace_sharded_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
-                                uint64_t nj, R* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr) {
+int api::trace_sharded_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                              uint64_t nj, R* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
     if (!d_rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
-    return trace_sharded<R>(c, scene, opt, cam, ni, nj, d_rgb, out, ctr);
+    return trace_sharded_gather<R>(c, scene, opt, cam, ni, nj, d_rgb, out, ctr);
 }
-int api::trace_sharded_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam,
-                                  uint64_t ni, uint64_t nj, double* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr) {
-    return trace_sharded_device<double>(ctx, scene, opt, cam, ni, nj, d_rgb, out, ctr);
-}
-int api::trace_sharded_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam,
-                                  uint64_t ni, uint64_t nj, float* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr) {
-    return trace_sharded_device<float>(ctx, scene, opt, cam, ni, nj, d_rgb, out, ctr);
-}
-int api::trace_sharded_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam,
-                           uint64_t ni, uint64_t nj, double* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr) {
-    return trace_sharded_host<double>(ctx, scene, opt, cam, ni, nj, rgb, out, ctr);
-}
-int api::trace_sharded_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam,
-                           uint64_t ni, uint64_t nj, float* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr) {
-    return trace_sharded_host<float>(ctx, scene, opt, cam, ni, nj, rgb, out, ctr);
-}
+RTGR_INSTANTIATE_F64_F32(api::trace_sharded);
+RTGR_INSTANTIATE_F64_F32(api::trace_sharded_device);
 
 }  // namespace rtgr
