@@ -11,6 +11,8 @@
                                             #   ellipsoid given as device source, UserObjects — where the small sphere was)
     python examples/render.py 6             # writes scenes/sphere6.png (objects of TWO separately written sources in one scene:
                                             #   that torus and ellipsoid, and the reference's Sphere written as device source)
+    python examples/render.py 2 400 400 --aa 4   # the same frame anti-aliased: 4 x 4 sub-rays for the pixels on an edge (rt.trace_aa;
+                                            #   scenes/sphere2_aa4.png; not with the run-time metrics of 3 and 4)
 
 The code below is what a user of RayTraceGR.jl writes, with `RayTraceGR.` replaced by the host mirror `rt.`.
 """
@@ -24,9 +26,14 @@ rt = load_package()
 
 
 def main():
-    which = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    ni = int(sys.argv[2]) if len(sys.argv) > 2 else 200
-    nj = int(sys.argv[3]) if len(sys.argv) > 3 else ni
+    argv, aa = list(sys.argv), 0
+    if "--aa" in argv:   # adaptive anti-aliasing: K x K sub-rays for the pixels on an edge
+        at = argv.index("--aa")
+        aa = int(argv[at + 1])
+        del argv[at:at + 2]
+    which = int(argv[1]) if len(argv) > 1 else 2
+    ni = int(argv[2]) if len(argv) > 2 else 200
+    nj = int(argv[3]) if len(argv) > 3 else ni
     metric = rt.minkowski if which == 1 else rt.kerr_schild
     if which in (3, 4):  # a metric function of the user's own (the reference: any Julia callable, src/RayTraceGR.jl:302-309)
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -52,9 +59,19 @@ def main():
     pos = (0, 0 if which == 1 else 4, -2, 0)
     if which in (5, 6):   # the sources bring a reach bound (it lets the FAR pass skip scans): once per scene, hold it against the single FULL pass
         rt.check_scene(metric, objs, dict(pos=pos, widthx=(0, 1, 0, 0), widthy=(0, 0, 0, 1), normal=(0, 0, 1, 0)))
+    from raytracegr_jl_amd.png import write_png
+    if aa:   # (an extension: the reference traces one ray per pixel)
+        import numpy as np
+        res = rt.trace_aa(metric, objs, dict(pos=pos, widthx=(0, 1, 0, 0), widthy=(0, 0, 0, 1), normal=(0, 0, 1, 0)), ni, nj, k=aa)
+        img = np.rint(np.clip(res["rgb"].reshape(3, nj, ni), 0.0, 1.0) * 255.0).astype(np.uint8)
+        os.makedirs(rt.api.outdir, exist_ok=True)
+        file = os.path.join(rt.api.outdir, f"sphere{'' if which == 1 else which}_aa{aa}.png")
+        write_png(file, np.ascontiguousarray(np.transpose(img, (1, 2, 0))))
+        st = res["stats"]
+        print(f'Output file is "{file}"  ({st["refined"]} of {st["pixels"]} pixels refined, {res["counters"]["rays"]} rays)')
+        return
     canvas = rt.make_canvas(metric, pos, (0, 1, 0, 0), (0, 0, 0, 1), (0, 0, 1, 0), ni, nj)
     canvas, info = rt.trace_rays(metric, objs, canvas, return_info=True)
-    from raytracegr_jl_amd.png import write_png
     os.makedirs(rt.api.outdir, exist_ok=True)
     file = os.path.join(rt.api.outdir, {1: "sphere.png", 2: "sphere2.png", 3: "sphere3.png", 4: "sphere4.png", 5: "sphere5.png", 6: "sphere6.png"}[which])
     write_png(file, canvas.image_u8())

@@ -374,6 +374,65 @@ int rtgr_trace_sharded_device_f32(rtgr_context* ctx, const rtgr_scene* scene, co
                                   const rtgr_camera* cam, uint64_t ni, uint64_t nj, float* d_rgb,
                                   const rtgr_ray_outputs* out, rtgr_counters* ctr);
 
+/* ---- adaptive anti-aliasing: supersample only the pixels on an edge ----------------------------------------------------
+ * AN EXTENSION: every other entry point delivers one ray through each pixel centre, and the reference's colour rule is discontinuous
+ * (a 24-band sawtooth in theta and phi, src/RayTraceGR.jl:427; an integer object index; a hard miss colour): staircase silhouettes,
+ * moire towards the photon ring.  These calls trace the plain frame, find the pixels that need more rays and trace only those again:
+ *   Pass 1     the plain camera frame of the whole ni x nj canvas into d_rgb, exactly as rtgr_trace_device_* does with `cam`, j0 = 0,
+ *              j1 = nj.  `out` describes that pixel-centre ray and is never changed by the refinement.
+ *   Edge rule  pixel p is refined if an in-frame 4-neighbour q (i +- 1 or j +- 1) has hit32(q) != hit32(p), or status(q) != status(p), or
+ *              max_c |rgb_c(p) - rgb_c(q)| > aa->contrast — the difference and the comparison in the entry point's scalar type,
+ *              `contrast` rounded to it; a NaN difference is not an edge.  Symmetric: both pixels of a differing pair are refined.
+ *              contrast < 0: EVERY pixel is refined (uniform supersampling); +Inf: class edges (hit / status) only.
+ *              d_refined (optional, ni*nj bytes): 1 where the pixel was refined, else 0.
+ *   Pass 2     sub-ray (s, t), s, t in [0, k), of a refined pixel (i, j) is the camera ray of pixel (k i + s, k j + t) of the
+ *              (k ni) x (k nj) canvas of the same camera, so the k x k block is exactly the block of the k-times finer plain frame.
+ *              The sub-rays go through the same trace as caller-supplied ray states, aa->max_batch_rays at a time.
+ *   Reduce     per channel, in the scalar type: 0, plus the sub-colours with t outer and s inner, then ONE division by k*k (no fused
+ *              operation, no reciprocal); the result overwrites the pixel in d_rgb.  Unrefined pixels keep pass 1's bits.
+ * So the frame equals where(refined, box filter of the plain (k ni) x (k nj) frame, plain ni x nj frame) bit for bit, whatever the
+ * batch size, and does not depend on the order in which the library lists the refined pixels.
+ *   ctr (host, optional) is OVERWRITTEN with the counters of both passes summed; stats (host, optional): the canvas' pixels, the
+ *   refined ones, the sub-rays traced (k*k per refined pixel) and the batches they were traced in.
+ *   Streams: the call reads the number of refined pixels back, so it SYNCHRONISES `stream` once between the passes (and once more at
+ * its end when `ctr` is asked for); everything else is enqueued on `stream`.  It is refused during stream capture (RTGR_ERR_BAD_ARG),
+ * like workspace growth.  The device entry runs on the device that owns d_rgb; its scratch — refined count and counters, the hit /
+ * status arrays `out` does not ask for, the index list (8 bytes per pixel), the sub-ray states and sub-colours of one batch (11 scalars
+ * per sub-ray) — lives with that stream's state, only grows, and is retired, not freed, until rtgr_trim, like the workspace.  Calls on
+ * different streams may run concurrently; two such calls on ONE stream from two host threads at once are not supported.
+ *   rtgr_trace_aa_f64 / _f32 (host pointers) run the same thing on device 0 of the context and copy out: dealing an anti-aliased
+ * frame over several devices is out of scope.
+ *   RTGR_ERR_BAD_ARG (with a message): k outside 2..8, flags != 0, a NaN contrast, a null cam, and a scene whose metric is RTGR_USER (its
+ * camera kernel lives in the run-time unit; user OBJECTS under a built-in metric are fine: only the camera needs the metric).
+ * In scope: the built-in metrics (closed and generic), 3-D and 4-D grids, every object kind, both scalar types.  Out of scope:
+ * recursive refinement, filters other than the box, jittered samples. */
+typedef struct rtgr_aa {
+    uint32_t k;              /* k x k sub-rays per refined pixel, 2..8                                                        */
+    uint32_t flags;          /* 0                                                                                             */
+    double contrast;         /* refine where max_c |rgb_c(p) - rgb_c(q)| > contrast for a 4-neighbour q;
+                                < 0: refine EVERY pixel (uniform supersampling); +Inf: class edges only; NaN: RTGR_ERR_BAD_ARG */
+    uint64_t max_batch_rays; /* sub-rays traced per batch at most; 0 = default (2^22); rounded down to whole pixels, at least
+                                one pixel                                                                                     */
+} rtgr_aa;                   /* 24 bytes: k 0, flags 4, contrast 8, max_batch_rays 16 */
+typedef struct rtgr_aa_stats {
+    uint64_t pixels;         /* ni * nj                                  */
+    uint64_t refined;        /* pixels the edge rule selected            */
+    uint64_t sub_rays;       /* k * k * refined                          */
+    uint64_t batches;        /* traces of pass 2 (0 when refined == 0)   */
+} rtgr_aa_stats;             /* 32 bytes */
+int rtgr_trace_aa_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                             uint64_t nj, const rtgr_aa* aa, double* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined,
+                             rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
+int rtgr_trace_aa_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                             uint64_t nj, const rtgr_aa* aa, float* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined,
+                             rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
+int rtgr_trace_aa_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                      const rtgr_aa* aa, double* rgb, const rtgr_ray_outputs* out, uint8_t* refined, rtgr_counters* ctr,
+                      rtgr_aa_stats* stats);
+int rtgr_trace_aa_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                      const rtgr_aa* aa, float* rgb, const rtgr_ray_outputs* out, uint8_t* refined, rtgr_counters* ctr,
+                      rtgr_aa_stats* stats);
+
 /* ---- camera: make_canvas (src/RayTraceGR.jl:457-478) on the device ------------------------------------------
  * Writes n x 8 ray states (pos, null past-directed 4-velocity) for rows [j0, j1).  Device / host variants. */
 int rtgr_make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni,

@@ -25,6 +25,8 @@
 #   RtgrRayOutputs   64   state_end 0, lambda_end 8, status 16, hit 24, n_accept 32, n_reject 40, redshift 48, hit32 56
 #   RtgrGrid         64   n 0, pad 12, origin 16, spacing 40
 #   RtgrGrid4        80   n 0, origin 16, spacing 48
+#   RtgrAA           24   k 0, flags 4, contrast 8, max_batch_rays 16
+#   RtgrAAStats      32   pixels 0, refined 8, sub_rays 16, batches 24
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64          (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -94,6 +96,15 @@ struct RtgrGrid4               # a time-dependent metric sampled on a uniform 4-
     n::NTuple{4,UInt32}         # samples along t, x, y, z; each >= 4
     origin::NTuple{4,Float64}   # (t, x, y, z) of sample (0, 0, 0, 0)
     spacing::NTuple{4,Float64}
+end
+struct RtgrAA                  # adaptive anti-aliasing (rtgr_trace_aa_f64 / _f32): k x k sub-rays for the pixels on an edge
+    k::UInt32                   # 2..8
+    flags::UInt32               # 0
+    contrast::Float64           # refine where a colour channel differs from a 4-neighbour's by more than this; < 0: every pixel; Inf: class edges only
+    max_batch_rays::UInt64      # sub-rays per batch at most; 0 = default
+end
+struct RtgrAAStats
+    pixels::UInt64; refined::UInt64; sub_rays::UInt64; batches::UInt64
 end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
@@ -658,6 +669,44 @@ function render(metric, objs, pos, widthx, widthy, normal, ni::Integer, nj::Inte
     planes = (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3])
     details || return planes
     planes, RayDetails{T}(det.state_end, det.lambda_end, det.status, det.hit, det.n_accept, det.n_reject, det.redshift, ctr[])
+end
+
+"""
+    trace_rays_aa(metric, objs, pos, widthx, widthy, normal, ni, nj; k = 4, contrast = 1 / 255, T = Float64, ctx = nothing)
+        -> ((R, G, B), refined, RtgrAAStats)
+
+ADAPTIVE ANTI-ALIASING (`rtgr_trace_aa_f64/_f32`) — an extension: the reference traces one ray through each pixel centre, and its
+colour rule is discontinuous (the 24-band sawtooth of `objcolor`, :427; the object index; the miss colour, :528).  This is `render`'s
+frame with the pixels that differ from a 4-neighbour — in the object hit, in the solver's status, or by more than `contrast` in a colour
+channel — traced again with `k x k` sub-rays (the pixels of the `k ni x k nj` canvas of the same camera) and box-filtered; every other
+pixel keeps `render`'s bits.  `contrast < 0`: every pixel (uniform supersampling); `Inf`: class edges only.  `refined[i, j]` is 1
+where the pixel was refined.  Runs on device 0 of `ctx`.
+"""
+function trace_rays_aa(metric, objs, pos, widthx, widthy, normal, ni::Integer, nj::Integer;
+                       k::Integer = 4, contrast::Real = 1 / 255, T::Type = Float64, ctx = nothing)
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("trace_rays_aa has no CPU counterpart in the reference: ", why)
+    opt = solver_of(T)
+    cam = camera_of(pos, widthx, widthy, normal)
+    aa = Ref(RtgrAA(UInt32(k), UInt32(0), Float64(contrast), UInt64(0)))
+    rgb = Array{T}(undef, ni, nj, 3)                # plane-major: rgb[:, :, c] is plane c
+    refined = Matrix{UInt8}(undef, ni, nj)
+    ctr = Ref{RtgrCounters}()
+    stats = Ref{RtgrAAStats}()
+    GC.@preserve rgb refined begin
+        if T === Float64
+            check(ccall((:rtgr_trace_aa_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrCamera}, UInt64, UInt64, Ptr{RtgrAA}, Ptr{Float64},
+                         Ptr{RtgrRayOutputs}, Ptr{UInt8}, Ptr{RtgrCounters}, Ptr{RtgrAAStats}),
+                        handle(ctx), scene, opt, cam, ni, nj, aa, pointer(rgb), C_NULL, pointer(refined), ctr, stats))
+        else
+            check(ccall((:rtgr_trace_aa_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrCamera}, UInt64, UInt64, Ptr{RtgrAA}, Ptr{Float32},
+                         Ptr{RtgrRayOutputs}, Ptr{UInt8}, Ptr{RtgrCounters}, Ptr{RtgrAAStats}),
+                        handle(ctx), scene, opt, cam, ni, nj, aa, pointer(rgb), C_NULL, pointer(refined), ctr, stats))
+        end
+    end
+    (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), refined, stats[]
 end
 
 """

@@ -81,6 +81,18 @@ class rtgr_grid4(C.Structure):
     _fields_ = [("n", C.c_uint32 * 4), ("origin", C.c_double * 4), ("spacing", C.c_double * 4)]   # axes t, x, y, z
 
 
+class rtgr_aa(C.Structure):
+    """adaptive anti-aliasing (rtgr_trace_aa_*): k x k sub-rays for the pixels on an edge"""
+    _fields_ = [("k", C.c_uint32), ("flags", C.c_uint32), ("contrast", C.c_double), ("max_batch_rays", C.c_uint64)]
+
+
+class rtgr_aa_stats(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("refined", C.c_uint64), ("sub_rays", C.c_uint64), ("batches", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -103,6 +115,7 @@ EXPORTS = [
     "rtgr_eval_objects_f64", "rtgr_eval_objects_f32", "rtgr_user_source_join",
     "rtgr_trace_frames_f64", "rtgr_trace_frames_f32", "rtgr_trace_frames_pixels_f64", "rtgr_trace_frames_pixels_f32",
     "rtgr_grid_metric_load", "rtgr_grid_metric_unload", "rtgr_grid4_metric_load",
+    "rtgr_trace_aa_device_f64", "rtgr_trace_aa_device_f32", "rtgr_trace_aa_f64", "rtgr_trace_aa_f32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -166,6 +179,12 @@ def _declare(lib):
     for suf in ("f64", "f32"):
         getattr(lib, f"rtgr_make_canvas_device_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_camera), u64, u64, u64, u64, vp, vp]
         getattr(lib, f"rtgr_make_canvas_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_camera), u64, u64, u64, u64, vp]
+        getattr(lib, f"rtgr_trace_aa_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_camera), u64, u64, P(rtgr_aa), vp, P(rtgr_ray_outputs), vp, P(rtgr_counters),
+            P(rtgr_aa_stats), vp]
+        getattr(lib, f"rtgr_trace_aa_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_camera), u64, u64, P(rtgr_aa), vp, P(rtgr_ray_outputs), vp, P(rtgr_counters),
+            P(rtgr_aa_stats)]
     lib.rtgr_eval_fastmath_f64.argtypes = [ctx, vp, u64, vp, vp]
     lib.rtgr_quantize_device_f64.argtypes = [ctx, vp, u64, u64, vp, vp]
     lib.rtgr_user_metric_load.argtypes = [ctx, C.c_char_p, P(u64)]

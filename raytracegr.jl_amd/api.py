@@ -425,6 +425,35 @@ def trace_frames(metric, objs, cams, ni, nj, opt=None, dtype=np.float64, ctx=Non
     return [dict(per[k], rgb=rgb[k], counters=ctrs[k].as_dict()) for k in range(K)]
 
 
+def trace_aa(metric, objs, cam, ni, nj, k=4, contrast=1.0 / 255.0, opt=None, dtype=np.float64, ctx=None, details=False, max_batch_rays=0):
+    """ADAPTIVE ANTI-ALIASING (rtgr_trace_aa_f64 / _f32) — an extension: the plain ni x nj frame of the camera, then k x k sub-rays for
+    the pixels that differ from a 4-neighbour in hit, status or by more than `contrast` in a colour channel, averaged (box filter)
+    back into the frame; every other pixel keeps the plain frame's bits.  contrast < 0: every pixel (uniform supersampling); math.inf:
+    class edges only.  cam: make_camera arguments (dict) or an rtgr_camera.  -> dict(rgb [3, ni*nj], refined [ni*nj] (1 = refined),
+    counters (both passes), stats (pixels, refined, sub_rays, batches); details: + the per-ray outputs of the PIXEL-CENTRE rays)."""
+    lib = _lib()
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    camera = cam if isinstance(cam, rtgr_camera) else make_camera(**cam)
+    n = ni * nj
+    aa = _abi.rtgr_aa(k=int(k), flags=0, contrast=float(contrast), max_batch_rays=int(max_batch_rays))
+    res = dict(rgb=np.zeros((3, n), dtype), refined=np.zeros(n, np.uint8))
+    outs = None
+    if details:
+        outs = rtgr_ray_outputs()
+        wide = sc.nobj > 255
+        res.update(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
+                   hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
+        for name in ("state_end", "lambda_end", "status", "hit", "n_accept", "n_reject"):
+            setattr(outs, "hit32" if (wide and name == "hit") else name, res[name].ctypes.data)
+    ctr, stats = rtgr_counters(), _abi.rtgr_aa_stats()
+    fn = lib.rtgr_trace_aa_f64 if dtype == np.float64 else lib.rtgr_trace_aa_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(camera), ni, nj, C.byref(aa), res["rgb"].ctypes.data, outs,
+                       res["refined"].ctypes.data, C.byref(ctr), C.byref(stats)))
+    res["counters"], res["stats"] = ctr.as_dict(), stats.as_dict()
+    return res
+
+
 def trace_ray(metric, objs, cb, p, opt=None, ctx=None):
     """Legacy single-pixel shape `trace_ray(metric, objs, cb, p)::Pixel` (test/runtests.jl:65-79).
     `cb` is accepted for signature parity and ignored: the callback is always
@@ -534,5 +563,5 @@ def example2(ni=200, nj=200, save=True, ctx=None):
 
 __all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
-           "trace_rays", "trace_ray", "trace_frames", "dmetric", "christoffel", "geodesic", "example1", "example2",
+           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

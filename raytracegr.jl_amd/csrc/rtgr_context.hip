@@ -153,6 +153,8 @@ void free_device_state(DeviceCtx& d, bool all) {
         if (all) {
             if (kv.second.ws) (void)hipFree(kv.second.ws);
             if (kv.second.queue) (void)hipFree(kv.second.queue);
+            if (kv.second.aa_frame) (void)hipFree(kv.second.aa_frame);
+            if (kv.second.aa_batch) (void)hipFree(kv.second.aa_batch);
         }
     }
     for (auto& g : d.retired_grids) { (void)hipFree(g.d64); (void)hipFree(g.d32); }   // unloaded grid metrics (idle device: see above)

@@ -162,6 +162,11 @@ struct StreamState {
     size_t ws_bytes = 0;
     unsigned long long* queue = nullptr;  // 8 work-queue heads; stream order makes one slot per stream enough
     std::vector<void*> retired;           // superseded workspaces: kept alive for graphs captured earlier
+    // scratch of rtgr_trace_aa_device_* on this stream (rtgr_aa_host.hip), grow-only and retired like the workspace: per FRAME the
+    // counters + the refined count, the hit / status arrays the caller did not ask for and the index list of the refined pixels; per
+    // BATCH the sub-ray states and the sub-colours
+    void* aa_frame = nullptr; size_t aa_frame_bytes = 0;
+    void* aa_batch = nullptr; size_t aa_batch_bytes = 0;
 };
 
 struct Staging;  // host entry points (rtgr_internal.hpp)
@@ -278,5 +283,17 @@ int misc_quantize(const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img,
 template <class T>
 int misc_place_rows(const T* d_part, uint64_t ni, uint64_t nj, uint64_t rank, uint64_t nranks, uint64_t planes, uint64_t elem, T* d_full, hipStream_t st);
 int misc_poison_registers(int n_cu, unsigned pattern, hipStream_t st);   // the load-time probe's scrubber (rtgr_misc.hip)
+// adaptive anti-aliasing (rtgr_aa.hip; include/rtgr.h "adaptive anti-aliasing"): the edge rule over a traced frame -> flag bytes (d_flag
+// may be null) and the list of flagged pixels (*d_count entries, in no particular order; the caller zeroes *d_count on the stream) …
+template <class R>
+int aa_flag(const R* d_rgb, const uint32_t* d_hit32, const uint8_t* d_status, uint64_t ni, uint64_t nj, R contrast, bool all, uint8_t* d_flag,
+            uint64_t* d_list, unsigned long long* d_count, hipStream_t st);
+// … the k x k sub-rays of the npix listed pixels (states of the k ni x k nj canvas; a pixel's sub-rays contiguous, t outer, s inner) …
+template <class R>
+int aa_subrays(const DevScene<R>& sc, const DevCamera<R>& cam, uint64_t ni, uint64_t nj, uint32_t k, const uint64_t* d_list, uint64_t npix,
+               R* d_state0, hipStream_t st);
+// … and their colours (3 planes of npix k²) averaged into the listed pixels of d_rgb (3 planes of n)
+template <class R>
+int aa_reduce(const R* d_sub, const uint64_t* d_list, uint64_t npix, uint32_t k, R* d_rgb, uint64_t n, hipStream_t st);
 
 }  // namespace rtgr

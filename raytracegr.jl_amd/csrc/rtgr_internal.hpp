@@ -6,6 +6,7 @@
 //   rtgr_sharded.hip        one call over every device of a context: cyclic rows, peer copies to device 0
 //   rtgr_hooks.hip          make_canvas and the parity hooks (rtgr_eval_*), image quantisation
 //   rtgr_units.hip          run-time compiled units: build, audit, load-time probe, load, scene check
+//   rtgr_aa_host.hip        adaptive anti-aliasing: the plain frame, the edge rule, a sparse second trace (kernels: rtgr_aa.hip)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -246,6 +247,8 @@ template <class R> int trace_frames_pixels(rtgr_context* ctx, const rtgr_scene* 
 template <class R> int trace_one(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const R pos[4], const R normal[4], R rgb[3], R state_end[8], uint8_t* status);
 template <class R> int trace_sharded(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, R* rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
 template <class R> int trace_sharded_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, R* d_rgb, const rtgr_ray_outputs* out, rtgr_counters* ctr);
+template <class R> int trace_aa_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
+template <class R> int trace_aa(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_aa* aa, R* rgb, const rtgr_ray_outputs* out, uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats);
 template <class R> int make_canvas_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* d_state0, void* stream);
 template <class R> int make_canvas(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* state0);
 template <class R> int eval_metric(rtgr_context* ctx, const rtgr_scene* scene, const R* x, uint64_t n, R* g, R* dg, R* Gam);
