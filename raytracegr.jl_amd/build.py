@@ -30,8 +30,8 @@ UNITS = ["tu_f64_ksref.hip", "tu_f64_kstrue.hip", "tu_f64_generic.hip", "tu_f64_
 # THE list of device headers (csrc/): what every kernel — the library's and a run-time unit's — is made of.  A new device header goes
 # here and into rtgr_units.hip header_hash_of (the C++ build route of a unit, which runs without Python; tests/test_build_checks.py
 # holds the two lists against each other and against the #include lines).
-DEVICE_HEADERS = ["rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_grid_interp.hpp", "rtgr_integrator.hpp", "rtgr_persistent.hpp",
-                  "rtgr_tsit5_tables.hpp"]
+DEVICE_HEADERS = ["rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_grid_interp.hpp", "rtgr_objects.hpp", "rtgr_camera.hpp", "rtgr_tile.hpp",
+                  "rtgr_integrate.hpp", "rtgr_prepare.hpp", "rtgr_resolve.hpp", "rtgr_tsit5_tables.hpp"]
 # … plus what only the library's own kernels include (bench.py keys its roofline profile on the hash of these)
 KERNEL_HEADERS = DEVICE_HEADERS + ["rtgr_packed_f32.hpp"]
 HEADERS = KERNEL_HEADERS + ["rtgr_host.hpp", "rtgr_internal.hpp", "rtgr_pipeline.hpp", "rtgr_isa_audit.hpp", "rtgr_isa_repair.hpp", "rtgr_unit_build.hpp"]

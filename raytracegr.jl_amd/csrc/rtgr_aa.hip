@@ -4,7 +4,7 @@
 //   aa_reduce_kernel<R>    the sub-rays' colours averaged into the listed pixels of the frame
 // All three are memory-bound and tiny next to the trace between them: one thread per pixel / sub-ray, 64-bit indices, nothing clever.
 #include "rtgr_host.hpp"
-#include "rtgr_integrator.hpp"
+#include "rtgr_camera.hpp"
 
 namespace rtgr {
 

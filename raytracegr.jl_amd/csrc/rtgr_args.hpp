@@ -1,5 +1,5 @@
 // rtgr_args.hpp — plain-old-data shared by host and device code: device-side scene / solver / camera, the argument
-// blocks of the pipeline's kernels and the layout of the per-ray records in the workspace.  No device code here, so the
+// blocks of the pipeline's kernels and the layout of the per-ray records in the workspace.  No kernel code here, so the
 // host-only translation units (rtgr_context.hip …) can include it without instantiating kernels.
 #pragma once
 #include <stdint.h>
@@ -19,7 +19,7 @@ struct DevObject {
 // The object list (src/RayTraceGR.jl:433-441: a Vector of any length).  The first RTGR_MAX_OBJECTS objects sit in the kernels' argument
 // block (scalar loads from the kernarg segment), the rest — rare — in a device table the context keeps per distinct list
 // (rtgr_context.hip: object_table); `more` is null when nobj <= RTGR_MAX_OBJECTS.  Kernels walk the list with for_each_object /
-// for_each_by_kind (rtgr_physics.hpp), never by index.
+// for_each_by_kind (rtgr_objects.hpp), never by index.
 // ORDER.  The caller's order matters to the colour rule only (first-smaller-wins and the scale omin / length(objs),
 // src/RayTraceGR.jl:520-530); the event condition is a minimum (:433-441) and the FAR pass's reach test a conjunction — neither
 // cares.  So the device list is REGROUPED by the host: the spheres first (nsph of them, in the caller's order), then everything else
@@ -181,6 +181,12 @@ enum IntegrateMode : int { MODE_FULL = 0, MODE_FAR = 1, MODE_NEAR = 2 };
 // scalars per ray made every other hand-over record straddle a line (HBM traffic 991 -> 1124 B per ray), one slot padded to 32 made
 // resolve fetch two full lines per ray (1089).
 constexpr int HAND_W = 16;  // x[4] u[4] k0[4] t dt ps lq
+template <class R>
+__host__ __device__ __forceinline__ void hand_store(R* hd, const R x[4], const R u[4], const R k0[4], R t, R dt, R ps, float lq) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) { hd[q] = x[q]; hd[4 + q] = u[q]; hd[8 + q] = k0[q]; }
+    hd[12] = t; hd[13] = dt; hd[14] = ps; hd[15] = (R)lq;
+}
 constexpr int REC_TAIL = REC_W - HAND_W;              // 8
 constexpr int REC_TAIL_STATE = REC_W_STATE - HAND_W;  // 28
 template <class P>

@@ -267,7 +267,7 @@ int device_of(rtgr_context* c, const void* d_ptr, DeviceCtx** out) {
 // argument conversion
 // ---------------------------------------------------------------------------------------------------------------------
 // The band of s whose correctly rounded square root (in R) EQUALS r: lo = min{s : sqrt(s) >= r}, hi = min{s : sqrt(s) > r}.
-// disk_sign_distance (rtgr_physics.hpp) reads sign(r − RN(sqrt(s))) off these two thresholds, exactly as the IEEE square root
+// disk_sign_distance (rtgr_objects.hpp) reads sign(r − RN(sqrt(s))) off these two thresholds, exactly as the IEEE square root
 // of obj_distance would give it.  A few nextafter steps around r² (the root maps 1–3 neighbouring s onto one value).
 template <class R>
 void disk_sqrt_band(R r, R& lo, R& hi) {

@@ -1,8 +1,8 @@
-// rtgr_persistent.hpp — the production trace pipeline:
+// rtgr_integrate.hpp — the integrate kernel of the production trace pipeline:
 //     prepare (camera ray, queue key, u̇(y0), initial dt) -> [order scan/scatter] -> integrate<FAR> -> integrate<NEAR>
 //     -> resolve                                                              (rtgr_pipeline.hpp: launch_trace)
 //
-// Why a pipeline instead of one loop per ray (the simple tile kernel, trace_kernel in rtgr_pipeline.hpp, keeps that shape):
+// Why a pipeline instead of one loop per ray (the simple tile kernel, trace_kernel in rtgr_tile.hpp, keeps that shape):
 //   * rays need 27…991 Tsit5 step attempts inside one image; a wave that owns 64 fixed rays idles until
 //     its longest ray ends, and each ray's end-of-life episode (bracketed root-find on the dense output, colouring,
 //     next ray's camera set-up) would run with one lane active;
@@ -29,14 +29,11 @@
 //     evaluated at the 8 interior sample points θ = j/9; distances are evaluated object-major so
 //     each object's parameters are fetched once per block of sample points.
 #pragma once
-#include "rtgr_integrator.hpp"
+#include "rtgr_objects.hpp"
 #include "rtgr_tsit5_tables.hpp"
 
 #ifndef RTGR_GHOST_LANES
 #define RTGR_GHOST_LANES 1  // lanes without a ray run the step's control block too (few-lane VALU instructions are 2.4 x dearer)
-#endif
-#ifndef RTGR_ROOT_SHORTCUT
-#define RTGR_ROOT_SHORTCUT 1
 #endif
 #ifndef RTGR_WAVES_PER_SIMD_GENERIC
 #define RTGR_WAVES_PER_SIMD_GENERIC 2  // generic dual-number RHS: ~270 registers wanted; 2 waves with a small spill beat 1 wave (measured 6.72 vs 6.22 Gstep/s)
@@ -99,85 +96,6 @@ template <class R, int METRIC, bool SPIN> constexpr bool ldsk_of(int mode) {
     return SPIN && mode == MODE_FAR && RTGR_LDSK_SPIN_FAR != 0;
 }
 
-// fast f32 helpers for the step-size machinery
-// (uniform_(), rtgr_physics.hpp: a wave-uniform value computed with vector instructions — there is no scalar f64 ALU —
-//  lives in a VGPR and, in a kernel squeezed to 127 registers, gets spilled to scratch and reloaded in the loop; through
-//  readfirstlane it lives in SGPRs.)
-// one-instruction f32 max / min / clamp (fmaxf / fminf spend a second v_max x, x on canonicalising each computed operand)
-RTGR_DEV float fmax1(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-RTGR_DEV float fmin1(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-RTGR_DEV float fclamp1(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }  // v_med3_f32
-RTGR_DEV float flog2(float x) { return __builtin_amdgcn_logf(x); }   // v_log_f32
-RTGR_DEV float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }  // v_exp_f32
-
-typedef float float2_t __attribute__((ext_vector_type(2)));
-
-// lanes below `lane` set in mask
-RTGR_DEV uint32_t mask_rank(unsigned long long mask, uint32_t lane) {
-    return (uint32_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
-}
-
-// … of a SPHERE (the leading objects of the regrouped list, DevScene: no dispatch on the kind)
-template <class R, int P>
-RTGR_DEV void fold_sphere(const DevObject<R>& o, const R (&pos)[P][4], R (&dmin)[P]) {
-    const R cx = o.p[1], cy = o.p[2], cz = o.p[3], Rr = o.p[8];
-    const R nR2 = -Rr * Rr;
-    if (Rr < R(0)) {                                                                   // :415-419, sign(R) * (|x − c|² − R²)
-#pragma unroll
-        for (int p = 0; p < P; p++) {
-            const R dx = pos[p][1] - cx, dy = pos[p][2] - cy, dz = pos[p][3] - cz;
-            dmin[p] = rmin(dmin[p], -rfma(dx, dx, rfma(dy, dy, rfma(dz, dz, nR2))));
-        }
-    } else {
-#pragma unroll
-        for (int p = 0; p < P; p++) {
-            const R dx = pos[p][1] - cx, dy = pos[p][2] - cy, dz = pos[p][3] - cz;
-            dmin[p] = rmin(dmin[p], rfma(dx, dx, rfma(dy, dy, rfma(dz, dz, nR2))));
-        }
-    }
-}
-
-// distances of one object at P sample positions folded into dmin[] (object-major: parameters fetched once)
-template <class R, int P>
-RTGR_DEV void fold_distances(const DevObject<R>& o, const R (&pos)[P][4], R (&dmin)[P]) {
-    if (o.kind == RTGR_PLANE) {                                                        // src/RayTraceGR.jl:399-401
-        const R tm = o.p[0];
-#pragma unroll
-        for (int p = 0; p < P; p++) dmin[p] = rmin(dmin[p], pos[p][0] - tm);
-    } else if (o.kind == RTGR_SPHERE) {                                                // :415-419
-        const R cx = o.p[1], cy = o.p[2], cz = o.p[3], Rr = o.p[8];
-        const R nR2 = -Rr * Rr;
-        if (Rr < R(0)) {
-#pragma unroll
-            for (int p = 0; p < P; p++) {
-                const R dx = pos[p][1] - cx, dy = pos[p][2] - cy, dz = pos[p][3] - cz;
-                dmin[p] = rmin(dmin[p], -rfma(dx, dx, rfma(dy, dy, rfma(dz, dz, nR2))));
-            }
-        } else {
-#pragma unroll
-            for (int p = 0; p < P; p++) {
-                const R dx = pos[p][1] - cx, dy = pos[p][2] - cy, dz = pos[p][3] - cz;
-                dmin[p] = rmin(dmin[p], rfma(dx, dx, rfma(dy, dy, rfma(dz, dz, nR2))));
-            }
-        }
-#ifdef RTGR_USER_OBJECTS
-    } else if (o.kind == RTGR_USER_OBJECT) {                                           // the unit's own distance method (:377-386)
-#pragma unroll
-        for (int p = 0; p < P; p++) dmin[p] = rmin(dmin[p], rtgr_user_distance<R>(o.type, pos[p], o.p));
-#endif
-    } else {
-        // RTGR_DISK: the scan needs the distance's SIGN only — disk_sign_distance reads it off x² + y² without a square
-        // root, exactly (rtgr_physics.hpp).  The asm barrier pins the operands inside this branch: without it LLVM hoists
-        // the (loop-invariant) x² + y² of every sample point out of the object loop, for scenes that contain no disk at all.
-#pragma unroll
-        for (int p = 0; p < P; p++) {
-            R px = pos[p][1], py = pos[p][2];
-            asm volatile("" : "+v"(px), "+v"(py));
-            dmin[p] = rmin(dmin[p], disk_sign_distance<R>(o, px, py, pos[p][3]));
-        }
-    }
-}
-
 // FAR pass: append the wave's collected early-list entries (LDS) to the global list; ONE atomic for all of them
 constexpr uint32_t RTGR_EARLY_BUF = 128;
 template <class R>
@@ -188,19 +106,8 @@ RTGR_DEV void flush_early(const IntegrateArgs<R>& A, const uint32_t* buf, uint32
     for (uint32_t i = lane; i < cnt; i += 64) A.early[base + i] = buf[i];
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// integrate kernel
-// ---------------------------------------------------------------------------------------------------------------------
 // The kernel body is a device function so that run-time generated units (user metrics, rtgr_user_unit.hip.in) can
 // wrap it in extern "C" kernels of their own.
-// the wave-uniform metric constants of an instantiation (the grid's descriptor only where the grid RHS reads it)
-template <class R, int METRIC>
-RTGR_DEV MetricK<R> scene_consts(const DevScene<R>& sc) {
-    MetricK<R> k = metric_consts<R>(sc.M, sc.a);
-    Sampled<R, METRIC>::fill(k, sc);
-    return k;
-}
-
 template <class R, int METRIC, bool SPIN, bool NPTS10, int MODE, bool LDSK = false>
 RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
     using N = Tsit5N<R>;
@@ -520,11 +427,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                 //  already be huge — 0 · inf = NaN would end the ray as RTGR_RAY_NAN instead of DTMIN, a flushed h² would ACCEPT the
                 //  step with maximum growth; same three multiplies.  ADVICE r3.)
                 const float hf32 = (float)h;
-#ifdef RTGR_OLD_ERRNORM
-                const float EEst2 = (acc2.x + acc2.y) * (0.125f * hf32 * hf32);
-#else
                 const float EEst2 = ((acc2.x + acc2.y) * hf32) * (0.125f * hf32);
-#endif
         // [budget: controller]
                 uint32_t done = 0xffu;  // 0xff = still running, else rtgr_ray_status
                 bool is_event = false, is_interior = false, handed = false, hand_back = false;
@@ -604,22 +507,16 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                                 // value): then outside every member, by at least the same margin, for the whole step — no member's
                                 // distance changes sign.  The floor keeps that margin above the rounding noise of the members' own
                                 // distances (|X_g| − R_g > 64 eps (|X_g| + R_g), the noise is a few eps of |X_i| + R_i <= |X_g| + 2 R_g).
-                                const R X0 = x[1] - G.p[1], X1 = x[2] - G.p[2], X2 = x[3] - G.p[3], Rr = G.p[8];
-                                const R D0 = rfma(X0, X0, rfma(X1, X1, rfma(X2, X2, -Rr * Rr)));
-                                const R B = rfma(dl[1], rfma(R(2), rabs(X0), dl[1]),
-                                                 rfma(dl[2], rfma(R(2), rabs(X1), dl[2]), dl[3] * rfma(R(2), rabs(X2), dl[3])));
-                                const R mag = rabs(D0) + R(2) * Rr * Rr;
+                                R D0, B, mag;
+                                sphere_reach<R>(G, x, dl, D0, B, mag);
                                 const bool out = D0 > rfma(guard, B, R(256) * eps * mag);
                                 if (level != 0) { run_out = out; group_out = out; }   // (a lane that has ruled the run out has ruled its groups out)
                                 else group_out = run_out || out;
                                 return __ballot(run && !group_out) != 0ull;
                               },
                               [&](const DevObject<R>& ob, uint32_t o) {   // the spheres of the list: no dispatch, one batch of scalar loads each
-                                const R X0 = x[1] - ob.p[1], X1 = x[2] - ob.p[2], X2 = x[3] - ob.p[3], Rr = ob.p[8];
-                                const R D0 = rfma(X0, X0, rfma(X1, X1, rfma(X2, X2, -Rr * Rr)));
-                                const R B = rfma(dl[1], rfma(R(2), rabs(X0), dl[1]),
-                                                 rfma(dl[2], rfma(R(2), rabs(X1), dl[2]), dl[3] * rfma(R(2), rabs(X2), dl[3])));
-                                const R mag = rabs(D0) + R(2) * Rr * Rr;  // >= |X|² + R²: the operands' magnitude, for the floor
+                                R D0, B, mag;
+                                sphere_reach<R>(ob, x, dl, D0, B, mag);
                                 note(group_out || rabs(D0) > rfma(guard, B, R(256) * eps * mag), o);
                               },
                               [&](const DevObject<R>& ob, uint32_t o) {   // everything else
@@ -671,10 +568,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
         // [budget: hand over]
                     if (hand_over) {
                         // hand the ray, in its PRE-step state, to the NEAR pass (which redoes this step with the full scan)
-                        R* hd = A.hand + idx * HAND_W;
-#pragma unroll
-                        for (int q = 0; q < 4; q++) { hd[q] = x[q]; hd[4 + q] = u[q]; hd[8 + q] = k[0][q]; }
-                        hd[12] = t; hd[13] = dt; hd[14] = ps; hd[15] = (R)lq;
+                        hand_store<R>(A.hand + idx * HAND_W, x, u, k[0], t, dt, ps, lq);
                         const bool early_ray = MODE == MODE_FAR && A.early && nacc < A.near_early;
                         A.meta[idx * 3] = nacc; A.meta[idx * 3 + 1] = nrej;
                         A.meta[idx * 3 + 2] = early_ray ? META_HANDED_EARLY : META_HANDED;
@@ -857,10 +751,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                 if (hand_back) {
                     // NEAR -> next round's FAR pass: the ray has been out of every object's reach for two steps; its
                     // committed state goes back into the hand-over record and the cheaper pass carries it on
-                    R* hd = A.hand + idx * HAND_W;
-#pragma unroll
-                    for (int q = 0; q < 4; q++) { hd[q] = xn[q]; hd[4 + q] = un[q]; hd[8 + q] = k[6][q]; }
-                    hd[12] = t; hd[13] = dt; hd[14] = ps; hd[15] = (R)lq;
+                    hand_store<R>(A.hand + idx * HAND_W, xn, un, k[6], t, dt, ps, lq);
                     A.meta[idx * 3] = nacc; A.meta[idx * 3 + 1] = nrej; A.meta[idx * 3 + 2] = META_HANDBACK;
                     if (MODE == MODE_NEAR) c_maxnear = c_maxnear > (nacc - nacc0) ? c_maxnear : (nacc - nacc0);
                     state = L_FREE;
@@ -975,483 +866,6 @@ void integrate_kernel(const IntegrateArgs<R> A) {
 template <class R, int METRIC>
 __global__ __launch_bounds__(64, 4) void integrate_far4_kernel(const IntegrateArgs<R> A) {
     integrate_body<R, METRIC, false, true, MODE_FAR>(A);
-}
-
-// Ray set-up, one thread per ray: the camera ray itself when the caller gave a camera instead of states (make_canvas,
-// :457-478 — the state never goes through HBM), its key for the longest-first queue (see "ray ordering" below), u̇(y0), the Hairer initial step (d0, d1, one Euler probe, d2; the
-// norms in f32 like the controller's), sign(min_distance(y0)) for the ContinuousCallback (App. B.4) and the controller's
-// q_old = 1e-4 (App. B.2) -> the ray's 16-scalar start record.  2 RHS evaluations per ray (counted by the integrate
-// kernel's counters).  A body function for the same reason as integrate_body.
-template <class R>
-RTGR_DEV void order_key(const R x4[4], const R u4[4], bool valid, uint64_t w, uint8_t* keys, uint32_t* hist);
-
-template <class R, int METRIC, bool SPIN>
-RTGR_DEV void prepare_body(const IntegrateArgs<R>& A) {
-    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool valid = w < A.n;
-    const MetricK<R> MK = scene_consts<R, METRIC>(A.sc);
-    const R reltol = A.opt.reltol, abstol = A.opt.abstol, dtmax = A.opt.lambda1 - A.opt.lambda0;
-    R x[4] = {R(0), R(1), R(0), R(0)}, u[4] = {R(-1), R(0), R(1), R(0)}, k1[4], k2[4];
-    if (valid) {
-        if (A.state0) {
-            const R* s0 = A.state0 + w * 8;
-            bool bad = false;
-#pragma unroll
-            for (int q = 0; q < 4; q++) { x[q] = s0[q]; u[q] = s0[4 + q]; bad = bad || x[q] != x[q] || u[q] != u[q]; }
-            // `@assert !any(isnan, xx)` of kerr_schild (src/RayTraceGR.jl:279): evaluated here, where every caller-supplied
-            // state is read anyway; the host entry points turn the flag into RTGR_ERR_NAN_INPUT
-            if (bad && A.nan_flag) atomicOr(A.nan_flag, 1u);
-        } else {  // make_canvas (src/RayTraceGR.jl:457-478) for this pixel, straight into registers
-            R s[8];
-            const uint64_t idx = A.first + w;
-            make_pixel<R, Sampled<R, METRIC>::NE>(A.sc, A.cam, A.ni, A.nj, idx % A.ni, A.j0 + (idx / A.ni) * A.jstride, s);
-#pragma unroll
-            for (int q = 0; q < 4; q++) { x[q] = s[q]; u[q] = s[4 + q]; }
-        }
-    }
-    if (A.keys) order_key<R>(x, u, valid, w, A.keys, A.hist);  // block-wide (LDS histogram): before any early exit
-    if (!valid) return;
-    // The ray's state is a VALUE from here on, whichever way it was obtained: without this barrier the compiler contracts
-    // the last product of make_pixel (u = (…)·1/√2) into the first sum of the RHS (k_a u^a = u^t + …) when the camera ray
-    // is generated in this kernel, and cannot when the same ray is loaded from the caller's array — camera and state0
-    // frames then differ in the last bit of u̇(y0) (found by test_host_pipeline_with_many_chunks_and_every_output).
-#pragma unroll
-    for (int q = 0; q < 4; q++) { asm volatile("" : "+v"(x[q])); asm volatile("" : "+v"(u[q])); }
-    accel<R, METRIC, SPIN, true>(x + 1, u, MK, k1, x[0]);      // f0 = (u, k1)
-    float acc0 = 0.0f, acc1 = 0.0f;
-    float iskx[4], isku[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        iskx[q] = __builtin_amdgcn_rcpf((float)rfma(rabs(x[q]), reltol, abstol));
-        isku[q] = __builtin_amdgcn_rcpf((float)rfma(rabs(u[q]), reltol, abstol));
-        const float a0 = (float)x[q] * iskx[q], b0 = (float)u[q] * isku[q];
-        const float a1 = (float)u[q] * iskx[q], b1 = (float)k1[q] * isku[q];
-        acc0 = __builtin_fmaf(a0, a0, __builtin_fmaf(b0, b0, acc0));
-        acc1 = __builtin_fmaf(a1, a1, __builtin_fmaf(b1, b1, acc1));
-    }
-    const float d0f = __builtin_sqrtf(acc0 * 0.125f), d1f = __builtin_sqrtf(acc1 * 0.125f);
-    const float dt0f = (d0f < 1e-5f || d1f < 1e-5f) ? 1e-6f : (d0f / d1f) * 0.01f;
-    const R dt0 = rmin((R)dt0f, dtmax);
-    R X[3], U[4];                                              // y0 + dt0 f0
-#pragma unroll
-    for (int q = 0; q < 4; q++) U[q] = rfma(dt0, k1[q], u[q]);
-#pragma unroll
-    for (int q = 0; q < 3; q++) X[q] = rfma(dt0, u[1 + q], x[1 + q]);
-    accel<R, METRIC, SPIN, true>(X, U, MK, k2, rfma(dt0, u[0], x[0]));          // f1 − f0 = (dt0·k1, k2 − k1)
-    float acc2 = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const float a2 = (float)(dt0 * k1[q]) * iskx[q], b2 = (float)(k2[q] - k1[q]) * isku[q];
-        acc2 = __builtin_fmaf(a2, a2, __builtin_fmaf(b2, b2, acc2));
-    }
-    const float d2f = __builtin_sqrtf(acc2 * 0.125f) / (float)dt0;
-    const float md = fmaxf(d1f, d2f);
-    // dt1 = 10^(-(2 + log10 md)/5) = 2^(-(2 log2 10 + log2 md)/5)
-    const float dt1f = (md <= 1e-15f) ? fmaxf(1e-6f, (float)dt0 * 1e-3f) : fexp2(-0.2f * (6.643856189774724f + flog2(md)));
-    const R dt_init = rmin(rmin(R(100) * dt0, (R)dt1f), dtmax);
-    R* hd = A.hand + w * HAND_W;
-#pragma unroll
-    for (int q = 0; q < 4; q++) { hd[q] = x[q]; hd[4 + q] = u[q]; hd[8 + q] = k1[q]; }
-    hd[12] = A.opt.lambda0;
-    hd[13] = dt_init;
-    hd[14] = rsign(min_distance<R>(A.sc, x));
-    hd[15] = R(-13.287712379549449);                           // log2(qoldinit = 1e-4)
-}
-
-template <class R, int METRIC, bool SPIN>
-__global__ __launch_bounds__(256) void prepare_kernel(const IntegrateArgs<R> A) {
-    prepare_body<R, METRIC, SPIN>(A);
-}
-
-// Per-launch reset of the queue heads and of the ordering histogram.  A kernel rather than hipMemsetAsync: memset nodes
-// of a captured HIP graph were observed not to re-run on later replays (ROCm 7.0 runtime bundled with PyTorch), which
-// left stale queue heads / histograms and sent the scatter out of bounds; kernel nodes replay reliably.
-static __global__ __launch_bounds__(256) void reset_kernel(unsigned long long* ctrl, uint32_t* hist512) {
-    if (threadIdx.x < 8) ctrl[threadIdx.x] = 0ull;
-    if (hist512) { hist512[threadIdx.x] = 0u; hist512[256 + threadIdx.x] = 0u; }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// ray ordering: longest-expected-first (LPT) queue order
-//
-// Rays need 27…991 step attempts and a lane processes its rays one after another, so with few rays per lane (small
-// screens, or one slab of an 8-GPU split: ~10 rays per lane) the kernel time is set by the lanes that happen to draw a
-// long ray LAST: greedy scheduling in natural order runs 1.24x (10 rays/lane) … 1.46x (5 rays/lane) over the ideal.
-// The rays that get long are the ones aimed at the hole, so the queue is ordered by the angle α between the ray and the
-// direction to the origin (sin α = impact parameter / distance): a 256-bucket counting sort, ascending.  Simulated
-// makespan over ideal with that order: 1.02-1.03.  The order only changes WHEN a ray is integrated, never its result.
-// ---------------------------------------------------------------------------------------------------------------------
-template <class R>
-RTGR_DEV void order_key(const R x4[4], const R u4[4], bool valid, uint64_t w, uint8_t* keys, uint32_t* hist) {
-    __shared__ uint32_t lh[256];  // called by every thread of a 256-thread block (prepare_kernel)
-    lh[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t b = 0xffffffffu;
-    if (valid) {
-        const R x = x4[1], y = x4[2], z = x4[3], ux = u4[1], uy = u4[2], uz = u4[3];
-        const R xx = x * x + y * y + z * z, uu = ux * ux + uy * uy + uz * uz, xu = x * ux + y * uy + z * uz;
-        float sin2 = 1.0f;
-        if (xu < R(0) && xx > R(0) && uu > R(0)) sin2 = fmaxf(0.0f, 1.0f - (float)(xu * xu / (xx * uu)));
-        b = (uint32_t)fminf(255.0f, 256.0f * __builtin_sqrtf(sin2));  // moving away -> last bucket
-        keys[w] = (uint8_t)b;
-    }
-    // neighbouring rays share a handful of buckets: one LDS atomic per distinct bucket per wave, not one per ray
-    unsigned long long todo = __ballot(valid);
-    while (todo != 0ull) {
-        const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
-        const uint32_t b0 = __shfl(b, (int)leader, 64);
-        const unsigned long long m = __ballot(valid && b == b0);
-        if ((threadIdx.x & 63) == leader) atomicAdd(&lh[b0], (uint32_t)__builtin_popcountll(m));
-        todo &= ~m;
-    }
-    __syncthreads();
-    if (lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[threadIdx.x]);
-}
-// exclusive prefix sum of the 256-bin histogram (one block) -> running offsets used by the scatter
-static __global__ __launch_bounds__(256) void order_scan_kernel(const uint32_t* hist, uint32_t* offsets) {
-    __shared__ uint32_t sh[256];
-    sh[threadIdx.x] = hist[threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t acc = 0;
-        for (int b = 0; b < 256; b++) { const uint32_t c = sh[b]; sh[b] = acc; acc += c; }
-    }
-    __syncthreads();
-    offsets[threadIdx.x] = sh[threadIdx.x];
-}
-// order[offset(bucket)++] = ray index.  Ranks inside a 256-ray block come from LDS atomics; each block then claims its
-// range of every non-empty bucket with ONE global atomic (neighbouring rays share a handful of buckets).
-static __global__ __launch_bounds__(256) void order_scatter_kernel(const uint8_t* keys, uint64_t n, uint32_t* offsets, uint32_t* order) {
-    __shared__ uint32_t lcount[256], gbase[256];
-    lcount[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool valid = w < n;
-    const uint32_t b = valid ? keys[w] : 0xffffffffu;
-    const uint32_t lane = threadIdx.x & 63;
-    uint32_t r = 0;
-    unsigned long long todo = __ballot(valid);
-    while (todo != 0ull) {  // one LDS atomic per distinct bucket per wave; lanes rank themselves inside the ballot mask
-        const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
-        const uint32_t b0 = __shfl(b, (int)leader, 64);
-        const unsigned long long m = __ballot(valid && b == b0);
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&lcount[b0], (uint32_t)__builtin_popcountll(m));
-        base = __shfl(base, (int)leader, 64);
-        if (valid && b == b0) r = base + mask_rank(m, lane);
-        todo &= ~m;
-    }
-    __syncthreads();
-    if (lcount[threadIdx.x]) gbase[threadIdx.x] = atomicAdd(&offsets[threadIdx.x], lcount[threadIdx.x]);
-    __syncthreads();
-    if (valid) order[gbase[b] + r] = (uint32_t)w;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// resolve kernel: one thread per ray — root of cond(x(θ)) on [0, top], end state, colouring rule, stores
-// ---------------------------------------------------------------------------------------------------------------------
-template <class R, bool SEL = false>
-RTGR_DEV R cond_poly(const DevScene<R>& sc, const R x0[4], const R c[4][4], R th, ObjSel sel = ObjSel{}) {
-    R x[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) x[q] = rfma(th, rfma(th, rfma(th, rfma(th, c[3][q], c[2][q]), c[1][q]), c[0][q]), x0[q]);
-    return min_distance<R, SEL>(sc, x, sel);
-}
-
-// LONG LISTS.  The root-find below evaluates the condition — the minimum over ALL objects' distances (:433-441) — some ten times per
-// event, and the colour rule once more: with N objects, ~10 N distances per ray, of which all but one or two are of objects nowhere
-// near the step the event lies in.  For a list beyond the argument block the wave first narrows the list down: over the event's step
-// every object's distance stays within d_i(0) ± B_i (the bounds of the FAR pass's reach test, from the box |x_q(θ) − x_q(0)| <= δ_q,
-// θ in [0, top], that the step's polynomial spans), so the minimum never exceeds U = min_i (d_i(0) + B_i), and an object with
-// d_i(0) − B_i > U is never the minimum — neither its value nor its index can enter a result, at any θ of the bracket.  The objects
-// that SOME lane of the wave cannot leave out form the selection (one bit per object up to 64, per 2^shift neighbours beyond); the
-// rays of a wave are neighbours on the canvas, so the selection is a handful of objects.  Same frame bit for bit (under test with
-// option groups = 0, which switches this off too).  Guards as in the reach test: 1e-6 relative on the bound, a floor of 256 ulp of the
-// operands' magnitude; a NaN anywhere keeps the object in.
-template <class R>
-RTGR_DEV void distance_bounds(const DevObject<R>& ob, const R x[4], const R dl[4], R* lower, R* upper) {
-    const R eps = sizeof(R) == 8 ? R(2.220446049250313e-16) : R(1.1920929e-7);
-    const R guard = R(1) + R(1e-6);
-    R d0, B, mag;
-    if (ob.kind == RTGR_SPHERE) {
-        const R X0 = x[1] - ob.p[1], X1 = x[2] - ob.p[2], X2 = x[3] - ob.p[3], Rr = ob.p[8];
-        const R D0 = rfma(X0, X0, rfma(X1, X1, rfma(X2, X2, -Rr * Rr)));
-        B = rfma(dl[1], rfma(R(2), rabs(X0), dl[1]), rfma(dl[2], rfma(R(2), rabs(X1), dl[2]), dl[3] * rfma(R(2), rabs(X2), dl[3])));
-        mag = rabs(D0) + R(2) * Rr * Rr;
-        d0 = Rr < R(0) ? -D0 : D0;
-    } else if (ob.kind == RTGR_PLANE) {
-        d0 = x[0] - ob.p[0];
-        B = dl[0];
-        mag = rabs(x[0]) + rabs(ob.p[0]);
-#ifdef RTGR_USER_OBJECTS
-    } else if (ob.kind == RTGR_USER_OBJECT) {
-#ifdef RTGR_USER_REACH
-        const R gd[4] = {guard * dl[0], guard * dl[1], guard * dl[2], guard * dl[3]};
-        d0 = rtgr_user_distance<R>(ob.type, x, ob.p);
-        B = rtgr_user_reach<R>(ob.type, x, ob.p, gd);
-        mag = R(1) + rabs(d0);
-#else
-        d0 = R(0); B = R(__builtin_huge_val()); mag = R(0);   // no bound given: always in, never bounds the minimum
-#endif
-#endif
-    } else {   // RTGR_DISK: a maximum of three terms moves by at most the largest of their moves
-        d0 = obj_distance<R>(ob, x);
-        B = rmax(dl[3], dl[1] + dl[2]);
-        mag = rabs(d0) + rabs(x[1]) + rabs(x[2]) + rabs(x[3]) + rabs(ob.p[2]);
-    }
-    const R w = rfma(guard, B, R(256) * eps * mag);
-    *lower = d0 - w;
-    *upper = d0 + w;
-}
-template <class R>
-RTGR_DEV ObjSel select_objects(const DevScene<R>& sc, const R x0[4], const R c[4][4], R top, bool event) {
-    ObjSel sel{0ull, objsel_shift(sc.nobj), 0u, 0u};
-    R dl[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) dl[q] = top * rfma(top, rfma(top, rfma(top, rabs(c[3][q]), rabs(c[2][q])), rabs(c[1][q])), rabs(c[0][q]));
-    R U = R(__builtin_huge_val());
-    auto upper = [&](const DevObject<R>& ob, uint32_t) {
-        R lo, up;
-        distance_bounds<R>(ob, x0, dl, &lo, &up);
-        U = up < U ? up : U;
-    };
-    if (sc.ngroups == 0u) {   // a list without groups: every object twice
-        for_each_object<R>(sc, upper);
-        for_each_object<R>(sc, [&](const DevObject<R>& ob, uint32_t o) {
-            R lo, up;
-            distance_bounds<R>(ob, x0, dl, &lo, &up);
-            if (__ballot(event && !(lo > U)) != 0ull) sel.add(o);
-        });
-        return sel;
-    }
-    // A grouped list (DevScene): the bound U may come from ANY objects — from a sample first (one member of every group, the loose
-    // spheres, the other kinds).  A group whose bounding sphere stays farther than sqrt(U) away for the whole step holds no member
-    // that can be the minimum: with m = |X_g| − R_g − |δ| > sqrt(U) >= 0 every member has |X_i(θ)| − r_i >= m, so its distance
-    // (|X_i| − r_i)(|X_i| + r_i) >= m² > U (members have r_i >= 0: the host leaves inside-out spheres loose).  Such groups — and
-    // runs of groups — are passed over when every lane agrees; the members that remain tighten the bound (U2: the minimum over the
-    // sample AND over everything that passed, which holds the object the full list's bound comes from), and a last walk over what
-    // passed keeps what the tight bound cannot leave out: the same selection as two walks over the whole list give.
-    for_each_sample<R>(sc, upper);
-    const R eps = sizeof(R) == 8 ? R(2.220446049250313e-16) : R(1.1920929e-7);
-    const R guard = R(1) + R(1e-6);
-    const R reach = guard * (rsqrt_(rfma(dl[1], dl[1], rfma(dl[2], dl[2], dl[3] * dl[3]))) + (U > R(0) ? rsqrt_(U) : R(0)));
-    R U2 = U;
-    auto member = [&](const DevObject<R>& ob, uint32_t o) {
-        R lo, up;
-        distance_bounds<R>(ob, x0, dl, &lo, &up);
-        const bool in = !(lo > U);
-        U2 = (in && up < U2) ? up : U2;
-        if (__ballot(event && in) != 0ull) sel.add(o);
-    };
-    for_each_within_reach<R>(sc,
-        [&](const DevObject<R>& G, int) -> bool {
-            const R X0 = x0[1] - G.p[1], X1 = x0[2] - G.p[2], X2 = x0[3] - G.p[3];
-            const R S = rfma(X0, X0, rfma(X1, X1, X2 * X2));
-            const R t = G.p[8] + reach;
-            const R rhs = t * t;
-            const bool far_away = S > rfma(guard, rhs, R(256) * eps * (S + rhs));
-            return __ballot(event && !far_away) != 0ull;
-        },
-        member, member);
-    ObjSel fin{0ull, sel.shift, 0u, 0u};
-    for_each_selected<R>(sc, sel, [&](const DevObject<R>& ob, uint32_t o) {
-        R lo, up;
-        distance_bounds<R>(ob, x0, dl, &lo, &up);
-        if (__ballot(event && !(lo > U2)) != 0ull) fin.add(o);
-    });
-    return fin;
-}
-
-// Bracketed root of g(θ) = ps·cond(x(θ)) on [0, top], g(0) > 0 >= g(top).  Ridders' method: every iterate stays inside
-// the bracket, the estimate x4 converges quadratically (the bracket WIDTH only halves per iteration, so convergence is
-// judged on successive estimates).  Once the estimate has settled, probes 16 ulp before and after it pin the crossing:
-// the result is a point with g >= 0 within ~32 ulp of it — the reference's prevfloat(find_zero(...))
-// up to a few ulp (a 512-ulp window, 1e-13 in θ, for the rays whose distance is too noisy for that).  If the probes fail
-// (estimate was off) the loop simply continues on the tightened bracket; the bisection point `mid` guarantees progress.
-// -DRTGR_ROOT_STATS builds report the iteration count of every ray through lambda_end.
-template <class R, bool SEL = false>
-RTGR_DEV R event_root(const DevScene<R>& sc, const R x0[4], const R c[4][4], R ps, R top, int* iters = nullptr, ObjSel sel = ObjSel{}) {
-    R lo = R(0), hi = top;
-    R fhi = cond_poly<R, SEL>(sc, x0, c, hi, sel) * ps;
-    R flo = cond_poly<R, SEL>(sc, x0, c, R(0), sel) * ps;
-    R result = R(0);
-    bool done = false;
-    if (fhi == R(0)) { result = hi; done = true; }
-    else if (!(flo > R(0)) || !(fhi < R(0))) { result = R(0); done = true; }
-    const R eps = sizeof(R) == 8 ? R(2.220446049250313e-16) : R(1.1920929e-7);
-    R est_prev = R(-1);
-    for (int it = 0; it < 96 && !done; it++) {
-        if (iters) *iters = it + 1;
-        const R width = hi - lo;
-        const R mid = rfma(R(0.5), width, lo);
-        if (!(width > R(2) * eps * hi) || !(mid > lo && mid < hi)) {
-            result = lo; done = true;
-        } else {
-            const R fm = cond_poly<R, SEL>(sc, x0, c, mid, sel) * ps;
-            const R rad = rfma(fm, fm, -flo * fhi);  // > 0 since flo > 0 > fhi
-            // Ridders' estimate.  When one end of the bracket already sits on the root (|g(lo)| ~ 1e-17 after a lucky
-            // iterate) the formula returns that end itself: the point to EVALUATE is then the midpoint (progress), but the
-            // ESTIMATE is the end — without this distinction such rays never "settled" and bisected 45 more times
-            // (0.3 % of the rays, 13-50 iterations; their waves waited: 4 iterations per ray, 10.5 per wave).
-            const R xr = rfma((mid - lo) * fm, frsq<R>(rad), mid);
-            const bool inside = xr > lo && xr < hi;
-            const R x4 = inside ? xr : mid;
-            const R est = inside ? xr : (xr <= lo ? lo : (xr >= hi ? hi : mid));
-            const R f4 = (x4 == mid) ? fm : cond_poly<R, SEL>(sc, x0, c, x4, sel) * ps;
-            // An exact zero is common (a plane at a representable time makes g vanish on a whole ulp-interval of θ):
-            // "directly at zero" is an accepted result, so stop there.
-            if (fm == R(0)) { result = mid; done = true; }
-            else if (f4 == R(0)) { result = x4; done = true; }
-            const R a = rmin(mid, x4), b = rmax(mid, x4);
-            const R fa = (mid <= x4) ? fm : f4, fb = (mid <= x4) ? f4 : fm;
-            if (fa > R(0)) {
-                lo = a; flo = fa;
-                if (fb > R(0)) { lo = b; flo = fb; } else { hi = b; fhi = fb; }
-            } else {
-                hi = a; fhi = fa;
-            }
-            // two successive estimates within 256 ulp: converged down to the rounding noise of the distance itself
-            // (ulp of max(θ, top/16): the noise is absolute in θ — λ = t + hθ is what matters — so a root near θ = 0
-            //  must not be chased to ITS ulp)
-            const R scale = rmax(est, R(0.0625) * top);
-            const bool settled = RTGR_ROOT_SHORTCUT && (rabs(est - est_prev) <= R(256) * eps * scale);
-            est_prev = est;
-            if (settled && !done) {
-                // Verify the settled estimate two-sidedly: 16 ulp before and after; if the sign change is not in there
-                // (the distance is evaluated with a rounding noise of ~10 ulp of θ, which makes the estimates jitter and
-                // can push the crossing out), 512 ulp.  Rays that never pass fall back to ~50 bisection steps on the
-                // one-sided Ridders bracket, and their whole wave waits for them (measured with an 8-ulp settle test
-                // and the 16-ulp window only: mean 5.4 iterations per ray, 15.7 per wave).
-#pragma unroll 1
-                for (int pass = 0; pass < 2 && !done; pass++) {
-                    const R wd = (pass == 0 ? R(16) : R(512)) * eps;
-                    const R pm = rmax(rfma(-wd, scale, est), lo), pp = rmin(rfma(wd, scale, est), hi);
-                    const R fpm = (pm > lo) ? cond_poly<R, SEL>(sc, x0, c, pm, sel) * ps : flo;
-                    const R fpp = (pp < hi) ? cond_poly<R, SEL>(sc, x0, c, pp, sel) * ps : fhi;
-                    if (!(fpm < R(0)) && !(fpp > R(0))) {
-                        result = pm; done = true;  // the sign change (or an exact zero at pm) is inside [pm, pp]
-                    } else if (fpp == R(0)) {
-                        result = pp; done = true;
-                    } else {
-                        // the crossing is elsewhere: tighten the bracket with what was learnt
-                        if (fpm > R(0)) { lo = pm; flo = fpm; } else { hi = pm; fhi = fpm; }
-                        if (fpp > R(0)) { if (pp > lo) { lo = pp; flo = fpp; } } else if (pp < hi) { hi = pp; fhi = fpp; }
-                    }
-                }
-                if (!done) est_prev = R(-1);
-            }
-        }
-    }
-    return done ? result : lo;
-}
-#ifdef RTGR_ROOT_STATS
-#define RTGR_ROOT_STATS_ARG , &root_iters
-#else
-#define RTGR_ROOT_STATS_ARG , nullptr
-#endif
-
-// the stores of one resolved ray
-template <class R>
-RTGR_DEV void resolve_store(const ResolveArgs<R>& A, uint64_t w, const RecRef<const R>& rec, const R xe[4], R Theta, R t, R h, const R col[3],
-                            uint32_t hit, R ps, int root_iters) {
-    (void)root_iters;
-    const uint64_t idx = A.offset + w;
-    A.rgb[idx] = col[0];
-    A.rgb[A.n_slab + idx] = col[1];
-    A.rgb[2 * A.n_slab + idx] = col[2];
-    const uint32_t* mt = A.meta + w * 3;
-    if (A.state_end) {
-        R* se = A.state_end + idx * 8;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            se[q] = xe[q];
-            R ue = rec[REC_U + q];
-            if (ps != R(0)) {
-                const R* cu = rec.tail + (REC_CU - HAND_W);
-                ue = rfma(Theta, rfma(Theta, rfma(Theta, rfma(Theta, cu[12 + q], cu[8 + q]), cu[4 + q]), cu[q]), ue);
-            }
-            se[4 + q] = ue;
-        }
-    }
-#ifdef RTGR_ROOT_STATS
-    if (A.lambda_end) A.lambda_end[idx] = (R)root_iters;  // debug build: iterations of the root find
-#else
-    if (A.lambda_end) A.lambda_end[idx] = rfma(h, Theta, t);
-#endif
-    if (A.status) A.status[idx] = (uint8_t)(mt[2] & 0xffu);
-    if (A.hit) A.hit[idx] = (uint8_t)hit;
-    if (A.hit32) A.hit32[idx] = hit;
-    if (A.n_accept) A.n_accept[idx] = mt[0];
-    if (A.n_reject) A.n_reject[idx] = mt[1];
-}
-template <class R> RTGR_DEV void resolve_body_selected(const ResolveArgs<R>& A);
-
-// (a body function: a unit with user objects wraps it in a resolve kernel of its own — the root-find evaluates the objects'
-//  distances and the colour rule their objcolor)
-template <class R>
-RTGR_DEV void resolve_body(const ResolveArgs<R>& A) {
-    if (__builtin_expect(A.select != 0u && A.sc.nobj > (uint32_t)RTGR_MAX_OBJECTS && A.n != 0, 0)) { resolve_body_selected<R>(A); return; }
-    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= A.n) return;
-    const RecRef<const R> rec{A.hand + w * HAND_W, A.rec + w * (uint64_t)A.recw};
-    R x0[4], xe[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) xe[q] = x0[q] = rec[REC_X + q];
-    const R ps = rec[REC_PS], top = rec[REC_TOP], t = rec[REC_T], h = rec[REC_H];
-    R Theta = R(0);
-    int root_iters = 0;
-    (void)root_iters;
-    if (ps != R(0)) {  // an event: the polynomial part of the record is valid
-        R c[4][4];
-#pragma unroll
-        for (int m = 0; m < 4; m++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) c[m][q] = rec[REC_C + 4 * m + q];
-        Theta = event_root<R>(A.sc, x0, c, ps, top RTGR_ROOT_STATS_ARG);
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            xe[q] = rfma(Theta, rfma(Theta, rfma(Theta, rfma(Theta, c[3][q], c[2][q]), c[1][q]), c[0][q]), x0[q]);
-    }
-    R col[3];
-    const uint32_t hit = colour_pixel<R>(A.sc, A.opt, xe, col);
-    resolve_store<R>(A, w, rec, xe, Theta, t, h, col, hit, ps, root_iters);
-}
-// … and the same with the list narrowed down first (select_objects): lists beyond the argument block
-template <class R>
-RTGR_DEV void resolve_body_selected(const ResolveArgs<R>& A) {
-    const uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = w0 < A.n;
-    const uint64_t w = live ? w0 : A.n - 1;   // (every lane of the wave takes part in the selection's ballots; the spare ones repeat the last ray, silently)
-    const RecRef<const R> rec{A.hand + w * HAND_W, A.rec + w * (uint64_t)A.recw};
-    R x0[4], xe[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) xe[q] = x0[q] = rec[REC_X + q];
-    const R ps = rec[REC_PS], top = rec[REC_TOP], t = rec[REC_T], h = rec[REC_H];
-    R Theta = R(0);
-    int root_iters = 0;
-    (void)root_iters;
-    const bool event = ps != R(0);
-    R c[4][4];
-#pragma unroll
-    for (int m = 0; m < 4; m++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) c[m][q] = event ? rec[REC_C + 4 * m + q] : R(0);
-    ObjSel sel = select_objects<R>(A.sc, x0, c, event ? top : R(0), event);
-    if (event) {
-        Theta = event_root<R, true>(A.sc, x0, c, ps, top RTGR_ROOT_STATS_ARG, sel);
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            xe[q] = rfma(Theta, rfma(Theta, rfma(Theta, rfma(Theta, c[3][q], c[2][q]), c[1][q]), c[0][q]), x0[q]);
-    }
-    // (a ray without an event is coloured where it stopped: nothing is known about that point — every object is asked)
-    if (__ballot(!event) != 0ull) { sel.mask = ~0ull; sel.count = 65u; }
-    R col[3];
-    const uint32_t hit = colour_pixel<R, true>(A.sc, A.opt, xe, col, sel);
-    if (live) resolve_store<R>(A, w, rec, xe, Theta, t, h, col, hit, ps, root_iters);
-}
-template <class R>
-__global__ __launch_bounds__(256) void resolve_kernel(const ResolveArgs<R> A) {
-    resolve_body<R>(A);
 }
 
 }  // namespace rtgr

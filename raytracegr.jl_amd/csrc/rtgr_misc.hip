@@ -6,7 +6,7 @@
 //   redshift_kernel               frequency ratio observed/emitted from Sphere.vel (no reference counterpart)
 //   place_rows                    multi-device gather: a rank's cyclic rows back into the full frame on device 0
 #include "rtgr_host.hpp"
-#include "rtgr_integrator.hpp"
+#include "rtgr_camera.hpp"
 
 namespace rtgr {
 
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void place_rows_kernel(const T* part, uint64_t
     full[pl * ni * nj * elem + (rank + k * nranks) * row_elems + i] = part[t];
 }
 
-// ---- redshift: redshift_body (rtgr_integrator.hpp) ----------------------------------------------------------------------
+// ---- redshift: redshift_body (rtgr_camera.hpp) ----------------------------------------------------------------------
 template <class R>
 __global__ __launch_bounds__(256) void redshift_kernel(DevScene<R> sc, DevCamera<R> cam, const R* state0, uint64_t ni, uint64_t nj,
                                                        uint64_t j0, uint64_t jstride, uint64_t n, uint64_t out_offset,

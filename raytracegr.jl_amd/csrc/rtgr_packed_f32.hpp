@@ -16,7 +16,7 @@
 // FAR / NEAR split does not pay, rtgr_pipeline.hpp), interp_points = 10, closed-form RHS of the built-in metrics.  Everything
 // else (user metrics, generic RHS, other interp_points) keeps the scalar kernel; option pack = 0 forces it for A/B.
 #pragma once
-#include "rtgr_persistent.hpp"
+#include "rtgr_integrate.hpp"
 
 namespace rtgr {
 
@@ -53,22 +53,7 @@ RTGR_DEV void fold_distances2(const DevObject<float>& o, const V2 (&pos)[P][4], 
 #pragma unroll
         for (int p = 0; p < P; p++) dmin[p] = rmin<V2>(dmin[p], pos[p][0] - tm);
     } else if (o.kind == RTGR_SPHERE) {                                                // :415-419
-        const V2 cx = V2(o.p[1]), cy = V2(o.p[2]), cz = V2(o.p[3]);
-        const float Rr = o.p[8];
-        const V2 nR2 = V2(-Rr * Rr);
-        if (Rr < 0.0f) {
-#pragma unroll
-            for (int p = 0; p < P; p++) {
-                const V2 dx = pos[p][1] - cx, dy = pos[p][2] - cy, dz = pos[p][3] - cz;
-                dmin[p] = rmin<V2>(dmin[p], -rfma<V2>(dx, dx, rfma<V2>(dy, dy, rfma<V2>(dz, dz, nR2))));
-            }
-        } else {
-#pragma unroll
-            for (int p = 0; p < P; p++) {
-                const V2 dx = pos[p][1] - cx, dy = pos[p][2] - cy, dz = pos[p][3] - cz;
-                dmin[p] = rmin<V2>(dmin[p], rfma<V2>(dx, dx, rfma<V2>(dy, dy, rfma<V2>(dz, dz, nR2))));
-            }
-        }
+        fold_sphere<float, P>(o, pos, dmin);
     } else {   // RTGR_DISK: per half through the scalar sign-exact surrogate (fold_distances; the asm barrier keeps it inside this branch)
 #pragma unroll
         for (int p = 0; p < P; p++) {
@@ -81,7 +66,7 @@ RTGR_DEV void fold_distances2(const DevObject<float>& o, const V2 (&pos)[P][4], 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// the FULL pass, two rays per lane.  Structure and comments follow integrate_body (rtgr_persistent.hpp), MODE_FULL, NPTS10.
+// the FULL pass, two rays per lane.  Structure and comments follow integrate_body (rtgr_integrate.hpp), MODE_FULL, NPTS10.
 // ---------------------------------------------------------------------------------------------------------------------
 // FARP = true (round 4, experiment behind option `packfar`): the scan-free FAR instantiation.  The nine sample positions and
 // distances of both rays and the position polynomial are what push this kernel from 159 to 205 registers (two waves per SIMD,
@@ -126,7 +111,7 @@ RTGR_DEV void integrate2_body(const IntegrateArgs<float>& A) {
             while (m_need != 0ull) {
                 if (q_next == q_end) {
                     if (exhausted) break;
-                    // first pops by WAVE INDEX (see "wave ages", rtgr_persistent.hpp): queue positions [128 b, 128 b + 128) start in
+                    // first pops by WAVE INDEX (see "wave ages", rtgr_integrate.hpp): queue positions [128 b, 128 b + 128) start in
                     // workgroup b — 64 per half —, the atomic head serves positions from 128 * gridDim.x on
                     const unsigned long long amount = first_pop[hh] ? 64ull : qchunk;
                     unsigned long long base = 0;
@@ -278,13 +263,10 @@ RTGR_DEV void integrate2_body(const IntegrateArgs<float>& A) {
                     lhs = rabs<V2>(x[0] - V2(ob.p[0]));
                     rhs = rfma<V2>(V2(guard), dl[0], V2(256.0f * eps) * (rabs<V2>(x[0]) + V2(__builtin_fabsf(ob.p[0]))));
                 } else if (ob.kind == RTGR_SPHERE) {
-                    const V2 X0 = x[1] - V2(ob.p[1]), X1 = x[2] - V2(ob.p[2]), X2 = x[3] - V2(ob.p[3]);
-                    const float Rr = ob.p[8];
-                    const V2 D0 = rfma<V2>(X0, X0, rfma<V2>(X1, X1, rfma<V2>(X2, X2, V2(-Rr * Rr))));
-                    const V2 B = rfma<V2>(dl[1], rfma<V2>(V2(2.0f), rabs<V2>(X0), dl[1]),
-                                          rfma<V2>(dl[2], rfma<V2>(V2(2.0f), rabs<V2>(X1), dl[2]), dl[3] * rfma<V2>(V2(2.0f), rabs<V2>(X2), dl[3])));
+                    V2 D0, B, mag;
+                    sphere_reach<float>(ob, x, dl, D0, B, mag);
                     lhs = rabs<V2>(D0);
-                    rhs = rfma<V2>(V2(guard), B, V2(256.0f * eps) * (lhs + V2(2.0f * Rr * Rr)));
+                    rhs = rfma<V2>(V2(guard), B, V2(256.0f * eps) * mag);
                 } else {
                     V2 px = x[1], py = x[2];
                     asm volatile("" : "+v"(px), "+v"(py));  // keep the disk's root inside this branch

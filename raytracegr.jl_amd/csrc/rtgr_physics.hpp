@@ -120,7 +120,7 @@ struct KSField {
 // SPIN = false is the reference's actual configuration (a = 0 hard-wired, :276) and drops the a-terms statically.
 template <class R, int METRIC, bool SPIN, bool FAST = false>
 RTGR_DEV void ks_field(R x, R y, R z, R M, R a, KSField<R>& F) {
-#pragma clang fp contract(off)   // (part of the camera: see make_pixel, rtgr_integrator.hpp)
+#pragma clang fp contract(off)   // (part of the camera: see make_pixel, rtgr_camera.hpp)
     const R a2 = SPIN ? a * a : R(0);
     const R rho2 = rfma(x, x, rfma(y, y, z * z));
     R r, rq2, rz;  // r, 2*∂r/∂q (so that ∇r = rq2*(x,y,z) + rz*ẑ), explicit ∂r/∂z
@@ -250,6 +250,24 @@ RTGR_DEV double uniform_(double v) {
 RTGR_DEV float uniform_(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, v)));
 }
+// fast f32 helpers for the step-size machinery
+// (uniform_() above: a wave-uniform value computed with vector instructions — there is no scalar f64 ALU —
+//  lives in a VGPR and, in a kernel squeezed to 127 registers, gets spilled to scratch and reloaded in the loop; through
+//  readfirstlane it lives in SGPRs.)
+// one-instruction f32 max / min / clamp (fmaxf / fminf spend a second v_max x, x on canonicalising each computed operand)
+RTGR_DEV float fmax1(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+RTGR_DEV float fmin1(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+RTGR_DEV float fclamp1(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }  // v_med3_f32
+RTGR_DEV float flog2(float x) { return __builtin_amdgcn_logf(x); }   // v_log_f32
+RTGR_DEV float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }  // v_exp_f32
+
+typedef float float2_t __attribute__((ext_vector_type(2)));
+
+// lanes below `lane` set in mask
+RTGR_DEV uint32_t mask_rank(unsigned long long mask, uint32_t lane) {
+    return (uint32_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+}
+
 template <class R>
 RTGR_DEV MetricK<R> metric_consts(R M, R a) {
     MetricK<R> k;
@@ -647,7 +665,7 @@ RTGR_DT RTGR_DEV void metric_dual(uint32_t metric, R M, R a, const RTGR_DD xx[4]
 
 template <class R>
 RTGR_DEV void inv4sym(const R m[4][4], R o[4][4]) {  // cofactor inverse (StaticArrays closed form)
-#pragma clang fp contract(off)   // (part of the camera: see make_pixel, rtgr_integrator.hpp)
+#pragma clang fp contract(off)   // (part of the camera: see make_pixel, rtgr_camera.hpp)
     const R s0 = m[0][0] * m[1][1] - m[1][0] * m[0][1], s1 = m[0][0] * m[1][2] - m[1][0] * m[0][2];
     const R s2 = m[0][0] * m[1][3] - m[1][0] * m[0][3], s3 = m[0][1] * m[1][2] - m[1][1] * m[0][2];
     const R s4 = m[0][1] * m[1][3] - m[1][1] * m[0][3], s5 = m[0][2] * m[1][3] - m[1][2] * m[0][3];
@@ -840,267 +858,12 @@ RTGR_DEV void christoffel_dev(const R g[4][4], const R dg[4][4][4], R Gam[4][4][
             }
 }
 
-// ---- objects (src/RayTraceGR.jl:374-441) -------------------------------------------------------------------------------
-// `Object{T}` is an open abstract type with two methods, distance and objcolor (:374-389).  A run-time unit whose source
-// defines them (rtgr_user_unit.hip.in sets RTGR_USER_OBJECTS) supplies
-//     template <class S> __device__ S    rtgr_user_distance(unsigned type, const S x[4], const S p[9]);
-//     template <class S> __device__ void rtgr_user_objcolor(unsigned type, const S x[4], const S p[9], S rgb[3]);
-// and, optionally (RTGR_USER_REACH), the bound the FAR pass needs to skip a step's scan:
-//     template <class S> __device__ S    rtgr_user_reach(unsigned type, const S x[4], const S p[9], const S dl[4]);
-//     >= |distance(x') − distance(x)| for every x' with |x'_q − x_q| <= dl[q]
-// (include/rtgr.h "user objects").  The library's own kernels are compiled without them: a scene with an RTGR_USER_OBJECT
-// only ever runs with the kernels of its unit (convert_scene, rtgr_context.hip).
-#ifdef RTGR_USER_OBJECTS
-template <class S> __device__ S rtgr_user_distance(unsigned type, const S x[4], const S p[9]);
-template <class S> __device__ void rtgr_user_objcolor(unsigned type, const S x[4], const S p[9], S rgb[3]);
-#ifdef RTGR_USER_REACH
-template <class S> __device__ S rtgr_user_reach(unsigned type, const S x[4], const S p[9], const S dl[4]);
-#endif
-#ifdef RTGR_USER_SAMPLE
-template <class S> __device__ bool rtgr_user_sample(unsigned type, S p[9]);   // optional: a sample object of `type` for the load-time probe
-#endif
-#endif
-
-template <class R>
-RTGR_DEV R obj_distance(const DevObject<R>& o, const R pos[4]) {
-    if (o.kind == RTGR_PLANE) return pos[0] - o.p[0];                                    // :399-401
-    if (o.kind == RTGR_SPHERE) {                                                         // :415-419
-        const R dx = pos[1] - o.p[1], dy = pos[2] - o.p[2], dz = pos[3] - o.p[3];
-        const R Rr = o.p[8];
-        const R d = rfma(dx, dx, rfma(dy, dy, rfma(dz, dz, -Rr * Rr)));
-        return Rr < R(0) ? -d : d;  // sign(R)*( … ); R = 0 never used
-    }
-#ifdef RTGR_USER_OBJECTS
-    if (o.kind == RTGR_USER_OBJECT) return rtgr_user_distance<R>(o.type, pos, o.p);     // distance(obj::MyThing, pos)  :377-386
-#endif
-    // RTGR_DISK: max(|z|−h, r_in−ϱ, ϱ−r_out)
-    const R rc = rsqrt_(rfma(pos[1], pos[1], pos[2] * pos[2]));
-    R d = rabs(pos[3]) - o.p[0];
-    d = rmax(d, o.p[1] - rc);
-    d = rmax(d, rc - o.p[2]);
-    return d;
-}
-
-// The disk's distance as the ContinuousCallback SCAN needs it: its sign only (the scan multiplies the minimum over the
-// objects by the sign at the step start and tests < 0 / <= 0; the minimum's sign is fixed by its members' signs).  The two
-// radial terms r_in − ϱ and ϱ − r_out are replaced by THEIR SIGNS, read off s = x² + y² without taking the root: the host
-// precomputes, in the device's scalar type, the band of s whose correctly rounded square root equals the radius
-// (p[3] = min{s : √s >= r_in}, p[4] = min{s : √s > r_in}, p[5], p[6] likewise for r_out; disk_sqrt_band, rtgr_context.hip), so
-//     sign(r_in − RN(√s)) = +1 for s < p[3], 0 for p[3] <= s < p[4], −1 otherwise
-// EXACTLY — same sign, zero included, as obj_distance computes with its IEEE square root, for every s (√ is monotone and
-// correctly rounded).  Nine IEEE roots (~16 instructions each) per accepted NEAR step become compares and selects; the true
-// distance is still what the event root-finder (resolve_kernel) and the colouring see.
-template <class R>
-RTGR_DEV R disk_sign_distance(const DevObject<R>& o, R px, R py, R pz) {
-    const R s = rfma(px, px, py * py);
-    const R e_in = s < o.p[3] ? R(1) : (s < o.p[4] ? R(0) : R(-1));     // sign(r_in − ϱ)
-    const R e_out = s < o.p[5] ? R(-1) : (s < o.p[6] ? R(0) : R(1));    // sign(ϱ − r_out)
-    return rmax(rmax(rabs(pz) - o.p[0], e_in), e_out);
-}
-
-// … and as the FAR pass's reach bound needs it: its magnitude, to ~1e-16 relative (the bound carries a 1e-6 guard), from
-// the 6-instruction reciprocal square root instead of the IEEE expansion.
-template <class R>
-RTGR_DEV R disk_distance_fast(const DevObject<R>& o, R px, R py, R pz) {
-    const R s = rfma(px, px, py * py);
-    const R rc = s > R(0) ? s * frsq<R>(s) : R(0);
-    return rmax(rmax(rabs(pz) - o.p[0], o.p[1] - rc), rc - o.p[2]);
-}
-
-// The object list in order — f(object, index) —, as `for obj in objs` walks the reference's Vector (:434, :520): the first
-// RTGR_MAX_OBJECTS objects from the kernels' argument block (a wave-uniform index into the kernarg segment: scalar loads), the
-// rest of a longer list from the scene's device table (DevScene::more; the same wave-uniform walk over global memory).  The second
-// loop is cold code for every scene of up to RTGR_MAX_OBJECTS objects: never entered, and outside the hot loop's instruction
-// stream.
-template <class R, class F>
-RTGR_DEV void for_each_object(const DevScene<R>& sc, F&& f) {
-    const uint32_t n0 = sc.nobj < (uint32_t)RTGR_MAX_OBJECTS ? sc.nobj : (uint32_t)RTGR_MAX_OBJECTS;
-    for (uint32_t o = 0; o < n0; o++) f(sc.obj[o], o);
-#ifndef RTGR_INLINE_OBJECTS_ONLY   // (A/B builds: the loop as it was before lists could be longer — tools/launch_ab.py builds)
-    if (__builtin_expect(sc.nobj > (uint32_t)RTGR_MAX_OBJECTS, 0)) {   // (laid out of line: 0.4-0.7 % of the 4096² frame when it sat in the hot loop's stream)
-        // The table is read-only for the kernel's lifetime and walked with a wave-uniform index: through the CONSTANT address space
-        // its loads are scalar loads (s_load, the scalar cache — what the kernarg-resident objects get), not vector loads of one
-        // address by 64 lanes with a vector-memory round trip ahead of every object's arithmetic (measured at 64 objects, 2048²:
-        // the table walked with global_load cost the frame 3 x what its instruction count explains — DESIGN.md §4.7).
-        typedef const DevObject<R> __attribute__((address_space(4))) * ConstTable;
-        const ConstTable more = (ConstTable)(unsigned long long)sc.more;
-        for (uint32_t o = (uint32_t)RTGR_MAX_OBJECTS; o < sc.nobj; o++)
-            f(*(const DevObject<R>*)(more + (o - (uint32_t)RTGR_MAX_OBJECTS)), o);
-    }
-#endif
-}
-// The same walk with the spheres — objects [0, nsph) of the regrouped list (DevScene) — handed to a function of their own:
-// fs(sphere, position) needs no dispatch on the kind, fo(object, position) is the general one.  For consumers that do not care
-// about the order (the reach test's conjunction, the minima of the sample-point scan).
-template <class R, class FS, class FO>
-RTGR_DEV void for_each_by_kind(const DevScene<R>& sc, FS&& fs, FO&& fo) {
-    const uint32_t n0 = sc.nobj < (uint32_t)RTGR_MAX_OBJECTS ? sc.nobj : (uint32_t)RTGR_MAX_OBJECTS;
-    const uint32_t s0 = sc.nsph < n0 ? sc.nsph : n0;
-    for (uint32_t o = 0; o < s0; o++) fs(sc.obj[o], o);
-    for (uint32_t o = s0; o < n0; o++) fo(sc.obj[o], o);
-#ifndef RTGR_INLINE_OBJECTS_ONLY
-    if (__builtin_expect(sc.nobj > (uint32_t)RTGR_MAX_OBJECTS, 0)) {
-        typedef const DevObject<R> __attribute__((address_space(4))) * ConstTable;
-        const ConstTable more = (ConstTable)(unsigned long long)sc.more;
-        const uint32_t s1 = sc.nsph < sc.nobj ? sc.nsph : sc.nobj;
-        for (uint32_t o = (uint32_t)RTGR_MAX_OBJECTS; o < s1; o++) fs(*(const DevObject<R>*)(more + (o - (uint32_t)RTGR_MAX_OBJECTS)), o);
-        for (uint32_t o = s1 > (uint32_t)RTGR_MAX_OBJECTS ? s1 : (uint32_t)RTGR_MAX_OBJECTS; o < sc.nobj; o++)
-            fo(*(const DevObject<R>*)(more + (o - (uint32_t)RTGR_MAX_OBJECTS)), o);
-    }
-#endif
-}
-// The sample-point scan's walk (rtgr_persistent.hpp): the objects whose bit — bit (position >> shift) — is set in `mask`, spheres to fs,
-// the other kinds to fo.  A list in the argument block is walked object by object with the bit tested on the way (the hot loop's
-// stream); a longer one BY THE SET BITS, through the device table: the scan of a step that can meet three of 100000 objects is not
-// a walk over 100000 bits.
-template <class R, class FS, class FO>
-RTGR_DEV void for_each_masked_by_kind(const DevScene<R>& sc, unsigned long long mask, uint32_t shift, FS&& fs, FO&& fo) {
-#ifndef RTGR_INLINE_OBJECTS_ONLY
-    if (__builtin_expect(sc.nobj > (uint32_t)RTGR_MAX_OBJECTS, 0)) {
-        typedef const DevObject<R> __attribute__((address_space(4))) * ConstTable;
-        const ConstTable table = (ConstTable)(unsigned long long)(sc.more - (uint32_t)RTGR_MAX_OBJECTS);
-        unsigned long long m = mask;
-        while (m != 0ull) {
-            const uint32_t b = (uint32_t)__builtin_ctzll(m);
-            m &= m - 1ull;
-            const uint32_t o0 = b << shift;
-            uint32_t o1 = o0 + (1u << shift);
-            o1 = o1 < sc.nobj ? o1 : sc.nobj;
-            for (uint32_t o = o0; o < o1; o++) {
-                if (o < sc.nsph) fs(*(const DevObject<R>*)(table + o), o);
-                else fo(*(const DevObject<R>*)(table + o), o);
-            }
-        }
-        return;
-    }
-#endif
-    const uint32_t n0 = sc.nobj < (uint32_t)RTGR_MAX_OBJECTS ? sc.nobj : (uint32_t)RTGR_MAX_OBJECTS;   // (such a list has one bit per object: shift = 0)
-    const uint32_t s0 = sc.nsph < n0 ? sc.nsph : n0;
-    for (uint32_t o = 0; o < s0; o++) if ((mask >> o) & 1ull) fs(sc.obj[o], o);
-    for (uint32_t o = s0; o < n0; o++) if ((mask >> o) & 1ull) fo(sc.obj[o], o);
-}
-// The reach test's walk (rtgr_persistent.hpp): as for_each_by_kind, but a list with GROUPS (DevScene, rtgr_args.hpp) is walked group
-// by group — fg(group, level) -> wave-uniform "some lane cannot rule this group out"; only then its members are handed to fs.  With a
-// second level (nsuper > 0) the runs of groups are asked first (level 1), their groups (level 0) only when a run is not ruled out.  The
-// whole walk of a grouped list reads the device table (scalar loads through the constant address space, as above) and is cold code for
-// every list without groups.
-template <class R, class FG, class FS, class FO>
-RTGR_DEV void for_each_within_reach(const DevScene<R>& sc, FG&& fg, FS&& fs, FO&& fo) {
-#ifndef RTGR_INLINE_OBJECTS_ONLY
-    if (__builtin_expect(sc.ngroups != 0u, 0)) {
-        typedef const DevObject<R> __attribute__((address_space(4))) * ConstTable;
-        const ConstTable table = (ConstTable)(unsigned long long)(sc.more - (uint32_t)RTGR_MAX_OBJECTS);
-        const ConstTable groups = table + sc.nobj;
-        const ConstTable supers = groups + sc.ngroups;
-        for (uint32_t o = 0; o < sc.nloose; o++) fs(*(const DevObject<R>*)(table + o), o);
-        const uint32_t runs = sc.nsuper != 0u ? sc.nsuper : 1u;
-        for (uint32_t s = 0; s < runs; s++) {
-            uint32_t g0 = 0u, g1 = sc.ngroups;
-            if (sc.nsuper != 0u) {
-                const DevObject<R>& S = *(const DevObject<R>*)(supers + s);
-                if (!fg(S, 1)) continue;
-                g0 = S.type;
-                g1 = S.type + S.orig;
-            }
-            for (uint32_t g = g0; g < g1; g++) {
-                const DevObject<R>& G = *(const DevObject<R>*)(groups + g);
-                if (fg(G, 0)) {
-                    const uint32_t o1 = G.type + G.orig;
-                    for (uint32_t o = G.type; o < o1; o++) fs(*(const DevObject<R>*)(table + o), o);
-                }
-            }
-        }
-        for (uint32_t o = sc.nsph; o < sc.nobj; o++) fo(*(const DevObject<R>*)(table + o), o);
-        return;
-    }
-#endif
-    for_each_by_kind<R>(sc, fs, fo);
-}
-// A SAMPLE of a grouped list (ngroups > 0): the loose spheres, ONE member of every group (of every run of groups, where there are
-// runs), the other kinds — f(object, position).
-template <class R, class F>
-RTGR_DEV void for_each_sample(const DevScene<R>& sc, F&& f) {
-    typedef const DevObject<R> __attribute__((address_space(4))) * ConstTable;
-    const ConstTable table = (ConstTable)(unsigned long long)(sc.more - (uint32_t)RTGR_MAX_OBJECTS);
-    const ConstTable groups = table + sc.nobj;
-    for (uint32_t o = 0; o < sc.nloose; o++) f(*(const DevObject<R>*)(table + o), o);
-    if (sc.nsuper != 0u) {   // (with a second level: one member of every RUN of groups — the bound only has to be a bound)
-        const ConstTable supers = groups + sc.ngroups;
-        for (uint32_t s = 0; s < sc.nsuper; s++) {
-            const uint32_t g = ((const DevObject<R>*)(supers + s))->type;
-            const uint32_t o = ((const DevObject<R>*)(groups + g))->type;
-            f(*(const DevObject<R>*)(table + o), o);
-        }
-    } else {
-        for (uint32_t g = 0; g < sc.ngroups; g++) {
-            const uint32_t o = ((const DevObject<R>*)(groups + g))->type;
-            f(*(const DevObject<R>*)(table + o), o);
-        }
-    }
-    for (uint32_t o = sc.nsph; o < sc.nobj; o++) f(*(const DevObject<R>*)(table + o), o);
-}
-// … and one object by (per-lane) POSITION in the regrouped list
-template <class R>
-RTGR_DEV const DevObject<R>& object_at(const DevScene<R>& sc, uint32_t o) {
-    return o < (uint32_t)RTGR_MAX_OBJECTS ? sc.obj[o] : sc.more[o - (uint32_t)RTGR_MAX_OBJECTS];
-}
-
-// A SELECTION of the list's objects (the resolve kernel, rtgr_persistent.hpp: select_objects): bit o >> shift of the mask says
-// whether object o (position in the device list) takes part.  Only ever used to leave out objects that provably cannot be the minimum.
-struct ObjSel {
-    unsigned long long mask;
-    uint32_t shift;
-    // lists beyond 64 objects (a bit is 2, 4, … 2048 neighbours): the selected positions themselves, entry k in lane k of `list`
-    // (read with v_readlane, which ignores EXEC), `count` of them; count > 64: too many, walk the mask's blocks
-    uint32_t list;
-    uint32_t count;
-    RTGR_DEV bool has(uint32_t o) const { return ((mask >> (o >> shift)) & 1ull) != 0ull; }
-    RTGR_DEV void add(uint32_t o) {   // wave-uniform o
-        mask |= 1ull << (o >> shift);
-        if (shift != 0u) {
-            if (count < 64u) list = ((threadIdx.x & 63u) == count) ? o : list;   // (called with every lane of the wave active: select_objects)
-            count++;
-        }
-    }
-};
-RTGR_DEV uint32_t objsel_shift(uint32_t nobj) {   // the smallest shift with (nobj − 1) >> shift <= 63
-    return nobj > 64u ? 32u - (uint32_t)__builtin_clz((nobj - 1u) >> 6) : 0u;
-}
-
-// The objects of a selection, in list order — f(object, position) —, found by the mask's set bits (a list of 1024 objects is not walked
-// to find the three that are selected).  Lists beyond the argument block only: the device table holds the whole list.
-template <class R, class F>
-RTGR_DEV void for_each_selected(const DevScene<R>& sc, ObjSel sel, F&& f) {
-    typedef const DevObject<R> __attribute__((address_space(4))) * ConstTable;
-    const ConstTable table = (ConstTable)(unsigned long long)(sc.more - (uint32_t)RTGR_MAX_OBJECTS);
-    if (sel.shift != 0u && sel.count <= 64u) {   // by the list of positions
-        for (uint32_t k = 0; k < sel.count; k++) {
-            const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)sel.list, (int)k);
-            f(*(const DevObject<R>*)(table + o), o);
-        }
-        return;
-    }
-    unsigned long long m = sel.mask;
-    while (m != 0ull) {
-        const uint32_t b = (uint32_t)__builtin_ctzll(m);
-        m &= m - 1ull;
-        const uint32_t o0 = b << sel.shift;
-        uint32_t o1 = o0 + (1u << sel.shift);
-        o1 = o1 < sc.nobj ? o1 : sc.nobj;
-        for (uint32_t o = o0; o < o1; o++) f(*(const DevObject<R>*)(table + o), o);
-    }
-}
-
-template <class R, bool SEL = false>
-RTGR_DEV R min_distance(const DevScene<R>& sc, const R pos[4], ObjSel sel = ObjSel{}) {   // :433-441
-    R dmin = R(__builtin_huge_val());
-    auto fold = [&](const DevObject<R>& ob, uint32_t) {
-        const R d = obj_distance<R>(ob, pos);
-        dmin = (d < dmin || d != d) ? d : dmin;
-    };
-    if constexpr (SEL) for_each_selected<R>(sc, sel, fold);
-    else for_each_object<R>(sc, fold);
-    return dmin;
+// the wave-uniform metric constants of an instantiation (the grid's descriptor only where the grid RHS reads it)
+template <class R, int METRIC>
+RTGR_DEV MetricK<R> scene_consts(const DevScene<R>& sc) {
+    MetricK<R> k = metric_consts<R>(sc.M, sc.a);
+    Sampled<R, METRIC>::fill(k, sc);
+    return k;
 }
 
 }  // namespace rtgr

@@ -1,4 +1,4 @@
-// rtgr_pipeline.hpp — host side of the trace pipeline: launch policy and the per-chunk kernel sequence
+// rtgr_pipeline.hpp — host side of the trace pipeline (no kernel is defined here): launch policy and the per-chunk kernel sequence
 //     reset -> prepare (camera ray, queue key, u̇(y0), initial dt) -> [order scan/scatter] -> integrate<FAR> -> integrate<NEAR>
 //     -> resolve
 // as templates over (scalar, metric variant, spin).  Each tu_*.hip instantiates the variants of its group, so the
@@ -8,7 +8,7 @@
 //   waves_per_cu       resident waves per CU of the integrate kernel (auto = 4 x the instantiation's waves/SIMD)
 //   chunk              rays per pipeline chunk (auto 2^26, less if memory is short); bounds the workspace
 //   split = 0          one FULL integrate pass instead of the FAR + NEAR pair
-//   order = 0 / 1      natural ray order / longest-expected-first (rtgr_persistent.hpp); auto: ordered, except Float32 above 2 M rays
+//   order = 0 / 1      natural ray order / longest-expected-first (rtgr_prepare.hpp); auto: ordered, except Float32 above 2 M rays
 //   fair = s           time slice 2^s clocks of the priority rotation (0 = off; auto 13 for 0.8-1.8 M rays, else off)
 //   near_early = n     accepted steps at hand-over below which a ray is put on the NEAR pass's early list (64)
 //   waves_per_cu_near  resident waves per CU of the NEAR pass (auto 4 below 2.4 M rays — 6.3 M with spin —, else all)
@@ -17,7 +17,10 @@
 //   packfar = 1        Float32 experiment: packed scan-free FAR pass (3 waves/SIMD) + scalar NEAR pass instead of the one FULL pass
 #pragma once
 #include "rtgr_host.hpp"
-#include "rtgr_persistent.hpp"
+#include "rtgr_tile.hpp"
+#include "rtgr_integrate.hpp"
+#include "rtgr_prepare.hpp"
+#include "rtgr_resolve.hpp"
 #include "rtgr_packed_f32.hpp"
 
 namespace rtgr {
@@ -25,63 +28,6 @@ namespace rtgr {
 #ifndef RTGR_F32_SPLIT_FROM
 #define RTGR_F32_SPLIT_FROM 32
 #endif
-
-// One lane = one ray.  A wave owns an 8x8 pixel tile (lock-step efficiency 0.90 vs 0.45 for 64 consecutive
-// pixels); a 256-thread workgroup owns 4 horizontally adjacent tiles.  The simple variant (knob tile = 1):
-// whole adaptive loop + event finder + colouring inline — an independent formulation kept for A/B and cross-checks.
-template <class R, int METRIC, bool SPIN>
-__global__ __launch_bounds__(256) void trace_kernel(const TraceArgs<R> A) {
-    const uint64_t tiles_i = (A.ni + 7) >> 3;
-    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t ti = wave % tiles_i, tj = wave / tiles_i;
-    const uint64_t i = ti * 8 + (lane & 7), jl = tj * 8 + (lane >> 3);
-    const bool valid = (i < A.ni) && (jl < A.nrows);
-    const uint64_t n = A.ni * A.nrows;
-    const uint64_t idx = i + jl * A.ni;
-
-    RayStats st{0, 0, 0, 0, 0};
-    bool ev = false;
-    if (valid) {
-        R s0[8], se[8], lam, col[3];
-        if (A.state0) {
-#pragma unroll
-            for (int c = 0; c < 8; c++) s0[c] = A.state0[idx * 8 + c];
-        } else {
-            make_pixel<R>(A.sc, A.cam, A.ni, A.nj, i, A.j0 + jl * A.jstride, s0);
-        }
-        st = integrate_ray<R, METRIC, SPIN>(A.sc, A.opt, s0, se, lam);
-        const uint32_t hit = colour_pixel<R>(A.sc, A.opt, se, col);
-        A.rgb[idx] = col[0];
-        A.rgb[n + idx] = col[1];
-        A.rgb[2 * n + idx] = col[2];
-        if (A.state_end) {
-#pragma unroll
-            for (int c = 0; c < 8; c++) A.state_end[idx * 8 + c] = se[c];
-        }
-        if (A.lambda_end) A.lambda_end[idx] = lam;
-        if (A.status) A.status[idx] = st.status;
-        if (A.hit) A.hit[idx] = (uint8_t)hit;
-        if (A.hit32) A.hit32[idx] = hit;
-        if (A.n_accept) A.n_accept[idx] = st.nacc;
-        if (A.n_reject) A.n_reject[idx] = st.nrej;
-        ev = (st.status == RTGR_RAY_EVENT);
-    }
-    if (A.counters) {
-        const unsigned long long c0 = wave_sum(valid ? 1ull : 0ull), c1 = wave_sum(st.nacc), c2 = wave_sum(st.nrej),
-                                 c3 = wave_sum(st.nrhs), c4 = wave_sum(ev ? 1ull : 0ull),
-                                 c5 = wave_sum(st.interior), c6 = wave_sum((valid && st.status >= RTGR_RAY_MAXSTEPS) ? 1ull : 0ull);
-        if (lane == 0) {
-            atomicAdd(&A.counters[0], c0);
-            atomicAdd(&A.counters[1], c1);
-            atomicAdd(&A.counters[2], c2);
-            atomicAdd(&A.counters[3], c3);
-            atomicAdd(&A.counters[4], c4);
-            atomicAdd(&A.counters[5], c5);
-            atomicAdd(&A.counters[6], c6);
-        }
-    }
-}
 
 template <class R, int METRIC, bool SPIN>
 static int launch_integrate(LaunchEnv& E, const IntegrateArgs<R>& IA, bool npts10, bool split, uint64_t waves, hipStream_t st) {
@@ -269,7 +215,7 @@ static int launch_trace(LaunchEnv& E, const TraceArgs<R>& A, hipStream_t st) {
     for (uint64_t off = 0; off < n; off += chunk) {
         const uint64_t m = (n - off) < chunk ? (n - off) : chunk;
         const R* s0 = A.state0 ? A.state0 + off * 8 : nullptr;  // null: prepare_kernel generates the camera rays
-        // longest-expected-first queue order: pays off when a lane gets few rays (see rtgr_persistent.hpp).  Float32 rays
+        // longest-expected-first queue order: pays off when a lane gets few rays (see rtgr_prepare.hpp).  Float32 rays
         // last ~20 steps, so above 2 M rays the order's own kernels and the scattered record traffic cost more than the
         // shorter tail returns (measured: 2048² a = 0.8 3.21 -> 2.98 ms, 4096² 12.4 -> 10.8 ms; 1024² a = 0 0.98 <- 1.56)
         const bool order_auto = sizeof(R) == 8 || m <= (1ull << 21);
@@ -284,7 +230,7 @@ static int launch_trace(LaunchEnv& E, const TraceArgs<R>& A, hipStream_t st) {
         IA.keys = use_order ? keys : nullptr; IA.hist = hist; IA.nan_flag = A.nan_flag;
         IA.early = early; IA.near_early = (uint32_t)(K.near_early < 0 ? 64 : K.near_early);  // 0: no early list
         if (IA.near_early == 0u) IA.early = nullptr;
-        // priority rotation among the waves of a SIMD: pays when a lane gets only a few rays (see rtgr_persistent.hpp)
+        // priority rotation among the waves of a SIMD: pays when a lane gets only a few rays (see rtgr_integrate.hpp)
         // measured FAR pass, off / on: 0.26 M rays 2.70 / 3.17 ms, 0.52 M 3.83 / 4.35, 1.05 M 7.05 / 6.29, 1.44 M 8.83 / 8.30,
         // 2.1 M 11.59 / 11.59, 16.8 M 83.8 / 84.8 -> on for 4..9 rays per lane of the 3-waves/SIMD grid
         IA.n_simd = (uint32_t)D.num_cu * 4u;

@@ -487,8 +487,8 @@ static int plan_unit(const char* source, int stationary, const rtgr_scene* built
 // records as rtgr_user_header_hash and load_module_image compares with the hash the library's own kernels were built from
 static int header_hash_of(const std::string& dir, unsigned long long* out) {
     uint64_t h = 1469598103934665603ull;
-    for (const char* f : {"rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_grid_interp.hpp", "rtgr_integrator.hpp", "rtgr_persistent.hpp", "rtgr_tsit5_tables.hpp",
-                          "../../include/rtgr.h"}) {
+    for (const char* f : {"rtgr_args.hpp", "rtgr_physics.hpp", "rtgr_grid_interp.hpp", "rtgr_objects.hpp", "rtgr_camera.hpp", "rtgr_tile.hpp", "rtgr_integrate.hpp",
+                          "rtgr_prepare.hpp", "rtgr_resolve.hpp", "rtgr_tsit5_tables.hpp", "../../include/rtgr.h"}) {
         std::vector<char> b;
         if (int rc = read_file(dir + "/" + f, b)) return rc;
         for (char ch : b) { h ^= (unsigned char)ch; h *= 1099511628211ull; }

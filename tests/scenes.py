@@ -83,7 +83,7 @@ def scene_variant(name, units=True, reach=True, jit=False):
 def circular_channels(hit, sc=None):
     """[3, n] bool: which RGB channels of a pixel carry a SAWTOOTH mod(·, 1)·omin/nobj and are therefore compared circularly.
     A sphere hit puts it on R and G (objcolor, src/RayTraceGR.jl:420-428: B is the constant 1), the thin disk (no reference
-    counterpart; rtgr_integrator.hpp colour_pixel) on G and B (R is the constant 1); a plane's colour is constant.  Without a
+    counterpart; rtgr_objects.hpp colour_pixel) on G and B (R is the constant 1); a plane's colour is constant.  Without a
     scene every hit is taken for a sphere.  (the helper used to wrap B for every object, which scored a real B error
     close to a multiple of omin/nobj on a sphere as ~0.)"""
     n = hit.shape[0]

@@ -1,7 +1,7 @@
 """Build-time checks on the generated gfx950 ISA (CPU only: hipcc cross-compiles without a GPU).
 
 The one-instruction min / max / clamp helpers of the hot loop are raw inline asm (rtgr_physics.hpp rmin / rmax / rmaxabs,
-rtgr_persistent.hpp fmax1 / fmin1).  LLVM's hazard recogniser treats inline asm as opaque, so a transcendental result
+fmax1 / fmin1).  LLVM's hazard recogniser treats inline asm as opaque, so a transcendental result
 (v_rcp / v_rsq / v_exp / v_log …) consumed by the very next VALU instruction would get no s_nop for the gfx940-family
 "trans use" hazard.  tools/isa_mix.py --hazards scans the final ISA of every integrate / prepare kernel for that
 adjacency; this test fails the suite when one appears."""

@@ -6,7 +6,7 @@ point scan (NEAR, FULL) / step-size controller / commit + bookkeeping / refill +
 How: the translation unit is compiled to a device object with full debug info (-g does not change the code: checked against the
 production object's loop, see --check), disassembled with llvm-objdump, and every instruction address of the kernel's hot loop
 (the span of its longest backward branch) is resolved with `llvm-symbolizer --inlines` to its inline stack.  The frame INSIDE
-integrate_body (rtgr_persistent.hpp) — the outermost one — gives the source line the instruction belongs to, whatever helper
+integrate_body (rtgr_integrate.hpp) — the outermost one — gives the source line the instruction belongs to, whatever helper
 (rfma, frsq, accel_*, fold_distances …) it was inlined from; lines map to blocks through the `// [budget: …]` markers that
 bracket the blocks in the source.  No code is changed for counting.
 
@@ -113,7 +113,7 @@ def main():
         sym = subprocess.run([os.path.join(LLVM, "llvm-symbolizer"), f"--obj={obj}", "--inlines", "--output-style=JSON"],
                              input=q, capture_output=True, text=True, check=True).stdout
         stacks = [json.loads(l) for l in sym.strip().split("\n") if l.strip()]
-    ranges = {os.path.basename(p): block_ranges(p) for p in (os.path.join(CSRC, "rtgr_persistent.hpp"), os.path.join(CSRC, "rtgr_packed_f32.hpp"))}
+    ranges = {os.path.basename(p): block_ranges(p) for p in (os.path.join(CSRC, "rtgr_integrate.hpp"), os.path.join(CSRC, "rtgr_packed_f32.hpp"))}
 
     def block_of(stack):
         # frames are innermost first; take the frame of the kernel BODY function (integrate_body / integrate2_body: the __global__
