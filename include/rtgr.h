@@ -433,6 +433,107 @@ int rtgr_trace_aa_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_sol
                       const rtgr_aa* aa, float* rgb, const rtgr_ray_outputs* out, uint8_t* refined, rtgr_counters* ctr,
                       rtgr_aa_stats* stats);
 
+/* ---- image textures for spheres, disks and escaping rays ------------------------------------------------------------------
+ * AN EXTENSION: the reference colours by fixed rules (a 24-band sawtooth on spheres, :427; constant green on planes; a hard miss
+ * colour, :528); nothing reads a picture.  A TEXTURE is an image the context keeps on its devices; a shaded trace is the plain trace
+ * followed by one shading kernel that overwrites the colour of the pixels whose object — or whose escape — has a texture bound.  No
+ * kernel of the trace itself changes, and a pixel that is not shaded keeps the plain frame's bits.
+ *
+ * Textures.  rtgr_texture_load takes `texels`: three planes of height*width doubles, column fastest, texels[(c*height + r)*width + q] —
+ * the layout of every `rgb` output of the library, so a traced ni x nj frame is a loadable width = ni, height = nj texture as it stands.
+ * RTGR_ERR_BAD_ARG: width or height outside 2 .. 16384, flags or pad non-zero, any non-finite texel (the index of the first one in
+ * rtgr_last_error()).  The texels are uploaded to every device of the context as a Float64 and a Float32 copy (the double rounded
+ * once; the _f32 entry points read the latter), each texel four scalars (r, g, b, 0) so that a corner is one aligned 32- / 16-byte
+ * load.  Texture ids come from a counter of their own and never coincide with grid ids or unit ids.  Lifetime as for grids:
+ * rtgr_texture_unload (id 0: every texture of the context) makes the id unknown at once — a later call naming it is RTGR_ERR_BAD_ARG —,
+ * the device memory is RETIRED and freed only by rtgr_trim / rtgr_destroy, so a hipGraph captured earlier may still replay it.
+ *
+ * The mapping and the sampler (one device function, csrc/rtgr_texture.hpp, in the entry point's scalar type; W = width, H = height).
+ *   From a 3-vector d (direction mapping):
+ *     theta = atan2(hypot(d_x, d_y), d_z)   (not acos: it is ill-conditioned at the poles),   phi = atan2(d_y, d_x),
+ *     s = (phi + pi) W / (2 pi) - 1/2,   v = theta H / pi - 1/2.
+ *     Column q has its centre at phi = -pi + (q + 1/2) 2 pi / W, row r at theta = (r + 1/2) pi / H.  These are the theta, phi of the
+ *     reference's objcolor(::Sphere) (:420-427).  A zero or non-finite d means "no sample": the pixel keeps its colour.
+ *   Disk mapping, from a position x with r_in and r_out of the disk: phi and s as above from (x, y);
+ *     v = (hypot(x, y) - r_in) / (r_out - r_in) H - 1/2   (a non-finite x, y or v: no sample).
+ *   RTGR_TEX_NEAREST:  column floor(s + 1/2) mod W, row clamp(floor(v + 1/2), 0, H - 1); the result is the texel's stored value, bit
+ *     for bit.
+ *   RTGR_TEX_BILINEAR: q0 = floor(s), f_x = s - q0, columns q0 mod W and (q0 + 1) mod W (the seam at phi = +-pi wraps); r0 = floor(v),
+ *     f_y = v - r0, rows clamp(r0, 0, H - 1) and clamp(r0 + 1, 0, H - 1) (clamped at the poles and rims, not reflected); per channel
+ *     a = t00 + f_x (t10 - t00), b = t01 + f_x (t11 - t01), result = a + f_y (b - a), no fused operation.  The form is written relative
+ *     to a corner, like the grid interpolant relative to its centre sample: a constant texture comes back to the bit.
+ *
+ * Shading, per pixel of the traced frame (rtgr_shade: nbind binds, at most RTGR_MAX_TEXTURE_BINDS; bind.object is the 1-based index
+ * in the caller's object list, 0 = rays that escape):
+ *   A hit on a bound object (hit32 == bind.object): the position is state_end[0..3]; for a Sphere of either radius sign d = x_end -
+ *     centre in the spatial components (so the inverted sky sphere `caelum` is covered); for a Disk the disk mapping.
+ *   A bound escape (bind.object == 0): hit32 == 0, status RTGR_RAY_LAMBDA1 or RTGR_RAY_OUTSIDE and the Euclidean |x_end| >= r_escape;
+ *     d is the spatial part of the end VELOCITY state_end[5..7] — the ray is traced backwards from the camera, so this is where on the
+ *     sky the light came from.  It is the coordinate direction, with no asymptotic correction.
+ *   Colour: the texel as sampled; the reference's omin / length(objs) dimming is not applied.
+ *   Every other pixel — unbound objects, planes, user objects, misses that did not escape, "no sample" — is not written.  A caller who
+ *     wants a black hole sets miss_rgb to black.
+ *
+ * rtgr_trace_shaded_device_*.  aa == NULL: a camera frame of the whole ni x nj canvas (as rtgr_trace_device_* with `cam`, j0 = 0,
+ * j1 = nj), then the shading kernel.  state_end, hit32 and status go to the caller's arrays where `out` asks for them, otherwise to a
+ * grow-only scratch of the stream, retired like the workspace; `out` describes the plain ray and is never changed by shading;
+ * d_refined and stats must be NULL.  The call only enqueues — unless `ctr` (host) is given: then it synchronises `stream` once at its
+ * end to copy the counters out.  With ctr == NULL it may be captured once the workspace and the scratch are large enough (a call of
+ * the same size before the capture makes them so); growth during capture is RTGR_ERR_BAD_ARG, like workspace growth.
+ *   aa != NULL: adaptive anti-aliasing (above) of the SHADED frame: pass 1 is the shaded plain frame, the edge rule reads the shaded
+ * colours, the sub-rays of pass 2 are traced with their end states and shaded before the reduction (8 + 11 scalars + 5 bytes of batch
+ * scratch per sub-ray).  So uniform == the box filter of the shaded (k ni) x (k nj) frame, adaptive == where(refined, uniform, shaded
+ * plain), bit for bit.  The rules of rtgr_trace_aa_device_* for ctr, stats, d_refined, streams and capture apply.
+ *   rtgr_trace_shaded_f64 / _f32 (host pointers) run the same on device 0 of the context and copy out, as rtgr_trace_aa_* do.
+ *   RTGR_ERR_BAD_ARG (with a message): a null shade or cam, flags != 0, nbind > RTGR_MAX_TEXTURE_BINDS, an unknown texture id or
+ * filter, object > nobj, an object (or the escape) bound twice, a bind to a Plane or a user object, a NaN or negative r_escape, and
+ * the anti-aliasing refusals.  nbind == 0 is legal: the frame is the plain frame, bit for bit.
+ *   In scope: every metric (RTGR_USER when aa == NULL, both grid kinds), object lists of any length, both scalar types.
+ *   Out of scope: the sharded, frames-in-flight, pixel-array and single-ray entry points; mip-mapping or any minification filter
+ * (anti-aliasing is the answer to minification); pole-aware bilinear; planes and user objects; emission or redshift weighting of the
+ * texel; several devices for one shaded frame.
+ *
+ * rtgr_eval_texture_*: the sampler at n points on device 0 (host pointers) — p: n x 3 (d, or a position whose x, y are read when
+ * disk_range = {r_in, r_out} is given; NULL: the direction mapping); rgb: n x 3 (AoS), read and written: a "no sample" point keeps
+ * what the caller put there. */
+enum rtgr_tex_filter { RTGR_TEX_NEAREST = 0, RTGR_TEX_BILINEAR = 1 };
+#define RTGR_MAX_TEXTURE_BINDS 16
+#define RTGR_TEXTURE_MAX_SIDE 16384
+typedef struct rtgr_texture_desc {
+    uint32_t width, height; /* 2 .. RTGR_TEXTURE_MAX_SIDE */
+    uint32_t flags;         /* 0 */
+    uint32_t pad;           /* 0 */
+} rtgr_texture_desc;        /* 16 bytes: width 0, height 4, flags 8, pad 12 */
+typedef struct rtgr_texture_bind {
+    uint32_t object;        /* 1-based index in the caller's object list; 0 = rays that escape */
+    uint32_t filter;        /* rtgr_tex_filter */
+    uint64_t texture;       /* id from rtgr_texture_load */
+} rtgr_texture_bind;        /* 16 bytes: object 0, filter 4, texture 8 */
+typedef struct rtgr_shade {
+    uint32_t nbind;         /* 0 .. RTGR_MAX_TEXTURE_BINDS */
+    uint32_t flags;         /* 0 */
+    const rtgr_texture_bind* bind; /* nbind binds (host memory; may be NULL when nbind == 0) */
+    double r_escape;        /* a miss counts as escaped when the Euclidean |x_end| >= r_escape; >= 0 */
+} rtgr_shade;               /* 24 bytes: nbind 0, flags 4, bind 8, r_escape 16 */
+int rtgr_texture_load(rtgr_context* ctx, const rtgr_texture_desc* desc, const double* texels, uint64_t* id_out);
+int rtgr_texture_unload(rtgr_context* ctx, uint64_t id); /* id 0: all */
+int rtgr_trace_shaded_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                                 uint64_t nj, const rtgr_shade* shade, const rtgr_aa* aa, double* d_rgb, const rtgr_ray_outputs* out,
+                                 uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
+int rtgr_trace_shaded_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                                 uint64_t nj, const rtgr_shade* shade, const rtgr_aa* aa, float* d_rgb, const rtgr_ray_outputs* out,
+                                 uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
+int rtgr_trace_shaded_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                          uint64_t nj, const rtgr_shade* shade, const rtgr_aa* aa, double* rgb, const rtgr_ray_outputs* out,
+                          uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats);
+int rtgr_trace_shaded_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                          uint64_t nj, const rtgr_shade* shade, const rtgr_aa* aa, float* rgb, const rtgr_ray_outputs* out,
+                          uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats);
+int rtgr_eval_texture_f64(rtgr_context* ctx, uint64_t texture, uint32_t filter, const double* p /* n x 3 */, uint64_t n,
+                          const double* disk_range /* NULL, or {r_in, r_out} */, double* rgb /* n x 3 */);
+int rtgr_eval_texture_f32(rtgr_context* ctx, uint64_t texture, uint32_t filter, const float* p /* n x 3 */, uint64_t n,
+                          const float* disk_range /* NULL, or {r_in, r_out} */, float* rgb /* n x 3 */);
+
 /* ---- camera: make_canvas (src/RayTraceGR.jl:457-478) on the device ------------------------------------------
  * Writes n x 8 ray states (pos, null past-directed 4-velocity) for rows [j0, j1).  Device / host variants. */
 int rtgr_make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni,

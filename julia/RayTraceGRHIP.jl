@@ -27,6 +27,9 @@
 #   RtgrGrid4        80   n 0, origin 16, spacing 48
 #   RtgrAA           24   k 0, flags 4, contrast 8, max_batch_rays 16
 #   RtgrAAStats      32   pixels 0, refined 8, sub_rays 16, batches 24
+#   RtgrTextureDesc  16   width 0, height 4, flags 8, pad 12
+#   RtgrTextureBind  16   object 0, filter 4, texture 8
+#   RtgrShade        24   nbind 0, flags 4, bind 8, r_escape 16
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64          (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -106,6 +109,23 @@ end
 struct RtgrAAStats
     pixels::UInt64; refined::UInt64; sub_rays::UInt64; batches::UInt64
 end
+struct RtgrTextureDesc         # an image texture (rtgr_texture_load): three planes of height x width doubles, column fastest
+    width::UInt32               # 2 .. 16384
+    height::UInt32
+    flags::UInt32               # 0
+    pad::UInt32                 # 0
+end
+struct RtgrTextureBind         # one texture bound to one object of the list — or to the rays that escape
+    object::UInt32              # 1-based index in `objs` (what `hit` holds); 0 = rays that escape
+    filter::UInt32              # RTGR_TEX_NEAREST / RTGR_TEX_BILINEAR
+    texture::UInt64             # id from load_texture
+end
+struct RtgrShade               # the binds of a shaded frame (rtgr_trace_shaded_f64 / _f32)
+    nbind::UInt32               # 0 .. 16
+    flags::UInt32               # 0
+    bind::Ptr{RtgrTextureBind}
+    r_escape::Float64           # a miss counts as escaped when the Euclidean |x_end| >= r_escape
+end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
     lambda_end::Ptr{Cvoid}
@@ -134,6 +154,8 @@ const RTGR_RAY_MAXSTEPS = UInt8(2)
 const RTGR_RAY_DTMIN = UInt8(3)
 const RTGR_RAY_NAN = UInt8(4)
 const RTGR_RAY_OUTSIDE = UInt8(5)
+const RTGR_TEX_NEAREST = UInt32(0)
+const RTGR_TEX_BILINEAR = UInt32(1)
 
 function check(rc)
     rc < 0 && error("librtgr_hip: ", unsafe_string(ccall((:rtgr_last_error, librtgr), Cstring, ())))
@@ -707,6 +729,64 @@ function trace_rays_aa(metric, objs, pos, widthx, widthy, normal, ni::Integer, n
         end
     end
     (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), refined, stats[]
+end
+
+"""
+    load_texture(planes; ctx = nothing) -> UInt64
+
+An IMAGE TEXTURE for `trace_rays_shaded` (`rtgr_texture_load`; include/rtgr.h "image textures"): `planes` is a `width x height x 3`
+array — the three colour planes, column fastest, which is the layout `render` returns its frame in: a rendered `ni x nj` frame is a
+texture as it stands.  Every texel must be finite, `width` and `height` 2 .. 16384.  Uploaded to every device of `ctx`; the id never
+coincides with a grid's or a unit's.  `unload_texture(id; ctx)` releases the id (`rtgr_texture_unload`; 0: every texture).
+"""
+function load_texture(planes; ctx = nothing)
+    size(planes, 3) == 3 || error("load_texture: planes must be width x height x 3")
+    t = Array{Float64,3}(planes)
+    desc = Ref(RtgrTextureDesc(UInt32(size(t, 1)), UInt32(size(t, 2)), UInt32(0), UInt32(0)))
+    id = Ref{UInt64}(0)
+    check(ccall((:rtgr_texture_load, librtgr), Cint, (Ctx, Ptr{RtgrTextureDesc}, Ptr{Float64}, Ptr{UInt64}), handle(ctx), desc, t, id))
+    id[]
+end
+function unload_texture(id; ctx = nothing)
+    check(ccall((:rtgr_texture_unload, librtgr), Cint, (Ctx, UInt64), handle(ctx), id))
+    nothing
+end
+
+"""
+    trace_rays_shaded(metric, objs, pos, widthx, widthy, normal, ni, nj; textures = (), r_escape = 0.0, T = Float64, ctx = nothing)
+        -> (R, G, B)
+
+A frame with IMAGE TEXTURES (`rtgr_trace_shaded_f64/_f32`) — an extension: the reference colours by fixed rules (`objcolor`, :420-427;
+the miss colour, :528).  This is `render`'s frame with the pixels whose object — or whose escape — has a texture bound coloured by the
+texel instead; every other pixel keeps `render`'s bits.  `textures` is a collection of `(object, id, filter)`: `object` the 1-based
+index in `objs` (a `Sphere` of either radius sign — the sky `caelum` — or a `Disk`), or 0 for the rays that end without a hit at
+`|x| >= r_escape`, which are coloured by the direction they end with; `id` from `load_texture`; `filter` `RTGR_TEX_NEAREST` or
+`RTGR_TEX_BILINEAR`.  Runs on device 0 of `ctx`.
+"""
+function trace_rays_shaded(metric, objs, pos, widthx, widthy, normal, ni::Integer, nj::Integer;
+                           textures = (), r_escape::Real = 0.0, T::Type = Float64, ctx = nothing)
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("trace_rays_shaded has no CPU counterpart in the reference: ", why)
+    opt = solver_of(T)
+    cam = camera_of(pos, widthx, widthy, normal)
+    binds = RtgrTextureBind[RtgrTextureBind(UInt32(b[1]), UInt32(b[3]), UInt64(b[2])) for b in textures]
+    rgb = Array{T}(undef, ni, nj, 3)                # plane-major: rgb[:, :, c] is plane c
+    ctr = Ref{RtgrCounters}()
+    GC.@preserve rgb binds begin
+        shade = Ref(RtgrShade(UInt32(length(binds)), UInt32(0), pointer(binds), Float64(r_escape)))
+        if T === Float64
+            check(ccall((:rtgr_trace_shaded_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrCamera}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrAA}, Ptr{Float64},
+                         Ptr{RtgrRayOutputs}, Ptr{UInt8}, Ptr{RtgrCounters}, Ptr{RtgrAAStats}),
+                        handle(ctx), scene, opt, cam, ni, nj, shade, C_NULL, pointer(rgb), C_NULL, C_NULL, ctr, C_NULL))
+        else
+            check(ccall((:rtgr_trace_shaded_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrCamera}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrAA}, Ptr{Float32},
+                         Ptr{RtgrRayOutputs}, Ptr{UInt8}, Ptr{RtgrCounters}, Ptr{RtgrAAStats}),
+                        handle(ctx), scene, opt, cam, ni, nj, shade, C_NULL, pointer(rgb), C_NULL, C_NULL, ctr, C_NULL))
+        end
+    end
+    (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3])
 end
 
 """

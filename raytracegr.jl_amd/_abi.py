@@ -13,6 +13,8 @@ RTGR_ABI_VERSION = 4
 RTGR_MAX_DEVICES = 16
 RTGR_MAX_SOURCES = 16
 RTGR_GRID_MAX_SAMPLES = 1 << 28  # n[0]*n[1]*n[2] (4-D: n[0]*n[1]*n[2]*n[3]) of a grid metric at most
+RTGR_MAX_TEXTURE_BINDS = 16      # binds of one rtgr_shade
+RTGR_TEXTURE_MAX_SIDE = 16384    # width and height of a texture: 2 .. this
 
 # enum rtgr_metric
 MINKOWSKI, KS_REF, KS_TRUE, USER, GRID = 0, 1, 2, 3, 4
@@ -21,6 +23,8 @@ METRIC_GENERIC = 0x100  # RTGR_METRIC_GENERIC flag
 PLANE, SPHERE, DISK, USER_OBJECT = 1, 2, 3, 4
 # enum rtgr_ray_status
 RAY_EVENT, RAY_LAMBDA1, RAY_MAXSTEPS, RAY_DTMIN, RAY_NAN, RAY_OUTSIDE = 0, 1, 2, 3, 4, 5
+# enum rtgr_tex_filter
+TEX_NEAREST, TEX_BILINEAR = 0, 1
 # enum rtgr_status
 OK, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NAN_INPUT, ERR_NOT_INIT = 0, -1, -2, -3, -4, -5
 
@@ -93,6 +97,20 @@ class rtgr_aa_stats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class rtgr_texture_desc(C.Structure):
+    """an image texture (rtgr_texture_load): three planes of height x width doubles, column fastest"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class rtgr_texture_bind(C.Structure):
+    """object: 1-based index in the caller's list, 0 = rays that escape"""
+    _fields_ = [("object", C.c_uint32), ("filter", C.c_uint32), ("texture", C.c_uint64)]
+
+
+class rtgr_shade(C.Structure):
+    _fields_ = [("nbind", C.c_uint32), ("flags", C.c_uint32), ("bind", C.POINTER(rtgr_texture_bind)), ("r_escape", C.c_double)]
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -116,6 +134,8 @@ EXPORTS = [
     "rtgr_trace_frames_f64", "rtgr_trace_frames_f32", "rtgr_trace_frames_pixels_f64", "rtgr_trace_frames_pixels_f32",
     "rtgr_grid_metric_load", "rtgr_grid_metric_unload", "rtgr_grid4_metric_load",
     "rtgr_trace_aa_device_f64", "rtgr_trace_aa_device_f32", "rtgr_trace_aa_f64", "rtgr_trace_aa_f32",
+    "rtgr_texture_load", "rtgr_texture_unload", "rtgr_trace_shaded_device_f64", "rtgr_trace_shaded_device_f32", "rtgr_trace_shaded_f64",
+    "rtgr_trace_shaded_f32", "rtgr_eval_texture_f64", "rtgr_eval_texture_f32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -185,6 +205,15 @@ def _declare(lib):
         getattr(lib, f"rtgr_trace_aa_{suf}").argtypes = [
             ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_camera), u64, u64, P(rtgr_aa), vp, P(rtgr_ray_outputs), vp, P(rtgr_counters),
             P(rtgr_aa_stats)]
+        getattr(lib, f"rtgr_trace_shaded_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_camera), u64, u64, P(rtgr_shade), P(rtgr_aa), vp, P(rtgr_ray_outputs), vp,
+            P(rtgr_counters), P(rtgr_aa_stats), vp]
+        getattr(lib, f"rtgr_trace_shaded_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_camera), u64, u64, P(rtgr_shade), P(rtgr_aa), vp, P(rtgr_ray_outputs), vp,
+            P(rtgr_counters), P(rtgr_aa_stats)]
+        getattr(lib, f"rtgr_eval_texture_{suf}").argtypes = [ctx, u64, C.c_uint32, vp, u64, vp, vp]
+    lib.rtgr_texture_load.argtypes = [ctx, P(rtgr_texture_desc), vp, P(u64)]
+    lib.rtgr_texture_unload.argtypes = [ctx, u64]
     lib.rtgr_eval_fastmath_f64.argtypes = [ctx, vp, u64, vp, vp]
     lib.rtgr_quantize_device_f64.argtypes = [ctx, vp, u64, u64, vp, vp]
     lib.rtgr_user_metric_load.argtypes = [ctx, C.c_char_p, P(u64)]

@@ -454,6 +454,109 @@ def trace_aa(metric, objs, cam, ni, nj, k=4, contrast=1.0 / 255.0, opt=None, dty
     return res
 
 
+# ---- image textures (include/rtgr.h "image textures") -------------------------------------------------------------------------
+class Texture:
+    """An image texture resident in a context (rtgr_texture_load): `id`, `width`, `height`; `unload()` releases the id (the device
+    memory goes at the next rtgr_trim)."""
+
+    def __init__(self, tid, width, height, ctx=None):
+        self.id, self.width, self.height, self.ctx = int(tid), int(width), int(height), ctx
+
+    def unload(self):
+        texture_unload(self, self.ctx)
+
+    def __repr__(self):
+        return f"Texture(id={self.id:#x}, {self.width} x {self.height})"
+
+
+def texture_load(array, ctx=None):
+    """rtgr_texture_load: `array` is (3, height, width) — the three colour planes, column fastest, the layout of every `rgb` output
+    (a traced ni x nj frame reshaped (3, nj, ni) is a texture as it stands) — or an image (height, width, 3).  -> Texture"""
+    a = np.asarray(array, dtype=np.float64)
+    if a.ndim == 3 and a.shape[0] != 3 and a.shape[2] == 3:
+        a = np.moveaxis(a, 2, 0)
+    if a.ndim != 3 or a.shape[0] != 3:
+        raise ValueError(f"texture_load: need (3, height, width) planes or a (height, width, 3) image, got {np.shape(array)}")
+    a = np.ascontiguousarray(a)
+    lib = _lib()
+    desc = _abi.rtgr_texture_desc(width=a.shape[2], height=a.shape[1], flags=0, pad=0)
+    out = C.c_uint64(0)
+    _abi.check(lib, lib.rtgr_texture_load(ctx, C.byref(desc), a.ctypes.data, C.byref(out)))
+    return Texture(out.value, a.shape[2], a.shape[1], ctx)
+
+
+def texture_unload(texture, ctx=None):
+    """rtgr_texture_unload: a Texture or an id; 0: every texture of the context"""
+    lib = _lib()
+    _abi.check(lib, lib.rtgr_texture_unload(ctx, int(getattr(texture, "id", texture))))
+
+
+def eval_texture(texture, points, filter=_abi.TEX_BILINEAR, disk_range=None, rgb=None, dtype=np.float64, ctx=None):
+    """rtgr_eval_texture_f64 / _f32: the sampler at the points [n, 3] — directions d, or positions whose (x, y) are read when
+    disk_range = (r_in, r_out) is given.  rgb [n, 3]: what a "no sample" point (a zero or non-finite d) keeps; default NaN.
+    -> rgb [n, 3]"""
+    lib = _lib()
+    p = np.ascontiguousarray(points, dtype=dtype).reshape(-1, 3)
+    n = p.shape[0]
+    out = np.full((n, 3), np.nan, dtype) if rgb is None else np.ascontiguousarray(rgb, dtype=dtype).reshape(n, 3).copy()
+    rng = None if disk_range is None else np.array(disk_range, dtype=dtype).reshape(2)
+    fn = lib.rtgr_eval_texture_f64 if dtype == np.float64 else lib.rtgr_eval_texture_f32
+    _abi.check(lib, fn(ctx, int(getattr(texture, "id", texture)), int(filter), p.ctypes.data, n, None if rng is None else rng.ctypes.data,
+                       out.ctypes.data))
+    return out
+
+
+def make_shade(textures, r_escape=0.0):
+    """{object: (texture, filter)} -> rtgr_shade (object: the 1-based index in the object list, 0 = rays that escape; a bare texture
+    means bilinear).  The bind array is kept alive by the struct (sh._keep)."""
+    items = list((textures or {}).items())
+    binds = (_abi.rtgr_texture_bind * max(len(items), 1))()
+    for k, (obj, tf) in enumerate(items):
+        tex, filt = tf if isinstance(tf, (tuple, list)) else (tf, _abi.TEX_BILINEAR)
+        binds[k].object, binds[k].filter, binds[k].texture = int(obj), int(filt), int(getattr(tex, "id", tex))
+    sh = _abi.rtgr_shade(nbind=len(items), flags=0, bind=C.cast(binds, C.POINTER(_abi.rtgr_texture_bind)), r_escape=float(r_escape))
+    sh._keep = binds
+    return sh
+
+
+def trace_shaded(metric, objs, cam, ni, nj, textures=None, r_escape=0.0, aa=None, opt=None, dtype=np.float64, ctx=None, details=False):
+    """A frame with IMAGE TEXTURES (rtgr_trace_shaded_f64 / _f32) — an extension: the plain ni x nj frame of the camera, then the pixels
+    whose object — or whose escape — has a texture bound get the texel's colour; every other pixel keeps the plain frame's bits.
+    textures = {omin: (texture, filter), 0: …}: omin is the 1-based index in objs (what `hit` holds), 0 binds the rays that end
+    without a hit at |x| >= r_escape (coloured by the direction they end with).  Spheres of either radius sign and Disks take
+    textures.  aa: None, or dict(k=…, contrast=…, max_batch_rays=…) / an rtgr_aa — adaptive anti-aliasing of the shaded frame.
+    -> dict(rgb [3, ni*nj], counters; aa: + refined, stats; details: + the per-ray outputs of the pixel-centre rays)."""
+    lib = _lib()
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    camera = cam if isinstance(cam, rtgr_camera) else make_camera(**cam)
+    n = ni * nj
+    sh = make_shade(textures, r_escape)
+    res = dict(rgb=np.zeros((3, n), dtype))
+    aap = refined = stats = None
+    if aa is not None:
+        aap = aa if isinstance(aa, _abi.rtgr_aa) else _abi.rtgr_aa(k=int(aa.get("k", 4)), flags=0, contrast=float(aa.get("contrast", 1.0 / 255.0)),
+                                                                     max_batch_rays=int(aa.get("max_batch_rays", 0)))
+        res["refined"] = np.zeros(n, np.uint8)
+        refined, stats = res["refined"].ctypes.data, _abi.rtgr_aa_stats()
+    outs = None
+    if details:
+        outs = rtgr_ray_outputs()
+        wide = sc.nobj > 255
+        res.update(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
+                   hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
+        for name in ("state_end", "lambda_end", "status", "hit", "n_accept", "n_reject"):
+            setattr(outs, "hit32" if (wide and name == "hit") else name, res[name].ctypes.data)
+    ctr = rtgr_counters()
+    fn = lib.rtgr_trace_shaded_f64 if dtype == np.float64 else lib.rtgr_trace_shaded_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(camera), ni, nj, C.byref(sh), aap, res["rgb"].ctypes.data, outs, refined,
+                       C.byref(ctr), stats))
+    res["counters"] = ctr.as_dict()
+    if stats is not None:
+        res["stats"] = stats.as_dict()
+    return res
+
+
 def trace_ray(metric, objs, cb, p, opt=None, ctx=None):
     """Legacy single-pixel shape `trace_ray(metric, objs, cb, p)::Pixel` (test/runtests.jl:65-79).
     `cb` is accepted for signature parity and ignored: the callback is always
@@ -563,5 +666,5 @@ def example2(ni=200, nj=200, save=True, ctx=None):
 
 __all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
-           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "dmetric", "christoffel", "geodesic", "example1", "example2",
+           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

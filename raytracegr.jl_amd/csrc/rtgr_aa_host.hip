@@ -1,7 +1,8 @@
 // rtgr_aa_host.hip — adaptive anti-aliasing (include/rtgr.h "adaptive anti-aliasing"): the plain frame, the edge rule over it, and a
 // sparse second trace of the flagged pixels' k x k sub-rays, averaged back into the frame.  Host side only: both traces are
 // trace_device — the integrate / prepare / resolve kernels run as for any other call, the sub-rays as caller-supplied ray states —
-// and the three small kernels in between are rtgr_aa.hip's.
+// and the three small kernels in between are rtgr_aa.hip's.  With a shade description (rtgr_trace_shaded_*, rtgr_texture_host.hip) both
+// traces also deliver their end states and the shading kernel runs behind each; without one nothing of that exists.
 #include "rtgr_internal.hpp"
 
 namespace rtgr {
@@ -25,7 +26,7 @@ static int aa_check(const rtgr_scene* scene, const rtgr_camera* cam, const rtgr_
 }
 
 // grow-only scratch of a stream, retired like its workspace (D.mu held; never called during capture: the entry point refuses first)
-static int aa_need(StreamState& ss, void*& p, size_t& have, size_t bytes) {
+int aa_need(StreamState& ss, void*& p, size_t& have, size_t bytes) {
     if (bytes <= have) return RTGR_OK;
     void* q = nullptr;
     HIP_TRY(hipMalloc(&q, bytes));
@@ -37,9 +38,9 @@ static int aa_need(StreamState& ss, void*& p, size_t& have, size_t bytes) {
 
 // the call on device D, stream st; d_rgb, the members of `out` and d_refined are pointers of that device
 template <class R>
-static int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
-                       const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats,
-                       hipStream_t st) {
+int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats,
+                hipStream_t st, const ShadeDesc<R>* shade) {
     int rc;
     if ((rc = aa_check(scene, cam, aa, ni, nj))) return rc;
     DeviceGuard guard(D.dev);
@@ -51,10 +52,12 @@ static int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver*
     const uint64_t n = ni * nj;
     const uint32_t k = aa->k, kk = k * k;
     const bool want_status = !(out && out->status), want_hit32 = !(out && out->hit32);
+    const bool want_state = shade && !(out && out->state_end);   // (the shading kernel reads the end states)
 
-    // ---- frame scratch: [counters | count] [hit32] [status] [list] ---------------------------------------------------------------
+    // ---- frame scratch: [counters | count] [hit32] [status] [list] [end states: shaded frames only] -------------------------------
     const size_t off_hit = AA_HEAD, off_status = off_hit + (want_hit32 ? align256(n * sizeof(uint32_t)) : 0),
-                 off_list = off_status + (want_status ? align256(n) : 0), frame_bytes = off_list + align256(n * sizeof(uint64_t));
+                 off_list = off_status + (want_status ? align256(n) : 0), off_state = off_list + align256(n * sizeof(uint64_t)),
+                 frame_bytes = off_state + (want_state ? align256(n * 8 * sizeof(R)) : 0);
     StreamState* ss = nullptr;
     DevScene<R> sc;
     DevCamera<R> cm;
@@ -74,7 +77,13 @@ static int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver*
     if (out) o1 = *out; else std::memset(&o1, 0, sizeof o1);
     if (want_hit32) o1.hit32 = (uint32_t*)(frame + off_hit);
     if (want_status) o1.status = (uint8_t*)(frame + off_status);
+    if (want_state) o1.state_end = frame + off_state;
     if ((rc = trace_device<R>(D, scene, opt, nullptr, cam, ni, nj, 0, nj, d_rgb, &o1, ctr ? d_ctr : nullptr, st))) return rc;
+    if (shade) {   // the edge rule reads the SHADED colours
+        std::lock_guard<std::mutex> lk(D.mu);
+        KernelTimer timer(D, st, 0);
+        if ((rc = shade_launch<R>(ShadeArgs<R>{d_rgb, o1.hit32, o1.status, (const R*)o1.state_end, n, n, *shade}, st))) return rc;
+    }
 
     // ---- the edge rule -------------------------------------------------------------------------------------------------------------
     {
@@ -96,9 +105,13 @@ static int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver*
     const uint64_t batches = (count + per - 1) / per;
     const uint64_t m_max = count < per ? count : per;
     const size_t off_sub = align256((size_t)m_max * kk * 8 * sizeof(R));   // batch scratch: [sub-ray states] [sub-colours, 3 planes]
+    // … and for a shaded frame what the shading kernel reads of the sub-rays: [end states] [hit32] [status]
+    const size_t off_end = off_sub + align256((size_t)m_max * kk * 3 * sizeof(R)), off_hit2 = off_end + (shade ? align256((size_t)m_max * kk * 8 * sizeof(R)) : 0),
+                 off_status2 = off_hit2 + (shade ? align256((size_t)m_max * kk * sizeof(uint32_t)) : 0),
+                 batch_bytes = off_status2 + (shade ? align256((size_t)m_max * kk) : 0);
     if (count) {
         std::lock_guard<std::mutex> lk(D.mu);
-        if ((rc = aa_need(*ss, ss->aa_batch, ss->aa_batch_bytes, off_sub + align256((size_t)m_max * kk * 3 * sizeof(R))))) return rc;
+        if ((rc = aa_need(*ss, ss->aa_batch, ss->aa_batch_bytes, batch_bytes))) return rc;
     }
     for (uint64_t b = 0; b < batches; b++) {
         const uint64_t first = b * per, m = count - first < per ? count - first : per;
@@ -109,7 +122,19 @@ static int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver*
             KernelTimer timer(D, st, 0);
             if ((rc = aa_subrays<R>(sc, cm, ni, nj, k, d_list + first, m, d_states, st))) return rc;
         }
-        if ((rc = trace_device<R>(D, scene, opt, d_states, nullptr, m * kk, 1, 0, 1, d_sub, nullptr, ctr ? d_ctr : nullptr, st))) return rc;
+        rtgr_ray_outputs o2;
+        std::memset(&o2, 0, sizeof o2);
+        if (shade) {
+            o2.state_end = (char*)ss->aa_batch + off_end;
+            o2.hit32 = (uint32_t*)((char*)ss->aa_batch + off_hit2);
+            o2.status = (uint8_t*)((char*)ss->aa_batch + off_status2);
+        }
+        if ((rc = trace_device<R>(D, scene, opt, d_states, nullptr, m * kk, 1, 0, 1, d_sub, shade ? &o2 : nullptr, ctr ? d_ctr : nullptr, st))) return rc;
+        if (shade) {   // the sub-rays as a one-row canvas of m k² pixels
+            std::lock_guard<std::mutex> lk(D.mu);
+            KernelTimer timer(D, st, 0);
+            if ((rc = shade_launch<R>(ShadeArgs<R>{d_sub, o2.hit32, o2.status, (const R*)o2.state_end, m * kk, m * kk, *shade}, st))) return rc;
+        }
         {
             std::lock_guard<std::mutex> lk(D.mu);
             KernelTimer timer(D, st, 0);
@@ -135,7 +160,7 @@ int api::trace_aa_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_
     if ((rc = aa_check(scene, cam, aa, ni, nj))) return rc;
     DeviceCtx* D = nullptr;
     if ((rc = device_of(c, d_rgb, &D))) return rc;
-    return trace_aa_on<R>(*D, scene, opt, cam, ni, nj, aa, d_rgb, out, d_refined, ctr, stats, (hipStream_t)stream);
+    return trace_aa_on<R>(*D, scene, opt, cam, ni, nj, aa, d_rgb, out, d_refined, ctr, stats, (hipStream_t)stream, nullptr);
 }
 
 // host pointers: the same call on device 0 of the context, on its staging's compute stream, and the frame copied out
@@ -162,7 +187,7 @@ int api::trace_aa(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver*
     char* base = (char*)S->d_out.p;
     const rtgr_ray_outputs o = ray_outputs_at(base, arrs, out);
     uint8_t* d_refined = refined ? (uint8_t*)(base + off_refined) : nullptr;
-    if ((rc = trace_aa_on<R>(D, scene, opt, cam, ni, nj, aa, (R*)(base + arrs[0].off), out ? &o : nullptr, d_refined, ctr, stats, S->s_comp))) {
+    if ((rc = trace_aa_on<R>(D, scene, opt, cam, ni, nj, aa, (R*)(base + arrs[0].off), out ? &o : nullptr, d_refined, ctr, stats, S->s_comp, nullptr))) {
         (void)hipStreamSynchronize(S->s_comp);
         return rc;
     }
@@ -171,6 +196,7 @@ int api::trace_aa(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver*
     if (refined) HIP_TRY(hipMemcpy(refined, d_refined, n, hipMemcpyDeviceToHost));
     return RTGR_OK;
 }
+RTGR_INSTANTIATE_F64_F32(trace_aa_on);
 RTGR_INSTANTIATE_F64_F32(api::trace_aa_device);
 RTGR_INSTANTIATE_F64_F32(api::trace_aa);
 

@@ -155,6 +155,7 @@ void free_device_state(DeviceCtx& d, bool all) {
             if (kv.second.queue) (void)hipFree(kv.second.queue);
             if (kv.second.aa_frame) (void)hipFree(kv.second.aa_frame);
             if (kv.second.aa_batch) (void)hipFree(kv.second.aa_batch);
+            if (kv.second.shade_frame) (void)hipFree(kv.second.shade_frame);
         }
     }
     for (auto& g : d.retired_grids) { (void)hipFree(g.d64); (void)hipFree(g.d32); }   // unloaded grid metrics (idle device: see above)
@@ -162,6 +163,12 @@ void free_device_state(DeviceCtx& d, bool all) {
     if (all) {
         for (auto& g : d.grids) { (void)hipFree(g.d64); (void)hipFree(g.d32); }
         d.grids.clear();
+    }
+    for (auto& t : d.retired_textures) { (void)hipFree(t.d64); (void)hipFree(t.d32); }   // unloaded image textures, likewise
+    d.retired_textures.clear();
+    if (all) {
+        for (auto& t : d.textures) { (void)hipFree(t.d64); (void)hipFree(t.d32); }
+        d.textures.clear();
     }
     for (auto& kv : d.object_tables) (void)hipFree(kv.second.dev);   // (the device is idle: synchronised above)
     d.object_tables.clear();

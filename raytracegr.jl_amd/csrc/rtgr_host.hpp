@@ -156,6 +156,13 @@ template <class R> inline DevGrid<R> dev_grid(const GridTable& t) {
     }
     return G;
 }
+// An image texture (rtgr_texture_load): the texels on one device, four scalars per texel (r, g, b, 0), row after row, in Float64 and
+// Float32.  Immutable; rtgr_texture_unload moves the table to DeviceCtx::retired_textures, rtgr_trim / rtgr_destroy free it.
+struct TextureTable {
+    uint64_t id = 0;
+    uint32_t W = 0, H = 0;
+    void* d64 = nullptr, *d32 = nullptr;
+};
 // pipeline workspace of one (device, stream)
 struct StreamState {
     void* ws = nullptr;
@@ -167,6 +174,9 @@ struct StreamState {
     // BATCH the sub-ray states and the sub-colours
     void* aa_frame = nullptr; size_t aa_frame_bytes = 0;
     void* aa_batch = nullptr; size_t aa_batch_bytes = 0;
+    // scratch of rtgr_trace_shaded_device_* without anti-aliasing (rtgr_texture_host.hip), likewise: the counters, then the end states /
+    // hit map / status bytes the shading kernel reads and the caller did not ask for
+    void* shade_frame = nullptr; size_t shade_frame_bytes = 0;
 };
 
 struct Staging;  // host entry points (rtgr_internal.hpp)
@@ -180,6 +190,8 @@ struct DeviceCtx {
     std::vector<UserModule> modules;
     std::vector<GridTable> grids;           // resident grid metrics, by id
     std::vector<GridTable> retired_grids;   // unloaded ones: freed by rtgr_trim / rtgr_destroy only
+    std::vector<TextureTable> textures;           // resident image textures, by id
+    std::vector<TextureTable> retired_textures;   // unloaded ones: freed by rtgr_trim / rtgr_destroy only
     std::unordered_multimap<uint64_t, ObjectTable> object_tables;   // by FNV-1a of the content
     size_t object_table_bytes = 0;                                   // … and what they hold together
     std::unordered_map<uint64_t, int> checked_scenes;                // auto_scene_check: key of a scene -> the verdict it got (RTGR_OK or the refusal)
@@ -203,6 +215,10 @@ struct DeviceCtx {
     }
     const GridTable* find_grid(uint64_t id) const {
         for (auto& g : grids) if (g.id == id) return &g;
+        return nullptr;
+    }
+    const TextureTable* find_texture(uint64_t id) const {
+        for (auto& t : textures) if (t.id == id) return &t;
         return nullptr;
     }
     const UserModule* find_module(uint64_t id) const {
@@ -295,5 +311,36 @@ int aa_subrays(const DevScene<R>& sc, const DevCamera<R>& cam, uint64_t ni, uint
 // … and their colours (3 planes of npix k²) averaged into the listed pixels of d_rgb (3 planes of n)
 template <class R>
 int aa_reduce(const R* d_sub, const uint64_t* d_list, uint64_t npix, uint32_t k, R* d_rgb, uint64_t n, hipStream_t st);
+// image textures (rtgr_shade.hip; include/rtgr.h "image textures").  A bind as the shading kernel reads it, resolved by the host at call
+// time for one device and scalar type: the texels, the filter, and what the mapping needs of the caller's object — kind 0: rays that
+// escape; RTGR_SPHERE: (a, b, c) = the centre; RTGR_DISK: a = r_in, b = r_out.
+template <class R>
+struct DevTexBind {
+    const R* tex;
+    uint32_t W, H, filter, kind;
+    uint32_t object, pad;   // 1-based index in the caller's list (what hit32 holds); 0: the escape bind
+    R a, b, c;
+};
+template <class R>
+struct ShadeDesc {
+    uint32_t nbind;
+    R r_escape;
+    DevTexBind<R> bind[RTGR_MAX_TEXTURE_BINDS];
+};
+// the shading kernel's argument block: n pixels, colour planes plane_stride apart
+template <class R>
+struct ShadeArgs {
+    R* rgb;
+    const uint32_t* hit32;
+    const uint8_t* status;
+    const R* state_end;
+    uint64_t n, plane_stride;
+    ShadeDesc<R> desc;
+};
+template <class R>
+int shade_launch(const ShadeArgs<R>& A, hipStream_t st);
+template <class R>
+int eval_texture_launch(const R* d_tex, uint32_t W, uint32_t H, uint32_t filter, bool disk, R r_in, R r_out, const R* d_p, uint64_t n, R* d_rgb,
+                        hipStream_t st);
 
 }  // namespace rtgr

@@ -7,6 +7,8 @@
 //   rtgr_hooks.hip          make_canvas and the parity hooks (rtgr_eval_*), image quantisation
 //   rtgr_units.hip          run-time compiled units: build, audit, load-time probe, load, scene check
 //   rtgr_aa_host.hip        adaptive anti-aliasing: the plain frame, the edge rule, a sparse second trace (kernels: rtgr_aa.hip)
+//   rtgr_texture_host.hip   image textures: load / unload, the shaded trace (a plain or anti-aliased trace + the shading kernel), the
+//                           sampler hook (kernels: rtgr_shade.hip)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -135,6 +137,16 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
                  uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* d_rgb, const rtgr_ray_outputs* out,
                  rtgr_counters* d_counters, hipStream_t st, uint64_t jstride = 1, uint64_t nrows_strided = 0,
                  const Window* win = nullptr);
+
+// ---- adaptive anti-aliasing on one device (rtgr_aa_host.hip), optionally of a SHADED frame (rtgr_texture_host.hip) ---------------
+// grow-only scratch of a stream, retired like its workspace (D.mu held; never called during capture: the entry points refuse first)
+int aa_need(StreamState& ss, void*& p, size_t& have, size_t bytes);
+// the call on device D, stream st; d_rgb, the members of `out` and d_refined are pointers of that device.  shade == nullptr: the plain
+// anti-aliased frame; otherwise both passes are shaded with these (resolved) binds
+template <class R>
+int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats,
+                hipStream_t st, const ShadeDesc<R>* shade);
 
 // scratch device buffers of the small host-pointer hooks (eval_*, make_canvas, the probe): RAII, synchronous
 struct DevBuf {
@@ -270,6 +282,11 @@ int user_metric_loaded(rtgr_context* ctx, uint64_t id);
 int grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out);
 int grid_metric_unload(rtgr_context* ctx, uint64_t id);
 int grid4_metric_load(rtgr_context* ctx, const rtgr_grid4* grid, const double* g, uint64_t* id_out);
+int texture_load(rtgr_context* ctx, const rtgr_texture_desc* desc, const double* texels, uint64_t* id_out);
+int texture_unload(rtgr_context* ctx, uint64_t id);
+template <class R> int trace_shaded_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
+template <class R> int trace_shaded(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_aa* aa, R* rgb, const rtgr_ray_outputs* out, uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats);
+template <class R> int eval_texture(rtgr_context* ctx, uint64_t texture, uint32_t filter, const R* p, uint64_t n, const R* disk_range, R* rgb);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 

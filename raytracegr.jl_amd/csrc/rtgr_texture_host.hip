@@ -1,0 +1,318 @@
+// rtgr_texture_host.hip — image textures (include/rtgr.h "image textures"): load (checks, upload to every device of the context in Float64
+// and Float32) and unload (retire: a hipGraph captured earlier may still replay the texels; rtgr_trim frees them), the shaded trace —
+// a plain trace_device, or the anti-aliased one of rtgr_aa_host.hip, with the shading kernel behind it — and the sampler hook.  Host
+// code only: the kernels are rtgr_shade.hip's, the mapping and the sampler rtgr_texture.hpp's.
+#include "rtgr_internal.hpp"
+
+namespace rtgr {
+
+// Texture ids: a counter of their own, in a range of their own (top bits 0x7…; grid ids carry 0xA…), and never the id of a resident
+// unit or grid of the context.
+static std::atomic<uint64_t> g_next_texture{1};
+constexpr uint64_t TEXTURE_ID_TAG = 0x7000000000000000ull, TEXTURE_ID_MASK = 0xF000000000000000ull;
+constexpr size_t SHADE_HEAD = 256;   // head of the frame scratch: rtgr_counters (64 bytes)
+
+int api::texture_load(rtgr_context* ctx, const rtgr_texture_desc* desc, const double* texels, uint64_t* id_out) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if (!desc || !texels || !id_out) return fail(RTGR_ERR_BAD_ARG, "rtgr_texture_load: NULL argument");
+    const uint32_t W = desc->width, H = desc->height;
+    if (W < 2u || W > RTGR_TEXTURE_MAX_SIDE || H < 2u || H > RTGR_TEXTURE_MAX_SIDE)
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_texture_load: width and height must be 2 .. " + std::to_string(RTGR_TEXTURE_MAX_SIDE) + ", got " +
+                                      std::to_string(W) + " x " + std::to_string(H));
+    if (desc->flags != 0 || desc->pad != 0) return fail(RTGR_ERR_BAD_ARG, "rtgr_texture_load: rtgr_texture_desc.flags and .pad must be 0");
+    const size_t ntex = (size_t)W * H;
+    // every texel finite; the device layout (four scalars per texel) in both scalar types
+    std::vector<double> t64(ntex * 4, 0.0);
+    std::vector<float> t32(ntex * 4, 0.0f);
+    for (int ch = 0; ch < 3; ch++)
+        for (size_t q = 0; q < ntex; q++) {
+            const double v = texels[ch * ntex + q];
+            if (!std::isfinite(v))
+                return fail(RTGR_ERR_BAD_ARG, "rtgr_texture_load: texel " + std::to_string(ch * ntex + q) + " (channel " + std::to_string(ch) + ", row " +
+                                              std::to_string(q / W) + ", column " + std::to_string(q % W) + ") holds a non-finite value");
+            t64[q * 4 + ch] = v;
+            t32[q * 4 + ch] = (float)v;
+        }
+    std::lock_guard<std::mutex> load_lock(c->modules_mu);   // (units, grids and textures are loaded / unloaded under the same lock)
+    uint64_t id = 0;
+    for (;;) {
+        id = TEXTURE_ID_TAG | (g_next_texture.fetch_add(1) & ~TEXTURE_ID_MASK);
+        bool taken = false;
+        for (auto& d : c->devs) {
+            std::lock_guard<std::mutex> lk(d->mu);
+            taken = taken || d->find_module(id) || d->find_grid(id) || d->find_texture(id);
+        }
+        if (!taken) break;
+    }
+    // allocate and upload everywhere first; the texture becomes visible to calls only when every device has its copy
+    std::vector<TextureTable> made(c->devs.size());
+    auto release = [&]() {
+        for (size_t k = 0; k < made.size(); k++) {
+            DeviceGuard guard(c->devs[k]->dev);
+            if (made[k].d64) (void)hipFree(made[k].d64);
+            if (made[k].d32) (void)hipFree(made[k].d32);
+        }
+    };
+    for (size_t k = 0; k < c->devs.size(); k++) {
+        DeviceGuard guard(c->devs[k]->dev);
+        if (!guard.ok) { release(); return fail(RTGR_ERR_HIP, "hipSetDevice failed"); }
+        TextureTable& t = made[k];
+        t.id = id; t.W = W; t.H = H;
+        hipError_t e = hipMalloc(&t.d64, t64.size() * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(&t.d32, t32.size() * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(t.d64, t64.data(), t64.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(t.d32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            release();
+            return fail(RTGR_ERR_HIP, "rtgr_texture_load: upload to device " + std::to_string(k) + ": " + hipGetErrorString(e));
+        }
+    }
+    for (size_t k = 0; k < c->devs.size(); k++) {
+        std::lock_guard<std::mutex> lk(c->devs[k]->mu);
+        c->devs[k]->textures.push_back(made[k]);
+    }
+    *id_out = id;
+    return RTGR_OK;
+}
+
+int api::texture_unload(rtgr_context* ctx, uint64_t id) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> load_lock(c->modules_mu);
+    bool found = id == 0;
+    for (auto& d : c->devs) {
+        std::lock_guard<std::mutex> lk(d->mu);
+        for (size_t k = 0; k < d->textures.size();)
+            if (id == 0 || d->textures[k].id == id) {
+                d->retired_textures.push_back(d->textures[k]);   // (not freed: a captured hipGraph may replay it until rtgr_trim)
+                d->textures.erase(d->textures.begin() + (long)k);
+                found = true;
+            } else {
+                k++;
+            }
+    }
+    if (!found) return fail(RTGR_ERR_BAD_ARG, "rtgr_texture_unload: no texture with id " + std::to_string(id) + " is loaded in this context");
+    return RTGR_OK;
+}
+
+static int filter_check(uint32_t filter) {
+    if (filter != RTGR_TEX_NEAREST && filter != RTGR_TEX_BILINEAR)
+        return fail(RTGR_ERR_BAD_ARG, "unknown texture filter " + std::to_string(filter) + " (RTGR_TEX_NEAREST = 0, RTGR_TEX_BILINEAR = 1)");
+    return RTGR_OK;
+}
+
+// the caller's binds into the records the shading kernel reads, for device D and scalar type R (takes D.mu: the texture tables)
+template <class R>
+static int shade_resolve(DeviceCtx& D, const rtgr_scene* scene, const rtgr_shade* shade, ShadeDesc<R>& sd) {
+    if (!scene) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
+    if (!shade) return fail(RTGR_ERR_BAD_ARG, "rtgr_shade is NULL");
+    if (shade->flags != 0) return fail(RTGR_ERR_BAD_ARG, "rtgr_shade.flags must be 0");
+    if (shade->nbind > RTGR_MAX_TEXTURE_BINDS)
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_shade.nbind = " + std::to_string(shade->nbind) + ": at most RTGR_MAX_TEXTURE_BINDS (16) binds");
+    if (shade->nbind && !shade->bind) return fail(RTGR_ERR_BAD_ARG, "rtgr_shade.bind is NULL");
+    if (!(shade->r_escape >= 0.0)) return fail(RTGR_ERR_BAD_ARG, "rtgr_shade.r_escape must be >= 0 (and not NaN)");
+    if (scene->nobj > RTGR_OBJECTS_LIMIT || (!scene->objects && scene->nobj > RTGR_MAX_OBJECTS))
+        return fail(RTGR_ERR_BAD_ARG, "bad object list: more than RTGR_MAX_OBJECTS objects need rtgr_scene.objects");
+    std::memset(&sd, 0, sizeof sd);
+    sd.nbind = shade->nbind;
+    sd.r_escape = (R)shade->r_escape;
+    std::lock_guard<std::mutex> lk(D.mu);
+    for (uint32_t k = 0; k < shade->nbind; k++) {
+        const rtgr_texture_bind& b = shade->bind[k];
+        const std::string who = "rtgr_shade.bind[" + std::to_string(k) + "]";
+        int rc;
+        if ((rc = filter_check(b.filter))) return fail(rc, who + ": " + last_error_string());
+        const TextureTable* t = D.find_texture(b.texture);
+        if (!t) return fail(RTGR_ERR_BAD_ARG, who + ": no texture with id " + std::to_string(b.texture) + " is loaded in this context");
+        if (b.object > scene->nobj)
+            return fail(RTGR_ERR_BAD_ARG, who + ": object " + std::to_string(b.object) + " of a list of " + std::to_string(scene->nobj) + " (1-based; 0 = rays that escape)");
+        for (uint32_t q = 0; q < k; q++)
+            if (shade->bind[q].object == b.object)
+                return fail(RTGR_ERR_BAD_ARG, who + ": " + (b.object ? "object " + std::to_string(b.object) : std::string("the escape")) + " is bound twice");
+        DevTexBind<R>& d = sd.bind[k];
+        d.tex = (const R*)(sizeof(R) == 8 ? t->d64 : t->d32);
+        d.W = t->W; d.H = t->H; d.filter = b.filter; d.object = b.object;
+        if (b.object == 0) continue;   // (kind 0: the escape)
+        const rtgr_object& o = scene_objects(scene)[b.object - 1];
+        if (o.kind == RTGR_SPHERE) { d.kind = RTGR_SPHERE; d.a = (R)o.p[1]; d.b = (R)o.p[2]; d.c = (R)o.p[3]; }
+        else if (o.kind == RTGR_DISK) { d.kind = RTGR_DISK; d.a = (R)o.p[1]; d.b = (R)o.p[2]; }
+        else
+            return fail(RTGR_ERR_BAD_ARG, who + ": object " + std::to_string(b.object) + " is a " + (o.kind == RTGR_PLANE ? "Plane" : o.kind == RTGR_USER_OBJECT ? "user object" : "unknown kind") +
+                                          ": textures go on Spheres, Disks and escaping rays");
+    }
+    return RTGR_OK;
+}
+
+static int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refined, const rtgr_aa_stats* stats, uint64_t ni, uint64_t nj) {
+    if (!cam) return fail(RTGR_ERR_BAD_ARG, "a shaded frame needs a camera (cam is NULL)");
+    if (!aa && (refined || stats)) return fail(RTGR_ERR_BAD_ARG, "refined and stats belong to anti-aliasing: they must be NULL when aa is NULL");
+    if (ni == 0 || nj == 0 || ni > (1ull << 32) || nj > (1ull << 32) || ni * nj > (1ull << 34))
+        return fail(RTGR_ERR_BAD_ARG, "bad canvas: need ni, nj > 0 and at most 2^34 pixels for a shaded frame");
+    return RTGR_OK;
+}
+
+// the call on device D, stream st; d_rgb, the members of `out` and d_refined are pointers of that device
+template <class R>
+static int trace_shaded_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                           const rtgr_shade* shade, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr,
+                           rtgr_aa_stats* stats, hipStream_t st) {
+    int rc;
+    if ((rc = shaded_check(cam, aa, d_refined, stats, ni, nj))) return rc;
+    if ((rc = check_redshift_outputs(out))) return rc;
+    ShadeArgs<R> A;
+    if ((rc = shade_resolve<R>(D, scene, shade, A.desc))) return rc;
+    if (aa) return trace_aa_on<R>(D, scene, opt, cam, ni, nj, aa, d_rgb, out, d_refined, ctr, stats, st, &A.desc);
+    DeviceGuard guard(D.dev);
+    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    if (capturing && ctr)
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_shaded_*: the stream is being captured and `ctr` asks for a synchronisation at the end of the call "
+                                      "(which cannot be captured): pass ctr = NULL");
+    const uint64_t n = ni * nj;
+    const bool shading = A.desc.nbind != 0;
+    const bool want_state = shading && !(out && out->state_end), want_hit32 = shading && !(out && out->hit32),
+               want_status = shading && !(out && out->status);
+    // ---- frame scratch: [counters] [end states] [hit32] [status] -------------------------------------------------------------------
+    const size_t off_state = SHADE_HEAD, off_hit = off_state + (want_state ? align256(n * 8 * sizeof(R)) : 0),
+                 off_status = off_hit + (want_hit32 ? align256(n * sizeof(uint32_t)) : 0), frame_bytes = off_status + (want_status ? align256(n) : 0);
+    char* frame = nullptr;
+    if (ctr || frame_bytes > SHADE_HEAD) {
+        std::lock_guard<std::mutex> lk(D.mu);
+        StreamState* ss = nullptr;
+        if ((rc = stream_state(D, st, &ss))) return rc;
+        if (capturing && frame_bytes > ss->shade_frame_bytes)
+            return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_shaded_*: the stream's shading scratch must grow but the stream is being captured: make a call of "
+                                          "this size on the stream before hipStreamBeginCapture");
+        if ((rc = aa_need(*ss, ss->shade_frame, ss->shade_frame_bytes, frame_bytes))) return rc;
+        frame = (char*)ss->shade_frame;
+    }
+    rtgr_counters* d_ctr = ctr ? (rtgr_counters*)frame : nullptr;
+    if (ctr) HIP_TRY(hipMemsetAsync(frame, 0, SHADE_HEAD, st));
+    // ---- the plain frame, with what the shading kernel reads of it ------------------------------------------------------------------
+    rtgr_ray_outputs o1;
+    if (out) o1 = *out; else std::memset(&o1, 0, sizeof o1);
+    if (want_state) o1.state_end = frame + off_state;
+    if (want_hit32) o1.hit32 = (uint32_t*)(frame + off_hit);
+    if (want_status) o1.status = (uint8_t*)(frame + off_status);
+    if ((rc = trace_device<R>(D, scene, opt, nullptr, cam, ni, nj, 0, nj, d_rgb, (out || shading) ? &o1 : nullptr, d_ctr, st))) return rc;
+    if (shading) {
+        std::lock_guard<std::mutex> lk(D.mu);
+        KernelTimer timer(D, st, 0);
+        A.rgb = d_rgb; A.hit32 = o1.hit32; A.status = o1.status; A.state_end = (const R*)o1.state_end;
+        A.n = n; A.plane_stride = n;
+        if ((rc = shade_launch<R>(A, st))) return rc;
+    }
+    if (ctr) {
+        HIP_TRY(hipMemcpyAsync(ctr, d_ctr, sizeof *ctr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return RTGR_OK;
+}
+
+template <class R>
+int api::trace_shaded_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                             const rtgr_shade* shade, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined,
+                             rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if (!d_rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
+    if ((rc = shaded_check(cam, aa, d_refined, stats, ni, nj))) return rc;
+    DeviceCtx* D = nullptr;
+    if ((rc = device_of(c, d_rgb, &D))) return rc;
+    return trace_shaded_on<R>(*D, scene, opt, cam, ni, nj, shade, aa, d_rgb, out, d_refined, ctr, stats, (hipStream_t)stream);
+}
+
+// host pointers: the same call on device 0 of the context, on its staging's compute stream, and the frame copied out
+template <class R>
+int api::trace_shaded(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                      const rtgr_shade* shade, const rtgr_aa* aa, R* rgb, const rtgr_ray_outputs* out, uint8_t* refined, rtgr_counters* ctr,
+                      rtgr_aa_stats* stats) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if (!rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
+    if ((rc = shaded_check(cam, aa, refined, stats, ni, nj))) return rc;
+    if ((rc = check_redshift_outputs(out))) return rc;
+    DeviceCtx& D = *c->devs[0];
+    DeviceGuard guard(D.dev);
+    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    Staging* S = nullptr;
+    { std::lock_guard<std::mutex> lk(D.mu); if ((rc = staging_of(D, &S))) return rc; }
+    std::lock_guard<std::mutex> call_lock(S->mu);
+    HIP_TRY(hipStreamSynchronize(S->s_comp));   // (a previous call that failed half-way; the stream is idle otherwise)
+    const uint64_t n = ni * nj;
+    std::vector<RayArray> arrs = ray_arrays(rgb, out, sizeof(R));
+    const size_t off_refined = ray_arrays_layout(arrs, n);
+    if ((rc = S->d_out.need(off_refined + (refined ? align256(n) : 0)))) return rc;
+    char* base = (char*)S->d_out.p;
+    const rtgr_ray_outputs o = ray_outputs_at(base, arrs, out);
+    uint8_t* d_refined = refined ? (uint8_t*)(base + off_refined) : nullptr;
+    if ((rc = trace_shaded_on<R>(D, scene, opt, cam, ni, nj, shade, aa, (R*)(base + arrs[0].off), out ? &o : nullptr, d_refined, ctr, stats, S->s_comp))) {
+        (void)hipStreamSynchronize(S->s_comp);
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(S->s_comp));
+    for (const RayArray& a : arrs) HIP_TRY(hipMemcpy(a.ptr, base + a.off, (size_t)n * a.elem * a.planes, hipMemcpyDeviceToHost));
+    if (refined) HIP_TRY(hipMemcpy(refined, d_refined, n, hipMemcpyDeviceToHost));
+    return RTGR_OK;
+}
+
+// the sampler at n points, on device 0 of the context (host pointers): rgb goes up too — a "no sample" point keeps its entry
+template <class R>
+int api::eval_texture(rtgr_context* ctx, uint64_t texture, uint32_t filter, const R* p, uint64_t n, const R* disk_range, R* rgb) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if ((n && !p) || (n && !rgb)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_texture: NULL argument");
+    if ((rc = filter_check(filter))) return rc;
+    if (n > (1ull << 32)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_texture: at most 2^32 points per call");
+    if (disk_range && !(std::isfinite((double)disk_range[0]) && std::isfinite((double)disk_range[1])))
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_texture: disk_range = {r_in, r_out} must be finite");
+    DeviceCtx& D = *c->devs[0];
+    DeviceGuard guard(D.dev);
+    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    TextureTable t;
+    {
+        std::lock_guard<std::mutex> lk(D.mu);
+        const TextureTable* found = D.find_texture(texture);
+        if (!found) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_texture: no texture with id " + std::to_string(texture) + " is loaded in this context");
+        t = *found;
+    }
+    if (n == 0) return RTGR_OK;
+    const size_t bytes = (size_t)n * 3 * sizeof(R);
+    DevBuf d_p, d_rgb;
+    if ((rc = d_p.alloc(bytes)) || (rc = d_rgb.alloc(bytes))) return rc;
+    HIP_TRY(hipMemcpy(d_p.p, p, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_rgb.p, rgb, bytes, hipMemcpyHostToDevice));
+    if ((rc = eval_texture_launch<R>((const R*)(sizeof(R) == 8 ? t.d64 : t.d32), t.W, t.H, filter, disk_range != nullptr, disk_range ? disk_range[0] : R(0),
+                                     disk_range ? disk_range[1] : R(0), (const R*)d_p.p, n, (R*)d_rgb.p, nullptr)))
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(rgb, d_rgb.p, bytes, hipMemcpyDeviceToHost));
+    return RTGR_OK;
+}
+
+RTGR_INSTANTIATE_F64_F32(api::trace_shaded_device);
+RTGR_INSTANTIATE_F64_F32(api::trace_shaded);
+RTGR_INSTANTIATE_F64_F32(api::eval_texture);
+
+}  // namespace rtgr
+
+// A test hook, not part of include/rtgr.h (tests/test_textures.py): texture tables on device `index` of the context — resident and
+// retired (unloaded, waiting for rtgr_trim).
+extern "C" int rtgr_testhook_texture_tables(rtgr_context* ctx, int index, uint32_t* resident, uint32_t* retired) {
+    rtgr_context* c = nullptr;
+    int rc = rtgr::resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if (index < 0 || (size_t)index >= c->devs.size() || !resident || !retired) return rtgr::fail(RTGR_ERR_BAD_ARG, "bad argument");
+    rtgr::DeviceCtx& d = *c->devs[(size_t)index];
+    std::lock_guard<std::mutex> lk(d.mu);
+    *resident = (uint32_t)d.textures.size();
+    *retired = (uint32_t)d.retired_textures.size();
+    return RTGR_OK;
+}
