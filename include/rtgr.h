@@ -491,7 +491,8 @@ int rtgr_trace_aa_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_sol
  *   In scope: every metric (RTGR_USER when aa == NULL, both grid kinds), object lists of any length, both scalar types.
  *   Out of scope: the sharded, frames-in-flight, pixel-array and single-ray entry points; mip-mapping or any minification filter
  * (anti-aliasing is the answer to minification); pole-aware bilinear; planes and user objects; emission or redshift weighting of the
- * texel; several devices for one shaded frame.
+ * TEXEL (a disk that glows by itself is "disk emission" below; a textured disk is coloured as sampled); several devices for one
+ * shaded frame.
  *
  * rtgr_eval_texture_*: the sampler at n points on device 0 (host pointers) — p: n x 3 (d, or a position whose x, y are read when
  * disk_range = {r_in, r_out} is given; NULL: the direction mapping); rgb: n x 3 (AoS), read and written: a "no sample" point keeps
@@ -533,6 +534,90 @@ int rtgr_eval_texture_f64(rtgr_context* ctx, uint64_t texture, uint32_t filter, 
                           const double* disk_range /* NULL, or {r_in, r_out} */, double* rgb /* n x 3 */);
 int rtgr_eval_texture_f32(rtgr_context* ctx, uint64_t texture, uint32_t filter, const float* p /* n x 3 */, uint64_t n,
                           const float* disk_range /* NULL, or {r_in, r_out} */, float* rgb /* n x 3 */);
+
+/* ---- disk emission: an orbiting disk that glows as a black body -------------------------------------------------------------
+ * AN EXTENSION: the reference colours a hit by fixed rules, and rtgr_ray_outputs.redshift takes a disk's emitter to be the observer at
+ * rest in the slicing.  A disk ORBITS: an emitted trace is the plain trace (then the textures of `shade`, if any) followed by one
+ * emission kernel over the pixels with hit32 == emit->object, which replaces their colour by the black-body colour of gas on circular
+ * orbits, shifted by the Doppler and gravitational frequency ratio g.  No kernel of the trace itself changes; every other pixel keeps
+ * its bits; rtgr_ray_outputs.redshift keeps its documented (static) emitter.
+ *
+ * The model (one device function, csrc/rtgr_emission.hpp, in the entry point's scalar type; x_0, k_0: the ray's state at the camera,
+ * x_end, k_end: its state where it ended on the disk).
+ *   The orbital rate comes from the metric, not from a closed form.  The metric must be stationary, axisymmetric about z and symmetric
+ *   under z -> -z.  With psi = (0, -y, x, 0) the orbit of xi = d_t + Omega psi is a geodesic iff the gradient of g(xi, xi) vanishes at
+ *   fixed Omega.  At the equatorial projection P = (t, x_end, y_end, 0), with D = x d_x + y d_y acting on the metric's components:
+ *     g_tpsi = -y g_tx + x g_ty,   g_psipsi = y^2 g_xx - 2 x y g_xy + x^2 g_yy,
+ *     A = D g_tt,   B = (-y D g_tx + x D g_ty) + g_tpsi,   C = (y^2 D g_xx - 2 x y D g_xy + x^2 D g_yy) + 2 g_psipsi,
+ *     C Omega^2 + 2 B Omega + A = 0:   Omega_+- = (-B +- sqrt(B^2 - A C)) / C.
+ *   g and dg at P are those of rtgr_eval_metric_* (forward duals through a built-in metric; the interpolant of a 3-D grid).  For the
+ *   textbook Kerr metric Omega_+- are sqrt(M) / (r^(3/2) + a sqrt(M)) and -sqrt(M) / (r^(3/2) - a sqrt(M)); for the reference's own
+ *   metric (RTGR_KS_REF, whose radius is not Kerr's) and for grids the closed form would be wrong and this is not.
+ *   RTGR_EMIT_KEPLER: Omega = the root `orbit` names (+1: Omega_+, counter-clockwise seen from +z for a > 0; -1: Omega_-).
+ *   RTGR_EMIT_RIGID:  Omega = orbit itself (0: xi = d_t, the static emitter).
+ *   Emitter: xi = (1, -Omega y_end, Omega x_end, 0) at x_end (the disk has a half thickness, z_end != 0: it rotates on cylinders at the
+ *   equatorial rate), n^2 = g(x_end)(xi, xi), u_emit = xi / sqrt(-n^2).  VALID iff B^2 - A C >= 0, C != 0, every quantity finite and
+ *   n^2 < 0 (and the camera's static observer is timelike).
+ *   g = (k_0 . u_obs) / (k_end . u_emit), u_obs the static observer at the pixel exactly as for rtgr_ray_outputs.redshift; every
+ *   inner product with the metric at the point where its vectors live.
+ *   Colour: a black body's I_nu / nu^3 is invariant, so the observed spectrum is Planck's at g T_em:
+ *     rho = hypot(x_end, y_end),   T_em = T_in (rho / r_in)^(-p)   [RTGR_EMIT_INNER_EDGE: times (max(1 - sqrt(r_in / rho), 0))^(1/4),
+ *     evaluated as two square roots],   rgb_c = gain weight_c / expm1(theta_c / (g T_em)),   theta_c = h c / (lambda_c k_B).
+ *   An invalid emitter, g <= 0 or T_em <= 0 gives BLACK (0, 0, 0) and g = NaN: a disk region with no circular orbit emits nothing.
+ *   r_in is the Disk's own (rtgr_object.p[1]).  No operation of the function is fused, so the hook below predicts a pixel to the bit.
+ *
+ * rtgr_trace_emission_device_*.  Order of work: the plain frame (as rtgr_trace_shaded_device_*: the whole ni x nj canvas of `cam`), the
+ * textures of `shade` (may be NULL), the emission kernel.  d_g (n scalars, may be NULL) receives g on the disk's pixels and NaN on every
+ * other.  `out`, ctr, d_refined, stats, the scratch (grow-only, with the stream's state, retired until rtgr_trim) and the capture rules
+ * are those of rtgr_trace_shaded_device_*: the call may be captured when aa == NULL and ctr == NULL, once workspace and scratch are
+ * large enough.  With `aa`: pass 1 is shaded and emitted before the edge rule reads it, the sub-rays of pass 2 are emitted from their
+ * own sub-ray states before the reduction, and d_g is pass 1's (the pixel-centre rays').  So uniform == the box filter of the emitted
+ * (k ni) x (k nj) frame and adaptive == where(refined, uniform, emitted plain), bit for bit.
+ *   rtgr_trace_emission_f64 / _f32 (host pointers) run the same on device 0 of the context and copy out.
+ *   RTGR_ERR_BAD_ARG (with a message): a null emit or cam; object 0, > nobj or not a Disk; a disk that `shade` also binds; an unknown
+ * emitter or flags, pad != 0; KEPLER with orbit other than +1 / -1; a non-finite orbit; T_in, gain or a theta_c that is <= 0 or NaN; a
+ * weight_c < 0 (or NaN); a non-finite p; a scene whose metric is RTGR_USER (its kernels live in the unit) or a 4-D grid (not
+ * stationary); the refusals of rtgr_trace_shaded_* and of anti-aliasing.
+ *   In scope: the built-in metrics (closed and generic flags alike), 3-D grids, object lists of any length, both scalar types.
+ *   Out of scope: emission inside the innermost stable orbit (plunging gas), more than one emitting disk per call, limb darkening, a
+ * colour-matching-function integral, RTGR_USER metrics and 4-D grids, the sharded, frames-in-flight, pixel-array and single-ray entry
+ * points.
+ *
+ * rtgr_eval_disk_emission_*: the same device function at n pairs of states on device 0 (host pointers) — s0, s_end: n x 8; omega: n;
+ * u_emit: n x 4; g: n; rgb: n x 3 (AoS).  Any output may be NULL.  An invalid point gives NaN, NaN, NaN and black. */
+enum rtgr_emitter { RTGR_EMIT_KEPLER = 0, RTGR_EMIT_RIGID = 1 };
+#define RTGR_EMIT_INNER_EDGE 1u
+typedef struct rtgr_disk_emission {
+    uint32_t object;   /* 1-based index of a Disk in the caller's list */
+    uint32_t emitter;  /* rtgr_emitter */
+    uint32_t flags;    /* 0 | RTGR_EMIT_INNER_EDGE */
+    uint32_t pad;      /* 0 */
+    double orbit;      /* KEPLER: +1 = the root Omega_+ (counter-clockwise from +z), -1 = Omega_-; RIGID: Omega itself (0: xi = d_t) */
+    double T_in, p, gain;
+    double theta[3], weight[3];
+} rtgr_disk_emission;  /* 96 bytes: object 0, emitter 4, flags 8, pad 12, orbit 16, T_in 24, p 32, gain 40, theta 48, weight 72 */
+int rtgr_trace_emission_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                                   uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                                   const rtgr_aa* aa /* may be NULL */, double* d_rgb, const rtgr_ray_outputs* out,
+                                   double* d_g /* n, may be NULL */, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
+int rtgr_trace_emission_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                                   uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                                   const rtgr_aa* aa /* may be NULL */, float* d_rgb, const rtgr_ray_outputs* out,
+                                   float* d_g /* n, may be NULL */, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
+int rtgr_trace_emission_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                            uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                            const rtgr_aa* aa /* may be NULL */, double* rgb, const rtgr_ray_outputs* out, double* g /* n, may be NULL */,
+                            uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats);
+int rtgr_trace_emission_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni,
+                            uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                            const rtgr_aa* aa /* may be NULL */, float* rgb, const rtgr_ray_outputs* out, float* g /* n, may be NULL */,
+                            uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats);
+int rtgr_eval_disk_emission_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const double* s0 /* n x 8 */,
+                                const double* s_end /* n x 8 */, uint64_t n, double* omega /* n */, double* u_emit /* n x 4 */,
+                                double* g /* n */, double* rgb /* n x 3 */);
+int rtgr_eval_disk_emission_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const float* s0 /* n x 8 */,
+                                const float* s_end /* n x 8 */, uint64_t n, float* omega /* n */, float* u_emit /* n x 4 */,
+                                float* g /* n */, float* rgb /* n x 3 */);
 
 /* ---- camera: make_canvas (src/RayTraceGR.jl:457-478) on the device ------------------------------------------
  * Writes n x 8 ray states (pos, null past-directed 4-velocity) for rows [j0, j1).  Device / host variants. */

@@ -30,6 +30,7 @@
 #   RtgrTextureDesc  16   width 0, height 4, flags 8, pad 12
 #   RtgrTextureBind  16   object 0, filter 4, texture 8
 #   RtgrShade        24   nbind 0, flags 4, bind 8, r_escape 16
+#   RtgrDiskEmission 96   object 0, emitter 4, flags 8, pad 12, orbit 16, T_in 24, p 32, gain 40, theta 48, weight 72
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64          (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -126,6 +127,18 @@ struct RtgrShade               # the binds of a shaded frame (rtgr_trace_shaded_
     bind::Ptr{RtgrTextureBind}
     r_escape::Float64           # a miss counts as escaped when the Euclidean |x_end| >= r_escape
 end
+struct RtgrDiskEmission        # an orbiting disk that glows as a black body (rtgr_trace_emission_f64 / _f32)
+    object::UInt32              # 1-based index of a Disk in `objs`
+    emitter::UInt32             # RTGR_EMIT_KEPLER / RTGR_EMIT_RIGID
+    flags::UInt32               # 0 | RTGR_EMIT_INNER_EDGE
+    pad::UInt32                 # 0
+    orbit::Float64              # KEPLER: +1 = Omega_+ (counter-clockwise seen from +z), -1 = Omega_-; RIGID: Omega itself
+    T_in::Float64               # T_em(rho) = T_in (rho / r_in)^(-p)
+    p::Float64
+    gain::Float64
+    theta::NTuple{3,Float64}    # h c / (lambda_c k_B) per channel
+    weight::NTuple{3,Float64}
+end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
     lambda_end::Ptr{Cvoid}
@@ -156,6 +169,9 @@ const RTGR_RAY_NAN = UInt8(4)
 const RTGR_RAY_OUTSIDE = UInt8(5)
 const RTGR_TEX_NEAREST = UInt32(0)
 const RTGR_TEX_BILINEAR = UInt32(1)
+const RTGR_EMIT_KEPLER = UInt32(0)
+const RTGR_EMIT_RIGID = UInt32(1)
+const RTGR_EMIT_INNER_EDGE = UInt32(1)
 
 function check(rc)
     rc < 0 && error("librtgr_hip: ", unsafe_string(ccall((:rtgr_last_error, librtgr), Cstring, ())))
@@ -787,6 +803,55 @@ function trace_rays_shaded(metric, objs, pos, widthx, widthy, normal, ni::Intege
         end
     end
     (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3])
+end
+
+"""
+    disk_emission(object, T_in; p = 0.75, orbit = 1, emitter = RTGR_EMIT_KEPLER, inner_edge = false, gain = 1.0,
+                  wavelengths_nm = (700.0, 546.1, 435.8)) -> RtgrDiskEmission
+
+The parameters of an emitting disk for `trace_rays_emission`: `object` is the 1-based index of a `Disk` in `objs`; the three channels are
+Planck's law at `wavelengths_nm`, theta_c = h c / (lambda_c k_B) and weight_c = (546.1 / lambda_c)^5.
+"""
+function disk_emission(object::Integer, T_in::Real; p::Real = 0.75, orbit::Real = 1, emitter::UInt32 = RTGR_EMIT_KEPLER, inner_edge::Bool = false,
+                       gain::Real = 1.0, wavelengths_nm = (700.0, 546.1, 435.8))
+    lam = Float64.(Tuple(wavelengths_nm))
+    length(lam) == 3 || error("disk_emission: wavelengths_nm needs three wavelengths (r, g, b)")
+    RtgrDiskEmission(UInt32(object), emitter, inner_edge ? RTGR_EMIT_INNER_EDGE : UInt32(0), UInt32(0), Float64(orbit), Float64(T_in), Float64(p),
+                     Float64(gain), 1.438776877e7 ./ lam, (546.1 ./ lam) .^ 5)
+end
+
+"""
+    trace_rays_emission(metric, objs, pos, widthx, widthy, normal, ni, nj, emission; T = Float64, ctx = nothing) -> ((R, G, B), g)
+
+A frame with an EMITTING DISK (`rtgr_trace_emission_f64/_f32`) — an extension: `render`'s frame with the pixels that hit the `Disk`
+`emission.object` coloured as a black body on the circular orbits of the scene's own metric (include/rtgr.h "disk emission"), shifted by
+the frequency ratio `g`, which comes back as an `ni x nj` matrix (NaN off the disk and where no circular orbit exists: black).  Every
+other pixel keeps `render`'s bits.  `emission` from `disk_emission`.  Built-in metrics and 3-D grids; runs on device 0 of `ctx`.
+"""
+function trace_rays_emission(metric, objs, pos, widthx, widthy, normal, ni::Integer, nj::Integer, emission::RtgrDiskEmission;
+                             T::Type = Float64, ctx = nothing)
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("trace_rays_emission has no CPU counterpart in the reference: ", why)
+    opt = solver_of(T)
+    cam = camera_of(pos, widthx, widthy, normal)
+    rgb = Array{T}(undef, ni, nj, 3)                # plane-major: rgb[:, :, c] is plane c
+    g = Array{T}(undef, ni, nj)
+    ctr = Ref{RtgrCounters}()
+    emit = Ref(emission)
+    GC.@preserve rgb g begin
+        if T === Float64
+            check(ccall((:rtgr_trace_emission_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrCamera}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission}, Ptr{RtgrAA},
+                         Ptr{Float64}, Ptr{RtgrRayOutputs}, Ptr{Float64}, Ptr{UInt8}, Ptr{RtgrCounters}, Ptr{RtgrAAStats}),
+                        handle(ctx), scene, opt, cam, ni, nj, C_NULL, emit, C_NULL, pointer(rgb), C_NULL, pointer(g), C_NULL, ctr, C_NULL))
+        else
+            check(ccall((:rtgr_trace_emission_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrCamera}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission}, Ptr{RtgrAA},
+                         Ptr{Float32}, Ptr{RtgrRayOutputs}, Ptr{Float32}, Ptr{UInt8}, Ptr{RtgrCounters}, Ptr{RtgrAAStats}),
+                        handle(ctx), scene, opt, cam, ni, nj, C_NULL, emit, C_NULL, pointer(rgb), C_NULL, pointer(g), C_NULL, ctr, C_NULL))
+        end
+    end
+    (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), g
 end
 
 """

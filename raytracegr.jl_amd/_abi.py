@@ -25,6 +25,9 @@ PLANE, SPHERE, DISK, USER_OBJECT = 1, 2, 3, 4
 RAY_EVENT, RAY_LAMBDA1, RAY_MAXSTEPS, RAY_DTMIN, RAY_NAN, RAY_OUTSIDE = 0, 1, 2, 3, 4, 5
 # enum rtgr_tex_filter
 TEX_NEAREST, TEX_BILINEAR = 0, 1
+# enum rtgr_emitter, and the flag of rtgr_disk_emission.flags
+EMIT_KEPLER, EMIT_RIGID = 0, 1
+EMIT_INNER_EDGE = 1
 # enum rtgr_status
 OK, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NAN_INPUT, ERR_NOT_INIT = 0, -1, -2, -3, -4, -5
 
@@ -111,6 +114,12 @@ class rtgr_shade(C.Structure):
     _fields_ = [("nbind", C.c_uint32), ("flags", C.c_uint32), ("bind", C.POINTER(rtgr_texture_bind)), ("r_escape", C.c_double)]
 
 
+class rtgr_disk_emission(C.Structure):
+    """an orbiting, glowing disk (rtgr_trace_emission_*): object = 1-based index of a Disk; 96 bytes"""
+    _fields_ = [("object", C.c_uint32), ("emitter", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32), ("orbit", C.c_double),
+                ("T_in", C.c_double), ("p", C.c_double), ("gain", C.c_double), ("theta", C.c_double * 3), ("weight", C.c_double * 3)]
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -136,6 +145,8 @@ EXPORTS = [
     "rtgr_trace_aa_device_f64", "rtgr_trace_aa_device_f32", "rtgr_trace_aa_f64", "rtgr_trace_aa_f32",
     "rtgr_texture_load", "rtgr_texture_unload", "rtgr_trace_shaded_device_f64", "rtgr_trace_shaded_device_f32", "rtgr_trace_shaded_f64",
     "rtgr_trace_shaded_f32", "rtgr_eval_texture_f64", "rtgr_eval_texture_f32",
+    "rtgr_trace_emission_device_f64", "rtgr_trace_emission_device_f32", "rtgr_trace_emission_f64", "rtgr_trace_emission_f32",
+    "rtgr_eval_disk_emission_f64", "rtgr_eval_disk_emission_f32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -212,6 +223,13 @@ def _declare(lib):
             ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_camera), u64, u64, P(rtgr_shade), P(rtgr_aa), vp, P(rtgr_ray_outputs), vp,
             P(rtgr_counters), P(rtgr_aa_stats)]
         getattr(lib, f"rtgr_eval_texture_{suf}").argtypes = [ctx, u64, C.c_uint32, vp, u64, vp, vp]
+        getattr(lib, f"rtgr_trace_emission_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_camera), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_aa), vp,
+            P(rtgr_ray_outputs), vp, vp, P(rtgr_counters), P(rtgr_aa_stats), vp]
+        getattr(lib, f"rtgr_trace_emission_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_camera), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_aa), vp,
+            P(rtgr_ray_outputs), vp, vp, P(rtgr_counters), P(rtgr_aa_stats)]
+        getattr(lib, f"rtgr_eval_disk_emission_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_disk_emission), vp, vp, u64, vp, vp, vp, vp]
     lib.rtgr_texture_load.argtypes = [ctx, P(rtgr_texture_desc), vp, P(u64)]
     lib.rtgr_texture_unload.argtypes = [ctx, u64]
     lib.rtgr_eval_fastmath_f64.argtypes = [ctx, vp, u64, vp, vp]

@@ -557,6 +557,84 @@ def trace_shaded(metric, objs, cam, ni, nj, textures=None, r_escape=0.0, aa=None
     return res
 
 
+# ---- disk emission (include/rtgr.h "disk emission") -----------------------------------------------------------------------------
+HC_OVER_KB_NM = 1.438776877e7   # h c / k_B in nm K: theta_c = HC_OVER_KB_NM / lambda_c
+
+
+def DiskEmission(object, T_in, p=0.75, orbit=+1, emitter="kepler", inner_edge=False, gain=1.0, wavelengths_nm=(700.0, 546.1, 435.8)):
+    """An orbiting disk that glows as a black body -> rtgr_disk_emission.  object: the 1-based index of a Disk in objs (what `hit`
+    holds).  emitter "kepler": gas on the circular geodesics of the scene's own metric, orbit = +1 (counter-clockwise seen from +z) or
+    -1; "rigid": Omega = orbit everywhere (0: the static emitter).  T_em(rho) = T_in (rho / r_in)^(-p) [inner_edge: times
+    (1 - sqrt(r_in / rho))^(1/4)] in kelvin; the three channels are Planck's law at wavelengths_nm, normalised so that the middle
+    wavelength has weight 1: theta_c = h c / (lambda_c k_B), weight_c = (546.1 / lambda_c)^5."""
+    kinds = {"kepler": _abi.EMIT_KEPLER, "rigid": _abi.EMIT_RIGID}
+    if emitter not in kinds:
+        raise ValueError(f"DiskEmission: emitter must be 'kepler' or 'rigid', got {emitter!r}")
+    lam = [float(v) for v in wavelengths_nm]
+    if len(lam) != 3:
+        raise ValueError("DiskEmission: wavelengths_nm needs three wavelengths (r, g, b)")
+    return _abi.rtgr_disk_emission(object=int(object), emitter=kinds[emitter], flags=_abi.EMIT_INNER_EDGE if inner_edge else 0, pad=0,
+                                   orbit=float(orbit), T_in=float(T_in), p=float(p), gain=float(gain),
+                                   theta=(C.c_double * 3)(*[HC_OVER_KB_NM / v for v in lam]),
+                                   weight=(C.c_double * 3)(*[(546.1 / v) ** 5 for v in lam]))
+
+
+def trace_emission(metric, objs, cam, ni, nj, emission, textures=None, r_escape=0.0, aa=None, opt=None, dtype=np.float64, ctx=None, details=False):
+    """A frame with an EMITTING DISK (rtgr_trace_emission_f64 / _f32) — an extension: the plain ni x nj frame of the camera, the
+    textures (as trace_shaded: {omin: (texture, filter), 0: …}; not on the emitting disk), then the pixels that hit the disk of
+    `emission` (a DiskEmission) get the black-body colour of the orbiting gas, shifted by the frequency ratio g; every other pixel
+    keeps its bits.  aa: None, or dict(k=…, contrast=…, max_batch_rays=…) / an rtgr_aa — adaptive anti-aliasing of the emitted frame.
+    -> dict(rgb [3, ni*nj], g [ni*nj] (NaN off the disk and where nothing emits), counters; aa: + refined, stats; details: + the
+    per-ray outputs of the pixel-centre rays)."""
+    lib = _lib()
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    camera = cam if isinstance(cam, rtgr_camera) else make_camera(**cam)
+    n = ni * nj
+    sh = make_shade(textures, r_escape) if textures else None
+    res = dict(rgb=np.zeros((3, n), dtype), g=np.zeros(n, dtype))
+    aap = refined = stats = None
+    if aa is not None:
+        aap = aa if isinstance(aa, _abi.rtgr_aa) else _abi.rtgr_aa(k=int(aa.get("k", 4)), flags=0, contrast=float(aa.get("contrast", 1.0 / 255.0)),
+                                                                     max_batch_rays=int(aa.get("max_batch_rays", 0)))
+        res["refined"] = np.zeros(n, np.uint8)
+        refined, stats = res["refined"].ctypes.data, _abi.rtgr_aa_stats()
+    outs = None
+    if details:
+        outs = rtgr_ray_outputs()
+        wide = sc.nobj > 255
+        res.update(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
+                   hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
+        for name in ("state_end", "lambda_end", "status", "hit", "n_accept", "n_reject"):
+            setattr(outs, "hit32" if (wide and name == "hit") else name, res[name].ctypes.data)
+    ctr = rtgr_counters()
+    fn = lib.rtgr_trace_emission_f64 if dtype == np.float64 else lib.rtgr_trace_emission_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(camera), ni, nj, None if sh is None else C.byref(sh), C.byref(emission), aap, res["rgb"].ctypes.data, outs,
+                       res["g"].ctypes.data, refined, C.byref(ctr), stats))
+    res["counters"] = ctr.as_dict()
+    if stats is not None:
+        res["stats"] = stats.as_dict()
+    return res
+
+
+def eval_disk_emission(metric, objs, emission, s0, s_end, dtype=np.float64, ctx=None):
+    """rtgr_eval_disk_emission_f64 / _f32: the emitter model at n pairs of ray states — s0 [n, 8] at the camera (make_canvas' states),
+    s_end [n, 8] on the disk.  -> dict(omega [n], u_emit [n, 4], g [n], rgb [n, 3]); a point with no valid emitter gives NaN, NaN,
+    NaN and black."""
+    lib = _lib()
+    sc = make_scene(metric, objs, ctx)
+    a = np.ascontiguousarray(s0, dtype=dtype).reshape(-1, 8)
+    e = np.ascontiguousarray(s_end, dtype=dtype).reshape(-1, 8)
+    if a.shape != e.shape:
+        raise ValueError(f"eval_disk_emission: s0 and s_end must have the same shape, got {a.shape} and {e.shape}")
+    n = a.shape[0]
+    res = dict(omega=np.zeros(n, dtype), u_emit=np.zeros((n, 4), dtype), g=np.zeros(n, dtype), rgb=np.zeros((n, 3), dtype))
+    fn = lib.rtgr_eval_disk_emission_f64 if dtype == np.float64 else lib.rtgr_eval_disk_emission_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(emission), a.ctypes.data, e.ctypes.data, n, res["omega"].ctypes.data, res["u_emit"].ctypes.data,
+                       res["g"].ctypes.data, res["rgb"].ctypes.data))
+    return res
+
+
 def trace_ray(metric, objs, cb, p, opt=None, ctx=None):
     """Legacy single-pixel shape `trace_ray(metric, objs, cb, p)::Pixel` (test/runtests.jl:65-79).
     `cb` is accepted for signature parity and ignored: the callback is always
@@ -666,5 +744,5 @@ def example2(ni=200, nj=200, save=True, ctx=None):
 
 __all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
-           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "dmetric", "christoffel", "geodesic", "example1", "example2",
+           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

@@ -1,8 +1,10 @@
 // rtgr_aa_host.hip — adaptive anti-aliasing (include/rtgr.h "adaptive anti-aliasing"): the plain frame, the edge rule over it, and a
 // sparse second trace of the flagged pixels' k x k sub-rays, averaged back into the frame.  Host side only: both traces are
 // trace_device — the integrate / prepare / resolve kernels run as for any other call, the sub-rays as caller-supplied ray states —
-// and the three small kernels in between are rtgr_aa.hip's.  With a shade description (rtgr_trace_shaded_*, rtgr_texture_host.hip) both
-// traces also deliver their end states and the shading kernel runs behind each; without one nothing of that exists.
+// and the three small kernels in between are rtgr_aa.hip's.  With an AfterTrace — what is applied to a traced frame before its colours
+// are read: the textures of rtgr_trace_shaded_* (rtgr_texture_host.hip), the emitting disk of rtgr_trace_emission_* (rtgr_emission_host.hip)
+// or both — the two traces also deliver their end states and the shading / emission kernels run behind each; without one nothing of
+// that exists.
 #include "rtgr_internal.hpp"
 
 namespace rtgr {
@@ -40,7 +42,7 @@ int aa_need(StreamState& ss, void*& p, size_t& have, size_t bytes) {
 template <class R>
 int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
                 const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats,
-                hipStream_t st, const ShadeDesc<R>* shade) {
+                hipStream_t st, const AfterTrace<R>* after) {
     int rc;
     if ((rc = aa_check(scene, cam, aa, ni, nj))) return rc;
     DeviceGuard guard(D.dev);
@@ -52,9 +54,12 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
     const uint64_t n = ni * nj;
     const uint32_t k = aa->k, kk = k * k;
     const bool want_status = !(out && out->status), want_hit32 = !(out && out->hit32);
-    const bool want_state = shade && !(out && out->state_end);   // (the shading kernel reads the end states)
+    const ShadeDesc<R>* shade = after ? after->shade : nullptr;
+    const DevEmission<R>* emit = after ? after->emit : nullptr;
+    const bool post = shade || emit;
+    const bool want_state = post && !(out && out->state_end);   // (the shading and emission kernels read the end states)
 
-    // ---- frame scratch: [counters | count] [hit32] [status] [list] [end states: shaded frames only] -------------------------------
+    // ---- frame scratch: [counters | count] [hit32] [status] [list] [end states: shaded / emitted frames only] -------------------------------
     const size_t off_hit = AA_HEAD, off_status = off_hit + (want_hit32 ? align256(n * sizeof(uint32_t)) : 0),
                  off_list = off_status + (want_status ? align256(n) : 0), off_state = off_list + align256(n * sizeof(uint64_t)),
                  frame_bytes = off_state + (want_state ? align256(n * 8 * sizeof(R)) : 0);
@@ -79,18 +84,26 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
     if (want_status) o1.status = (uint8_t*)(frame + off_status);
     if (want_state) o1.state_end = frame + off_state;
     if ((rc = trace_device<R>(D, scene, opt, nullptr, cam, ni, nj, 0, nj, d_rgb, &o1, ctr ? d_ctr : nullptr, st))) return rc;
+    {
+        std::lock_guard<std::mutex> lk(D.mu);
+        const UserModule* user = nullptr;
+        if ((rc = convert_scene<R>(D, scene, sc, &user, st))) return rc;   // (what the sub-ray and emission kernels read of the scene: its metric)
+        convert_camera<R>(cam, cm);
+    }
     if (shade) {   // the edge rule reads the SHADED colours
         std::lock_guard<std::mutex> lk(D.mu);
         KernelTimer timer(D, st, 0);
         if ((rc = shade_launch<R>(ShadeArgs<R>{d_rgb, o1.hit32, o1.status, (const R*)o1.state_end, n, n, *shade}, st))) return rc;
     }
+    if (emit) {    // … and the EMITTED ones; the pixel-centre rays start from the camera's own pixels
+        std::lock_guard<std::mutex> lk(D.mu);
+        KernelTimer timer(D, st, 0);
+        if ((rc = emit_launch<R>(EmitArgs<R>{d_rgb, after->d_g, nullptr, nullptr, o1.hit32, (const R*)o1.state_end, nullptr, n, n, 1, ni, nj, sc, cm, *emit}, st))) return rc;
+    }
 
     // ---- the edge rule -------------------------------------------------------------------------------------------------------------
     {
         std::lock_guard<std::mutex> lk(D.mu);
-        const UserModule* user = nullptr;
-        if ((rc = convert_scene<R>(D, scene, sc, &user, st))) return rc;   // (what the sub-ray kernel reads of the scene: its metric)
-        convert_camera<R>(cam, cm);
         KernelTimer timer(D, st, 0);
         if ((rc = aa_flag<R>(d_rgb, o1.hit32, o1.status, ni, nj, (R)aa->contrast, aa->contrast < 0.0, d_refined, d_list, d_count, st))) return rc;
     }
@@ -105,10 +118,10 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
     const uint64_t batches = (count + per - 1) / per;
     const uint64_t m_max = count < per ? count : per;
     const size_t off_sub = align256((size_t)m_max * kk * 8 * sizeof(R));   // batch scratch: [sub-ray states] [sub-colours, 3 planes]
-    // … and for a shaded frame what the shading kernel reads of the sub-rays: [end states] [hit32] [status]
-    const size_t off_end = off_sub + align256((size_t)m_max * kk * 3 * sizeof(R)), off_hit2 = off_end + (shade ? align256((size_t)m_max * kk * 8 * sizeof(R)) : 0),
-                 off_status2 = off_hit2 + (shade ? align256((size_t)m_max * kk * sizeof(uint32_t)) : 0),
-                 batch_bytes = off_status2 + (shade ? align256((size_t)m_max * kk) : 0);
+    // … and for a shaded or emitted frame what those kernels read of the sub-rays: [end states] [hit32] [status]
+    const size_t off_end = off_sub + align256((size_t)m_max * kk * 3 * sizeof(R)), off_hit2 = off_end + (post ? align256((size_t)m_max * kk * 8 * sizeof(R)) : 0),
+                 off_status2 = off_hit2 + (post ? align256((size_t)m_max * kk * sizeof(uint32_t)) : 0),
+                 batch_bytes = off_status2 + (post ? align256((size_t)m_max * kk) : 0);
     if (count) {
         std::lock_guard<std::mutex> lk(D.mu);
         if ((rc = aa_need(*ss, ss->aa_batch, ss->aa_batch_bytes, batch_bytes))) return rc;
@@ -124,16 +137,21 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
         }
         rtgr_ray_outputs o2;
         std::memset(&o2, 0, sizeof o2);
-        if (shade) {
+        if (post) {
             o2.state_end = (char*)ss->aa_batch + off_end;
             o2.hit32 = (uint32_t*)((char*)ss->aa_batch + off_hit2);
             o2.status = (uint8_t*)((char*)ss->aa_batch + off_status2);
         }
-        if ((rc = trace_device<R>(D, scene, opt, d_states, nullptr, m * kk, 1, 0, 1, d_sub, shade ? &o2 : nullptr, ctr ? d_ctr : nullptr, st))) return rc;
+        if ((rc = trace_device<R>(D, scene, opt, d_states, nullptr, m * kk, 1, 0, 1, d_sub, post ? &o2 : nullptr, ctr ? d_ctr : nullptr, st))) return rc;
         if (shade) {   // the sub-rays as a one-row canvas of m k² pixels
             std::lock_guard<std::mutex> lk(D.mu);
             KernelTimer timer(D, st, 0);
             if ((rc = shade_launch<R>(ShadeArgs<R>{d_sub, o2.hit32, o2.status, (const R*)o2.state_end, m * kk, m * kk, *shade}, st))) return rc;
+        }
+        if (emit) {    // … each emitted from its own sub-ray state
+            std::lock_guard<std::mutex> lk(D.mu);
+            KernelTimer timer(D, st, 0);
+            if ((rc = emit_launch<R>(EmitArgs<R>{d_sub, nullptr, nullptr, nullptr, o2.hit32, (const R*)o2.state_end, d_states, m * kk, m * kk, 1, 0, 0, sc, cm, *emit}, st))) return rc;
         }
         {
             std::lock_guard<std::mutex> lk(D.mu);

@@ -177,6 +177,9 @@ struct StreamState {
     // scratch of rtgr_trace_shaded_device_* without anti-aliasing (rtgr_texture_host.hip), likewise: the counters, then the end states /
     // hit map / status bytes the shading kernel reads and the caller did not ask for
     void* shade_frame = nullptr; size_t shade_frame_bytes = 0;
+    // scratch of rtgr_trace_emission_device_* without anti-aliasing (rtgr_emission_host.hip), likewise: the counters, then the end states /
+    // hit map / status bytes the emission and shading kernels read and the caller did not ask for
+    void* emit_frame = nullptr; size_t emit_frame_bytes = 0;
 };
 
 struct Staging;  // host entry points (rtgr_internal.hpp)
@@ -342,5 +345,41 @@ int shade_launch(const ShadeArgs<R>& A, hipStream_t st);
 template <class R>
 int eval_texture_launch(const R* d_tex, uint32_t W, uint32_t H, uint32_t filter, bool disk, R r_in, R r_out, const R* d_p, uint64_t n, R* d_rgb,
                         hipStream_t st);
+// disk emission (rtgr_emit.hip; include/rtgr.h "disk emission").  The caller's rtgr_disk_emission as the kernels read it, converted by
+// the host for one scalar type; r_in is the emitting disk's, from the caller's object list.
+template <class R>
+struct DevEmission {
+    uint32_t object, emitter, flags, pad;
+    R orbit, T_in, p, gain, r_in;
+    R theta[3], weight[3];
+};
+// the emission kernel's argument block.  Frame mode (hit32 given): n pixels, colour planes plane_stride apart (pixel_stride 1), g: the
+// frequency ratio per pixel (may be null); state0: the rays' start states when they were caller-supplied (the sub-rays of anti-aliasing),
+// null: pixel idx of the ni x nj canvas of cam.  Point mode (hit32 null; rtgr_eval_disk_emission_*): n pairs (state0, state_end), every
+// output optional, rgb n x 3 (plane_stride 1, pixel_stride 3).
+template <class R>
+struct EmitArgs {
+    R* rgb;
+    R* g;
+    R* omega;
+    R* u_emit;
+    const uint32_t* hit32;
+    const R* state_end;
+    const R* state0;
+    uint64_t n, plane_stride, pixel_stride, ni, nj;
+    DevScene<R> sc;
+    DevCamera<R> cam;
+    DevEmission<R> em;
+};
+template <class R>
+int emit_launch(const EmitArgs<R>& A, hipStream_t st);
+// What is applied to a traced frame before anyone reads its colours (trace_aa_on, rtgr_aa_host.hip): the textures of a shaded frame,
+// then the emission of a disk — either may be null.  d_g: the frequency ratios of the pixel-centre rays (pass 1), or null.
+template <class R>
+struct AfterTrace {
+    const ShadeDesc<R>* shade = nullptr;
+    const DevEmission<R>* emit = nullptr;
+    R* d_g = nullptr;
+};
 
 }  // namespace rtgr

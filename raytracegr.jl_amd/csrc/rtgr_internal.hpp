@@ -9,6 +9,8 @@
 //   rtgr_aa_host.hip        adaptive anti-aliasing: the plain frame, the edge rule, a sparse second trace (kernels: rtgr_aa.hip)
 //   rtgr_texture_host.hip   image textures: load / unload, the shaded trace (a plain or anti-aliased trace + the shading kernel), the
 //                           sampler hook (kernels: rtgr_shade.hip)
+//   rtgr_emission_host.hip  disk emission: the emitted trace (a plain, shaded and / or anti-aliased trace + the emission kernel), the
+//                           pointwise hook (kernels: rtgr_emit.hip)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -141,12 +143,16 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
 // ---- adaptive anti-aliasing on one device (rtgr_aa_host.hip), optionally of a SHADED frame (rtgr_texture_host.hip) ---------------
 // grow-only scratch of a stream, retired like its workspace (D.mu held; never called during capture: the entry points refuse first)
 int aa_need(StreamState& ss, void*& p, size_t& have, size_t bytes);
-// the call on device D, stream st; d_rgb, the members of `out` and d_refined are pointers of that device.  shade == nullptr: the plain
-// anti-aliased frame; otherwise both passes are shaded with these (resolved) binds
+// the call on device D, stream st; d_rgb, the members of `out` and d_refined are pointers of that device.  after == nullptr: the plain
+// anti-aliased frame; otherwise both passes are shaded with its (resolved) binds and / or emitted with its disk (AfterTrace, rtgr_host.hpp)
 template <class R>
 int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
                 const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats,
-                hipStream_t st, const ShadeDesc<R>* shade);
+                hipStream_t st, const AfterTrace<R>* after);
+// image textures (rtgr_texture_host.hip), shared with the emitted trace: the caller's binds into the records the shading kernel reads, for
+// device D and scalar type R (takes D.mu), and the checks of a shaded frame's arguments
+template <class R> int shade_resolve(DeviceCtx& D, const rtgr_scene* scene, const rtgr_shade* shade, ShadeDesc<R>& sd);
+int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refined, const rtgr_aa_stats* stats, uint64_t ni, uint64_t nj);
 
 // scratch device buffers of the small host-pointer hooks (eval_*, make_canvas, the probe): RAII, synchronous
 struct DevBuf {
@@ -287,6 +293,9 @@ int texture_unload(rtgr_context* ctx, uint64_t id);
 template <class R> int trace_shaded_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
 template <class R> int trace_shaded(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_aa* aa, R* rgb, const rtgr_ray_outputs* out, uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats);
 template <class R> int eval_texture(rtgr_context* ctx, uint64_t texture, uint32_t filter, const R* p, uint64_t n, const R* disk_range, R* rgb);
+template <class R> int trace_emission_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
+template <class R> int trace_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_aa* aa, R* rgb, const rtgr_ray_outputs* out, R* g, uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats);
+template <class R> int eval_disk_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const R* s0, const R* s_end, uint64_t n, R* omega, R* u_emit, R* g, R* rgb);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 

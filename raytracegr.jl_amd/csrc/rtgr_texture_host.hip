@@ -106,7 +106,7 @@ static int filter_check(uint32_t filter) {
 
 // the caller's binds into the records the shading kernel reads, for device D and scalar type R (takes D.mu: the texture tables)
 template <class R>
-static int shade_resolve(DeviceCtx& D, const rtgr_scene* scene, const rtgr_shade* shade, ShadeDesc<R>& sd) {
+int shade_resolve(DeviceCtx& D, const rtgr_scene* scene, const rtgr_shade* shade, ShadeDesc<R>& sd) {
     if (!scene) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
     if (!shade) return fail(RTGR_ERR_BAD_ARG, "rtgr_shade is NULL");
     if (shade->flags != 0) return fail(RTGR_ERR_BAD_ARG, "rtgr_shade.flags must be 0");
@@ -146,7 +146,7 @@ static int shade_resolve(DeviceCtx& D, const rtgr_scene* scene, const rtgr_shade
     return RTGR_OK;
 }
 
-static int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refined, const rtgr_aa_stats* stats, uint64_t ni, uint64_t nj) {
+int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refined, const rtgr_aa_stats* stats, uint64_t ni, uint64_t nj) {
     if (!cam) return fail(RTGR_ERR_BAD_ARG, "a shaded frame needs a camera (cam is NULL)");
     if (!aa && (refined || stats)) return fail(RTGR_ERR_BAD_ARG, "refined and stats belong to anti-aliasing: they must be NULL when aa is NULL");
     if (ni == 0 || nj == 0 || ni > (1ull << 32) || nj > (1ull << 32) || ni * nj > (1ull << 34))
@@ -164,7 +164,11 @@ static int trace_shaded_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_sol
     if ((rc = check_redshift_outputs(out))) return rc;
     ShadeArgs<R> A;
     if ((rc = shade_resolve<R>(D, scene, shade, A.desc))) return rc;
-    if (aa) return trace_aa_on<R>(D, scene, opt, cam, ni, nj, aa, d_rgb, out, d_refined, ctr, stats, st, &A.desc);
+    if (aa) {
+        AfterTrace<R> after;
+        after.shade = &A.desc;
+        return trace_aa_on<R>(D, scene, opt, cam, ni, nj, aa, d_rgb, out, d_refined, ctr, stats, st, &after);
+    }
     DeviceGuard guard(D.dev);
     if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -297,6 +301,7 @@ int api::eval_texture(rtgr_context* ctx, uint64_t texture, uint32_t filter, cons
     return RTGR_OK;
 }
 
+RTGR_INSTANTIATE_F64_F32(shade_resolve);
 RTGR_INSTANTIATE_F64_F32(api::trace_shaded_device);
 RTGR_INSTANTIATE_F64_F32(api::trace_shaded);
 RTGR_INSTANTIATE_F64_F32(api::eval_texture);
