@@ -619,6 +619,109 @@ int rtgr_eval_disk_emission_f32(rtgr_context* ctx, const rtgr_scene* scene, cons
                                 const float* s_end /* n x 8 */, uint64_t n, float* omega /* n */, float* u_emit /* n x 4 */,
                                 float* g /* n */, float* rgb /* n x 3 */);
 
+/* ---- observer camera: a pinhole carried by a static, moving or orbiting observer ---------------------------------------------
+ * AN EXTENSION: the reference's make_canvas spreads its ray origins over a plane and gives every pixel a static observer of its own.
+ * An rtgr_observer is a camera one can aim: ONE event, an observer with a 4-velocity, an orthonormal frame (tetrad) built from "look"
+ * and "up", a field of view.  An observer trace builds the frame (one small kernel), writes the rays' start states (one kernel, 8
+ * scalars per ray) and hands them to the untouched trace as caller-supplied states, a batch of whole rows at a time; no kernel of the
+ * trace itself changes, and a ray is, bit for bit, the ray rtgr_trace_* traces from the state rtgr_make_observer_canvas_* delivers.
+ *
+ * The frame (csrc/rtgr_observer.hpp, in the entry point's scalar type; every inner product with g = the metric at pos).
+ *   kind   RTGR_OBS_STATIC    u = -g^{-1} e_t, normalised, future-directed: exactly the observer of make_canvas and of
+ *                             rtgr_ray_outputs.redshift.
+ *          RTGR_OBS_VELOCITY  u = vel, the caller's coordinate 4-velocity, normalised with g (as rtgr_object's `vel` of a Sphere is).
+ *          RTGR_OBS_CIRCULAR  u along xi = d_t + Omega psi, psi = (0, -y, x, 0), Omega the root `orbit` (+1 / -1) of the quadratic of
+ *                             "disk emission" above at pos — the same device function, the same bits; pos must lie in the plane z = 0.
+ *   e_0     = u / sqrt(-g(u, u))
+ *   e_look  = normalise(look + g(look, e_0) e_0)
+ *   e_up    = normalise(up + g(up, e_0) e_0 - g(up, e_look) e_look)
+ *   e_right = the unit vector orthogonal to the three, oriented "right = look x up in flat space at rest": lowered,
+ *             (e_right)_a = -sqrt(-det g) eps_{abcd} e_0^b e_look^c e_up^d with eps_0123 = +1; raised with g^{-1}.  (Minkowski, u = d_t,
+ *             look = +y, up = +z: e_right = +x — example2's widthx / normal / widthy.)
+ *   look and up are coordinate vectors; only their parts orthogonal to u (and, for up, to the look axis) matter.
+ *   INVALID (no error: the frame is built on the device) iff u is not timelike or not future-directed (u^t <= 0); for CIRCULAR the
+ *   quadratic has no real root, C = 0 or g(xi, xi) >= 0; det g >= 0; look or up is degenerate after projection (squared norm of the
+ *   projected vector <= 4096 eps times sum |v^a g_ab v^b| of the given one); anything is not finite.
+ * The pixel (i, j), 0-based, i along e_right, j along e_up, output index i + j ni:  a = 2 (i + 1/2) / ni - 1,  b = 2 (j + 1/2) / nj - 1.
+ *   RTGR_PROJ_PERSPECTIVE  n = normalise(e_look + a tan(fov_x / 2) e_right + b tan(fov_y / 2) e_up); fov_x, fov_y in (0, pi), radians.
+ *   RTGR_PROJ_EQUIRECT     alpha = a fov_x / 2, beta = b fov_y / 2, n = cos beta (cos alpha e_look + sin alpha e_right) + sin beta e_up;
+ *                          0 < fov_x <= 2 pi, 0 < fov_y <= pi (the full sky: 2 pi x pi).
+ *   state: x = pos, k = (-e_0 + n) / sqrt(2): null, past-directed, make_canvas' normalisation (g(k, e_0) = +1 / sqrt(2)).
+ *   No operation of the frame's and the pixel's own arithmetic is fused; tan(fov / 2) is taken on the host in double.
+ *   An INVALID frame writes NaN into every state: the trace ends those rays as RTGR_RAY_NAN (not_finished = n) and returns RTGR_OK.
+ *   rtgr_eval_observer_* says up front whether a frame is valid.
+ *
+ * rtgr_trace_observer_device_*.  Order of work: the frame kernel; then, for batches of whole rows of at most max_batch_rays rays (at
+ * least one row): the ray kernel into the stream's scratch, the plain trace of those states into the caller's planes, the textures of
+ * `shade` (may be NULL), the emission kernel of `emit` (may be NULL).  d_g (n scalars, may be NULL; needs emit) receives the frequency
+ * ratio on the disk's pixels and NaN elsewhere.  With `emit`, u_obs in g = (k_0 . u_obs) / (k_end . u_emit) is THIS observer's e_0 —
+ * not the static observer — so an orbiting camera sees its own Doppler shift and beaming.  Textures need the end states only.
+ *   The call only enqueues, apart from one synchronisation at the end when `ctr` is given; it may be captured with ctr == NULL once
+ * workspace and scratch (grow-only, with the stream's state, retired until rtgr_trim) are large enough — make one call of the same size
+ * on the stream first.  The result does not depend on max_batch_rays or on the stream.  (Under the experiment option tile = 1, whose
+ * kernel writes whole frames only, a frame of more than one batch is refused, as adaptive anti-aliasing's windows are.)
+ *   rtgr_trace_observer_f64 / _f32 (host pointers) run the same on device 0 of the context and copy out.
+ * rtgr_make_observer_canvas_device_* / rtgr_make_observer_canvas_*: the states of rows [j0, j1) (ni (j1 - j0) x 8), as rtgr_make_canvas_*.
+ * rtgr_eval_observer_* (blocking, host pointers): frame = 4 x 4, rows e_0, e_right, e_up, e_look; omega (NaN unless CIRCULAR); valid.
+ * Any output may be NULL.  rtgr_eval_disk_emission_observer_*: rtgr_eval_disk_emission_* with u_obs = the e_0 of `obs` (obs == NULL: the
+ * static observer, the same call as rtgr_eval_disk_emission_*).
+ *   RTGR_ERR_BAD_ARG (with a message): a null obs; an unknown kind or projection; flags or pad != 0; a non-finite pos, look, up, fov,
+ * orbit (CIRCULAR) or vel (VELOCITY); a fov outside its range; CIRCULAR with orbit other than +1 / -1 or with pos[3] != 0; a scene
+ * whose metric is RTGR_USER or a 4-D grid; out->redshift (its definition names the static observer: use d_g); ni or nj = 0 (or more
+ * than 2^34 pixels); d_g without emit; more than one batch under option tile = 1; the refusals of rtgr_trace_shaded_* and rtgr_trace_emission_*.
+ *   In scope: the built-in metrics (closed and generic), 3-D grids, object lists of any length, both scalar types, textures, emission.
+ *   Out of scope: anti-aliasing with this camera; the sharded, frames-in-flight, pixel-array and single-ray entry points; RTGR_USER
+ * metrics and 4-D grids; the redshift output; lenses other than the two projections; a camera path over time. */
+enum rtgr_observer_kind { RTGR_OBS_STATIC = 0, RTGR_OBS_VELOCITY = 1, RTGR_OBS_CIRCULAR = 2 };
+enum rtgr_projection { RTGR_PROJ_PERSPECTIVE = 0, RTGR_PROJ_EQUIRECT = 1 };
+typedef struct rtgr_observer {
+    double pos[4];            /* the event the observer is at */
+    double vel[4];            /* VELOCITY: coordinate 4-velocity (any normalisation); ignored otherwise */
+    double look[4], up[4];    /* coordinate vectors */
+    double fov_x, fov_y;      /* radians */
+    double orbit;             /* CIRCULAR: +1 = the root Omega_+, -1 = Omega_-; ignored otherwise */
+    uint32_t kind;            /* rtgr_observer_kind */
+    uint32_t projection;      /* rtgr_projection */
+    uint32_t flags;           /* 0 */
+    uint32_t pad;             /* 0 */
+    uint64_t max_batch_rays;  /* rays traced per batch at most; 0 = default (2^22); rounded down to whole rows, at least one */
+} rtgr_observer;  /* 176 bytes: pos 0, vel 32, look 64, up 96, fov_x 128, fov_y 136, orbit 144, kind 152, projection 156, flags 160,
+                     pad 164, max_batch_rays 168 */
+int rtgr_trace_observer_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                   uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit /* may be NULL */,
+                                   double* d_rgb, const rtgr_ray_outputs* out, double* d_g /* n, may be NULL */, rtgr_counters* ctr,
+                                   void* stream);
+int rtgr_trace_observer_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                   uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit /* may be NULL */,
+                                   float* d_rgb, const rtgr_ray_outputs* out, float* d_g /* n, may be NULL */, rtgr_counters* ctr,
+                                   void* stream);
+int rtgr_trace_observer_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                            uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit /* may be NULL */,
+                            double* rgb, const rtgr_ray_outputs* out, double* g /* n, may be NULL */, rtgr_counters* ctr);
+int rtgr_trace_observer_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                            uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit /* may be NULL */,
+                            float* rgb, const rtgr_ray_outputs* out, float* g /* n, may be NULL */, rtgr_counters* ctr);
+int rtgr_make_observer_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
+                                         uint64_t j0, uint64_t j1, double* d_state0, void* stream);
+int rtgr_make_observer_canvas_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
+                                         uint64_t j0, uint64_t j1, float* d_state0, void* stream);
+int rtgr_make_observer_canvas_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, uint64_t j0,
+                                  uint64_t j1, double* state0);
+int rtgr_make_observer_canvas_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, uint64_t j0,
+                                  uint64_t j1, float* state0);
+int rtgr_eval_observer_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, double* frame /* 4 x 4 */, double* omega,
+                           int* valid);
+int rtgr_eval_observer_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, float* frame /* 4 x 4 */, float* omega,
+                           int* valid);
+int rtgr_eval_disk_emission_observer_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit,
+                                         const rtgr_observer* obs /* may be NULL */, const double* s0 /* n x 8 */,
+                                         const double* s_end /* n x 8 */, uint64_t n, double* omega /* n */, double* u_emit /* n x 4 */,
+                                         double* g /* n */, double* rgb /* n x 3 */);
+int rtgr_eval_disk_emission_observer_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit,
+                                         const rtgr_observer* obs /* may be NULL */, const float* s0 /* n x 8 */,
+                                         const float* s_end /* n x 8 */, uint64_t n, float* omega /* n */, float* u_emit /* n x 4 */,
+                                         float* g /* n */, float* rgb /* n x 3 */);
+
 /* ---- camera: make_canvas (src/RayTraceGR.jl:457-478) on the device ------------------------------------------
  * Writes n x 8 ray states (pos, null past-directed 4-velocity) for rows [j0, j1).  Device / host variants. */
 int rtgr_make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni,

@@ -31,6 +31,7 @@
 #   RtgrTextureBind  16   object 0, filter 4, texture 8
 #   RtgrShade        24   nbind 0, flags 4, bind 8, r_escape 16
 #   RtgrDiskEmission 96   object 0, emitter 4, flags 8, pad 12, orbit 16, T_in 24, p 32, gain 40, theta 48, weight 72
+#   RtgrObserver    176   pos 0, vel 32, look 64, up 96, fov_x 128, fov_y 136, orbit 144, kind 152, projection 156, flags 160, pad 164, max_batch_rays 168
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64          (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -139,6 +140,20 @@ struct RtgrDiskEmission        # an orbiting disk that glows as a black body (rt
     theta::NTuple{3,Float64}    # h c / (lambda_c k_B) per channel
     weight::NTuple{3,Float64}
 end
+struct RtgrObserver            # a pinhole camera carried by an observer (rtgr_trace_observer_f64 / _f32)
+    pos::NTuple{4,Float64}      # the event the observer is at
+    vel::NTuple{4,Float64}      # RTGR_OBS_VELOCITY: coordinate 4-velocity, any normalisation
+    look::NTuple{4,Float64}     # coordinate vectors; only their parts orthogonal to the 4-velocity matter
+    up::NTuple{4,Float64}
+    fov_x::Float64              # radians
+    fov_y::Float64
+    orbit::Float64              # RTGR_OBS_CIRCULAR: +1 = Omega_+ (counter-clockwise seen from +z), -1 = Omega_-
+    kind::UInt32                # RTGR_OBS_STATIC / RTGR_OBS_VELOCITY / RTGR_OBS_CIRCULAR
+    projection::UInt32          # RTGR_PROJ_PERSPECTIVE / RTGR_PROJ_EQUIRECT
+    flags::UInt32               # 0
+    pad::UInt32                 # 0
+    max_batch_rays::UInt64      # rays per batch at most; 0 = default
+end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
     lambda_end::Ptr{Cvoid}
@@ -172,6 +187,11 @@ const RTGR_TEX_BILINEAR = UInt32(1)
 const RTGR_EMIT_KEPLER = UInt32(0)
 const RTGR_EMIT_RIGID = UInt32(1)
 const RTGR_EMIT_INNER_EDGE = UInt32(1)
+const RTGR_OBS_STATIC = UInt32(0)
+const RTGR_OBS_VELOCITY = UInt32(1)
+const RTGR_OBS_CIRCULAR = UInt32(2)
+const RTGR_PROJ_PERSPECTIVE = UInt32(0)
+const RTGR_PROJ_EQUIRECT = UInt32(1)
 
 function check(rc)
     rc < 0 && error("librtgr_hip: ", unsafe_string(ccall((:rtgr_last_error, librtgr), Cstring, ())))
@@ -852,6 +872,77 @@ function trace_rays_emission(metric, objs, pos, widthx, widthy, normal, ni::Inte
         end
     end
     (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), g
+end
+
+"""
+    Observer(pos, look, up, fov_x, fov_y = fov_x; kind = RTGR_OBS_STATIC, vel = (0, 0, 0, 0), orbit = 1,
+             projection = RTGR_PROJ_PERSPECTIVE, max_batch_rays = 0) -> RtgrObserver
+
+A pinhole camera at the event `pos`, carried by an observer who is at rest in the slicing (`RTGR_OBS_STATIC`), moves with the coordinate
+4-velocity `vel` (`RTGR_OBS_VELOCITY`) or rides the circular geodesic through `pos` (z = 0) of the scene's own metric (`RTGR_OBS_CIRCULAR`,
+`orbit` = +1 / -1).  `look` and `up` are coordinate 4-vectors; angles in radians (include/rtgr.h "observer camera").
+"""
+function Observer(pos, look, up, fov_x::Real, fov_y::Real = fov_x; kind::UInt32 = RTGR_OBS_STATIC, vel = (0.0, 0.0, 0.0, 0.0), orbit::Real = 1,
+                  projection::UInt32 = RTGR_PROJ_PERSPECTIVE, max_batch_rays::Integer = 0)
+    v4(v) = NTuple{4,Float64}(Float64.(Tuple(v)))
+    RtgrObserver(v4(pos), v4(vel), v4(look), v4(up), Float64(fov_x), Float64(fov_y), Float64(orbit), kind, projection, UInt32(0), UInt32(0),
+                 UInt64(max_batch_rays))
+end
+
+# the frame the library builds from `obs` in `scene` (rtgr_eval_observer_f64/_f32, blocking): (4 x 4 matrix with the COLUMNS e_0, e_right,
+# e_up, e_look; Omega) — or an error when the frame is not valid
+function observer_frame(scene, obs; T::Type = Float64, ctx = nothing)
+    frame = Array{T}(undef, 4, 4)                   # C writes rows e_0, e_right, e_up, e_look: Julia's columns
+    omega = Ref{T}(T(0))
+    valid = Ref{Cint}(0)
+    GC.@preserve frame begin
+        if T === Float64
+            check(ccall((:rtgr_eval_observer_f64, librtgr), Cint, (Ctx, Ptr{RtgrScene}, Ptr{RtgrObserver}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+                        handle(ctx), scene, obs, pointer(frame), omega, valid))
+        else
+            check(ccall((:rtgr_eval_observer_f32, librtgr), Cint, (Ctx, Ptr{RtgrScene}, Ptr{RtgrObserver}, Ptr{Float32}, Ptr{Float32}, Ptr{Cint}),
+                        handle(ctx), scene, obs, pointer(frame), omega, valid))
+        end
+    end
+    valid[] == 0 && error("Observer: no valid frame at this event (a 4-velocity that is not timelike and future-directed, no circular orbit ",
+                          "there, or look / up degenerate after projection)")
+    frame, omega[]
+end
+
+"""
+    trace_rays_observer(metric, objs, observer, ni, nj; emission = nothing, T = Float64, ctx = nothing) -> ((R, G, B), g)
+
+A frame seen by an OBSERVER (`rtgr_trace_observer_f64/_f32`) — an extension: the rays of a pinhole at one event, in the orthonormal frame
+of a static, moving or orbiting observer (`Observer`), traced as `render` traces caller-supplied states.  With `emission` (from
+`disk_emission`) the disk glows and `g`, the frequency ratio against THIS observer's 4-velocity, comes back as an `ni x nj` matrix;
+without it `g` is `nothing`.  The frame is asked for first (`rtgr_eval_observer_f64/_f32`): an observer with no valid frame is an error.
+Built-in metrics and 3-D grids; runs on device 0 of `ctx`.
+"""
+function trace_rays_observer(metric, objs, observer::RtgrObserver, ni::Integer, nj::Integer; emission = nothing, T::Type = Float64, ctx = nothing)
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("trace_rays_observer has no CPU counterpart in the reference: ", why)
+    opt = solver_of(T)
+    obs = Ref(observer)
+    observer_frame(scene, obs; T = T, ctx = ctx)    # (raises when no frame exists there: the trace itself would only end every ray as NaN)
+    rgb = Array{T}(undef, ni, nj, 3)                # plane-major: rgb[:, :, c] is plane c
+    g = Array{T}(undef, ni, nj)
+    ctr = Ref{RtgrCounters}()
+    emit = emission === nothing ? C_NULL : Ref(emission::RtgrDiskEmission)
+    gp = emission === nothing ? Ptr{T}(C_NULL) : pointer(g)
+    GC.@preserve rgb g begin
+        if T === Float64
+            check(ccall((:rtgr_trace_observer_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission}, Ptr{Float64},
+                         Ptr{RtgrRayOutputs}, Ptr{Float64}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, emit, pointer(rgb), C_NULL, gp, ctr))
+        else
+            check(ccall((:rtgr_trace_observer_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission}, Ptr{Float32},
+                         Ptr{RtgrRayOutputs}, Ptr{Float32}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, emit, pointer(rgb), C_NULL, gp, ctr))
+        end
+    end
+    (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), (emission === nothing ? nothing : g)
 end
 
 """

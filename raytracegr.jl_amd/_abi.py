@@ -28,6 +28,9 @@ TEX_NEAREST, TEX_BILINEAR = 0, 1
 # enum rtgr_emitter, and the flag of rtgr_disk_emission.flags
 EMIT_KEPLER, EMIT_RIGID = 0, 1
 EMIT_INNER_EDGE = 1
+# enum rtgr_observer_kind, enum rtgr_projection
+OBS_STATIC, OBS_VELOCITY, OBS_CIRCULAR = 0, 1, 2
+PROJ_PERSPECTIVE, PROJ_EQUIRECT = 0, 1
 # enum rtgr_status
 OK, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NAN_INPUT, ERR_NOT_INIT = 0, -1, -2, -3, -4, -5
 
@@ -120,6 +123,13 @@ class rtgr_disk_emission(C.Structure):
                 ("T_in", C.c_double), ("p", C.c_double), ("gain", C.c_double), ("theta", C.c_double * 3), ("weight", C.c_double * 3)]
 
 
+class rtgr_observer(C.Structure):
+    """a pinhole camera carried by an observer (rtgr_trace_observer_*): 176 bytes"""
+    _fields_ = [("pos", C.c_double * 4), ("vel", C.c_double * 4), ("look", C.c_double * 4), ("up", C.c_double * 4), ("fov_x", C.c_double),
+                ("fov_y", C.c_double), ("orbit", C.c_double), ("kind", C.c_uint32), ("projection", C.c_uint32), ("flags", C.c_uint32),
+                ("pad", C.c_uint32), ("max_batch_rays", C.c_uint64)]
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -147,6 +157,9 @@ EXPORTS = [
     "rtgr_trace_shaded_f32", "rtgr_eval_texture_f64", "rtgr_eval_texture_f32",
     "rtgr_trace_emission_device_f64", "rtgr_trace_emission_device_f32", "rtgr_trace_emission_f64", "rtgr_trace_emission_f32",
     "rtgr_eval_disk_emission_f64", "rtgr_eval_disk_emission_f32",
+    "rtgr_trace_observer_device_f64", "rtgr_trace_observer_device_f32", "rtgr_trace_observer_f64", "rtgr_trace_observer_f32",
+    "rtgr_make_observer_canvas_device_f64", "rtgr_make_observer_canvas_device_f32", "rtgr_make_observer_canvas_f64", "rtgr_make_observer_canvas_f32",
+    "rtgr_eval_observer_f64", "rtgr_eval_observer_f32", "rtgr_eval_disk_emission_observer_f64", "rtgr_eval_disk_emission_observer_f32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -230,6 +243,17 @@ def _declare(lib):
             ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_camera), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_aa), vp,
             P(rtgr_ray_outputs), vp, vp, P(rtgr_counters), P(rtgr_aa_stats)]
         getattr(lib, f"rtgr_eval_disk_emission_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_disk_emission), vp, vp, u64, vp, vp, vp, vp]
+        getattr(lib, f"rtgr_trace_observer_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), vp, P(rtgr_ray_outputs), vp,
+            P(rtgr_counters), vp]
+        getattr(lib, f"rtgr_trace_observer_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), vp, P(rtgr_ray_outputs), vp,
+            P(rtgr_counters)]
+        getattr(lib, f"rtgr_make_observer_canvas_device_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_observer), u64, u64, u64, u64, vp, vp]
+        getattr(lib, f"rtgr_make_observer_canvas_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_observer), u64, u64, u64, u64, vp]
+        getattr(lib, f"rtgr_eval_observer_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_observer), vp, vp, P(i32)]
+        getattr(lib, f"rtgr_eval_disk_emission_observer_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_observer), vp, vp, u64, vp, vp, vp, vp]
     lib.rtgr_texture_load.argtypes = [ctx, P(rtgr_texture_desc), vp, P(u64)]
     lib.rtgr_texture_unload.argtypes = [ctx, u64]
     lib.rtgr_eval_fastmath_f64.argtypes = [ctx, vp, u64, vp, vp]

@@ -635,6 +635,90 @@ def eval_disk_emission(metric, objs, emission, s0, s_end, dtype=np.float64, ctx=
     return res
 
 
+# ---- observer camera (include/rtgr.h "observer camera") ---------------------------------------------------------------------------
+def Observer(pos, look, up, fov_x, fov_y=None, kind="static", vel=None, orbit=+1, projection="perspective", max_batch_rays=0):
+    """A pinhole camera carried by an observer -> rtgr_observer.  pos: the event (t, x, y, z); look, up: coordinate 4-vectors (only
+    their parts orthogonal to the observer's 4-velocity matter).  kind "static": at rest in the slicing (make_canvas' observer);
+    "velocity": the coordinate 4-velocity `vel`, any normalisation; "circular": on the circular geodesic through pos (z = 0) of the
+    scene's own metric, orbit = +1 (counter-clockwise seen from +z) or -1.  projection "perspective": fov_x, fov_y in (0, pi);
+    "equirect": a panorama, fov_x <= 2 pi, fov_y <= pi.  Angles in radians; fov_y = None: fov_x for a perspective frame, fov_x / 2
+    for a panorama."""
+    kinds = {"static": _abi.OBS_STATIC, "velocity": _abi.OBS_VELOCITY, "circular": _abi.OBS_CIRCULAR}
+    projs = {"perspective": _abi.PROJ_PERSPECTIVE, "equirect": _abi.PROJ_EQUIRECT}
+    if kind not in kinds:
+        raise ValueError(f"Observer: kind must be 'static', 'velocity' or 'circular', got {kind!r}")
+    if projection not in projs:
+        raise ValueError(f"Observer: projection must be 'perspective' or 'equirect', got {projection!r}")
+    if kind == "velocity" and vel is None:
+        raise ValueError("Observer: kind 'velocity' needs vel")
+    if fov_y is None:
+        fov_y = fov_x if projection == "perspective" else 0.5 * fov_x
+    v4 = lambda v: (C.c_double * 4)(*[float(c) for c in v])
+    return _abi.rtgr_observer(pos=v4(pos), vel=v4(vel if vel is not None else (0, 0, 0, 0)), look=v4(look), up=v4(up), fov_x=float(fov_x),
+                              fov_y=float(fov_y), orbit=float(orbit), kind=kinds[kind], projection=projs[projection], flags=0, pad=0,
+                              max_batch_rays=int(max_batch_rays))
+
+
+def eval_observer(metric, objs, observer, dtype=np.float64, ctx=None):
+    """rtgr_eval_observer_f64 / _f32: the frame the kernels build from `observer` (an Observer) in this scene.
+    -> dict(frame [4, 4] (rows e_0, e_right, e_up, e_look), omega (NaN unless circular), valid)."""
+    lib = _lib()
+    sc = make_scene(metric, objs, ctx)
+    frame, omega, valid = np.zeros((4, 4), dtype), np.zeros(1, dtype), C.c_int(0)
+    fn = lib.rtgr_eval_observer_f64 if dtype == np.float64 else lib.rtgr_eval_observer_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(observer), frame.ctypes.data, omega.ctypes.data, C.byref(valid)))
+    return dict(frame=frame, omega=omega[0], valid=bool(valid.value))
+
+
+def _valid_observer(metric, objs, observer, dtype, ctx):
+    if not eval_observer(metric, objs, observer, dtype, ctx)["valid"]:
+        raise ValueError("Observer: no valid frame at this event (a 4-velocity that is not timelike and future-directed, no circular orbit "
+                         "there, or look / up degenerate after projection)")
+
+
+def make_observer_canvas(metric, objs, observer, ni, nj, dtype=np.float64, ctx=None):
+    """rtgr_make_observer_canvas_f64 / _f32: the start states [ni*nj, 8] of the observer's rays (pixel i + j ni), which trace_rays
+    and rtgr_trace_* take as caller-supplied states.  Raises ValueError for an observer with no valid frame."""
+    lib = _lib()
+    _valid_observer(metric, objs, observer, dtype, ctx)
+    sc = make_scene(metric, objs, ctx)
+    out = np.zeros((ni * nj, 8), dtype)
+    fn = lib.rtgr_make_observer_canvas_f64 if dtype == np.float64 else lib.rtgr_make_observer_canvas_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(observer), ni, nj, 0, nj, out.ctypes.data))
+    return out
+
+
+def trace_observer(metric, objs, observer, ni, nj, emission=None, textures=None, r_escape=0.0, opt=None, dtype=np.float64, ctx=None, details=False):
+    """A frame seen by an OBSERVER (rtgr_trace_observer_f64 / _f32) — an extension: a pinhole at one event, carried by a static, moving
+    or orbiting observer (an Observer), perspective or equirectangular.  textures as trace_shaded, emission (a DiskEmission) as
+    trace_emission — with the frequency ratio taken against THIS observer's 4-velocity.  Raises ValueError for an observer with no
+    valid frame.  -> dict(rgb [3, ni*nj], counters; emission: + g [ni*nj]; details: + the per-ray outputs)."""
+    lib = _lib()
+    _valid_observer(metric, objs, observer, dtype, ctx)
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    n = ni * nj
+    sh = make_shade(textures, r_escape) if textures else None
+    res = dict(rgb=np.zeros((3, n), dtype))
+    if emission is not None:
+        res["g"] = np.zeros(n, dtype)
+    outs = None
+    if details:
+        outs = rtgr_ray_outputs()
+        wide = sc.nobj > 255
+        res.update(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
+                   hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
+        for name in ("state_end", "lambda_end", "status", "hit", "n_accept", "n_reject"):
+            setattr(outs, "hit32" if (wide and name == "hit") else name, res[name].ctypes.data)
+    ctr = rtgr_counters()
+    fn = lib.rtgr_trace_observer_f64 if dtype == np.float64 else lib.rtgr_trace_observer_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(observer), ni, nj, None if sh is None else C.byref(sh),
+                       None if emission is None else C.byref(emission), res["rgb"].ctypes.data, outs,
+                       res["g"].ctypes.data if emission is not None else None, C.byref(ctr)))
+    res["counters"] = ctr.as_dict()
+    return res
+
+
 def trace_ray(metric, objs, cb, p, opt=None, ctx=None):
     """Legacy single-pixel shape `trace_ray(metric, objs, cb, p)::Pixel` (test/runtests.jl:65-79).
     `cb` is accepted for signature parity and ignored: the callback is always
@@ -744,5 +828,5 @@ def example2(ni=200, nj=200, save=True, ctx=None):
 
 __all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
-           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "dmetric", "christoffel", "geodesic", "example1", "example2",
+           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

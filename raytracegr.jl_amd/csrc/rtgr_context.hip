@@ -157,6 +157,8 @@ void free_device_state(DeviceCtx& d, bool all) {
             if (kv.second.aa_batch) (void)hipFree(kv.second.aa_batch);
             if (kv.second.shade_frame) (void)hipFree(kv.second.shade_frame);
             if (kv.second.emit_frame) (void)hipFree(kv.second.emit_frame);
+            if (kv.second.obs_frame) (void)hipFree(kv.second.obs_frame);
+            if (kv.second.obs_batch) (void)hipFree(kv.second.obs_batch);
         }
     }
     for (auto& g : d.retired_grids) { (void)hipFree(g.d64); (void)hipFree(g.d32); }   // unloaded grid metrics (idle device: see above)

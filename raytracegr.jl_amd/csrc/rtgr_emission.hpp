@@ -52,32 +52,40 @@ RTGR_DEV void emission_dmetric(const DevScene<R>& sc, const R x[4], R g[4][4], R
     else dmetric_dev<R>(sc.metric, sc.M, sc.a, x, g, dg);
 }
 
-// The model above at one pair of states.  Returns whether the emitter is valid (and the frequency ratio finite); omega, uem, gred and
-// rgb are always written.
+// The orbital rate of the model above at the equatorial point (t, x, y, 0): the root `orbit` = ±1 names of C Omega² + 2 B Omega + A = 0.
+// ok: B² - A C >= 0 and C != 0.  ONE function for the emitter (disk_emission) and for an observer on a circular orbit
+// (rtgr_observer.hpp: observer_frame), so the two rates at one point are the same bits.
 template <class R>
-RTGR_DEV bool disk_emission(const DevScene<R>& sc, const DevEmission<R>& E, const R s0[8], const R se[8], R& omega, R uem[4], R& gred, R rgb[3]) {
+RTGR_DEV R circular_orbit_rate(const DevScene<R>& sc, R t, R x, R y, R orbit, bool& ok) {
+#pragma clang fp contract(off)
+    const R P[4] = {t, x, y, R(0)};
+    R g[4][4], dg[4][4][4];
+    emission_dmetric<R>(sc, P, g, dg);
+    const R Dtt = x * dg[0][0][1] + y * dg[0][0][2], Dtx = x * dg[0][1][1] + y * dg[0][1][2], Dty = x * dg[0][2][1] + y * dg[0][2][2];
+    const R Dxx = x * dg[1][1][1] + y * dg[1][1][2], Dxy = x * dg[1][2][1] + y * dg[1][2][2], Dyy = x * dg[2][2][1] + y * dg[2][2][2];
+    const R gtp = x * g[0][2] - y * g[0][1];
+    const R gpp = y * y * g[1][1] - R(2) * x * y * g[1][2] + x * x * g[2][2];
+    const R A = Dtt;
+    const R B = (x * Dty - y * Dtx) + gtp;
+    const R C = (y * y * Dxx - R(2) * x * y * Dxy + x * x * Dyy) + R(2) * gpp;
+    const R disc = B * B - A * C;
+    ok = disc >= R(0) && C != R(0);
+    return (orbit * rsqrt_(disc) - B) / C;   // (orbit = ±1 picks the root)
+}
+
+// The model above at one pair of states.  Returns whether the emitter is valid (and the frequency ratio finite); omega, uem, gred and
+// rgb are always written.  obs (may be null): the frame of an observer camera (rtgr_observer.hpp) — u_obs is then its e_0 instead of
+// the static observer at x_0.
+template <class R>
+RTGR_DEV bool disk_emission(const DevScene<R>& sc, const DevEmission<R>& E, const R s0[8], const R se[8], R& omega, R uem[4], R& gred, R rgb[3],
+                            const ObsFrame<R>* obs = nullptr) {
 #pragma clang fp contract(off)
     const R nan = R(__builtin_nan(""));
     const R x = se[1], y = se[2];
     bool ok = true;
     R Om;
-    if (E.emitter == RTGR_EMIT_KEPLER) {
-        const R P[4] = {se[0], x, y, R(0)};
-        R g[4][4], dg[4][4][4];
-        emission_dmetric<R>(sc, P, g, dg);
-        const R Dtt = x * dg[0][0][1] + y * dg[0][0][2], Dtx = x * dg[0][1][1] + y * dg[0][1][2], Dty = x * dg[0][2][1] + y * dg[0][2][2];
-        const R Dxx = x * dg[1][1][1] + y * dg[1][1][2], Dxy = x * dg[1][2][1] + y * dg[1][2][2], Dyy = x * dg[2][2][1] + y * dg[2][2][2];
-        const R gtp = x * g[0][2] - y * g[0][1];
-        const R gpp = y * y * g[1][1] - R(2) * x * y * g[1][2] + x * x * g[2][2];
-        const R A = Dtt;
-        const R B = (x * Dty - y * Dtx) + gtp;
-        const R C = (y * y * Dxx - R(2) * x * y * Dxy + x * x * Dyy) + R(2) * gpp;
-        const R disc = B * B - A * C;
-        ok = disc >= R(0) && C != R(0);
-        Om = (E.orbit * rsqrt_(disc) - B) / C;   // (orbit = ±1 picks the root)
-    } else {
-        Om = E.orbit;
-    }
+    if (E.emitter == RTGR_EMIT_KEPLER) Om = circular_orbit_rate<R>(sc, se[0], x, y, E.orbit, ok);
+    else Om = E.orbit;
     R ge[4][4], g0[4][4], tobs[4];
     metric_plain<R>(sc, se, ge);
     const R xi[4] = {R(1), -(Om * y), Om * x, R(0)};
@@ -87,7 +95,12 @@ RTGR_DEV bool disk_emission(const DevScene<R>& sc, const DevEmission<R>& E, cons
     for (int c = 0; c < 4; c++) uem[c] = xi[c] * sc_u;
     bool ok0;
     metric_plain<R>(sc, s0, g0);
-    static_observer<R>(g0, tobs, ok0);
+    if (obs) {
+        ok0 = obs->valid != 0u;
+        for (int c = 0; c < 4; c++) tobs[c] = obs->e[0][c];
+    } else {
+        static_observer<R>(g0, tobs, ok0);
+    }
     const R num = inner<R>(g0, s0 + 4, tobs), den = inner<R>(ge, se + 4, uem);
     R gr = num / den;
     ok = ok && ok0 && rfinite(gr);

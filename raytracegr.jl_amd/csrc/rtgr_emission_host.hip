@@ -9,7 +9,7 @@ constexpr size_t EMIT_HEAD = 256;   // head of the frame scratch: rtgr_counters 
 
 // the caller's parameters into the record the kernels read, for scalar type R; `shade` (may be null): the binds of the same call
 template <class R>
-static int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, const rtgr_disk_emission* emit, DevEmission<R>& em) {
+int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, const rtgr_disk_emission* emit, DevEmission<R>& em) {
     if (!scene) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
     if (!emit) return fail(RTGR_ERR_BAD_ARG, "rtgr_disk_emission is NULL (emit)");
     const uint32_t metric = scene->metric & ~(uint32_t)RTGR_METRIC_GENERIC;
@@ -55,7 +55,7 @@ static int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, co
 
 // the scene as the emission kernel reads it (D.mu held); a time-dependent grid has no stationary emitter
 template <class R>
-static int emission_scene(DeviceCtx& D, const rtgr_scene* scene, DevScene<R>& sc, hipStream_t st) {
+int emission_scene(DeviceCtx& D, const rtgr_scene* scene, DevScene<R>& sc, hipStream_t st) {
     const UserModule* user = nullptr;
     int rc;
     if ((rc = convert_scene<R>(D, scene, sc, &user, st))) return rc;
@@ -134,7 +134,7 @@ static int trace_emission_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_s
     {
         std::lock_guard<std::mutex> lk(D.mu);
         KernelTimer timer(D, st, 0);
-        E.rgb = d_rgb; E.g = d_g; E.omega = nullptr; E.u_emit = nullptr; E.hit32 = o1.hit32; E.state_end = (const R*)o1.state_end; E.state0 = nullptr;
+        E.rgb = d_rgb; E.g = d_g; E.omega = nullptr; E.u_emit = nullptr; E.hit32 = o1.hit32; E.state_end = (const R*)o1.state_end; E.state0 = nullptr; E.obs = nullptr;
         E.n = n; E.plane_stride = n; E.pixel_stride = 1; E.ni = ni; E.nj = nj;
         if ((rc = emit_launch<R>(E, st))) return rc;
     }
@@ -200,10 +200,11 @@ int api::trace_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_s
     return RTGR_OK;
 }
 
-// the model at n pairs of states, on device 0 of the context (host pointers): the emission kernel itself, in point mode
+// the model at n pairs of states, on device 0 of the context (host pointers): the emission kernel itself, in point mode.  obs (may be
+// null): u_obs is the e_0 of that observer camera's frame (rtgr_observer_host.hip), built by the frame kernel ahead of the points
 template <class R>
-int api::eval_disk_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const R* s0, const R* s_end, uint64_t n,
-                            R* omega, R* u_emit, R* g, R* rgb) {
+int api::eval_disk_emission_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_observer* obs, const R* s0,
+                                     const R* s_end, uint64_t n, R* omega, R* u_emit, R* g, R* rgb) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
@@ -212,6 +213,8 @@ int api::eval_disk_emission(rtgr_context* ctx, const rtgr_scene* scene, const rt
     EmitArgs<R> E;
     std::memset(&E, 0, sizeof E);
     if ((rc = emission_resolve<R>(scene, nullptr, emit, E.em))) return rc;
+    DevObserver<R> ob;
+    if (obs && (rc = observer_resolve<R>(scene, obs, ob))) return rc;
     DeviceCtx& D = *c->devs[0];
     DeviceGuard guard(D.dev);
     if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
@@ -219,8 +222,13 @@ int api::eval_disk_emission(rtgr_context* ctx, const rtgr_scene* scene, const rt
     if ((rc = emission_scene<R>(D, scene, E.sc, nullptr))) return rc;
     if (n == 0) return RTGR_OK;
     const size_t sbytes = (size_t)n * 8 * sizeof(R);
-    DevBuf d_s0, d_se, d_om, d_u, d_g, d_rgb;
+    DevBuf d_s0, d_se, d_om, d_u, d_g, d_rgb, d_frame;
     if ((rc = d_s0.alloc(sbytes)) || (rc = d_se.alloc(sbytes))) return rc;
+    if (obs) {
+        if ((rc = d_frame.alloc(sizeof(ObsFrame<R>)))) return rc;
+        if ((rc = observer_frame_launch<R>(E.sc, ob, (ObsFrame<R>*)d_frame.p, nullptr))) return rc;
+        E.obs = (const ObsFrame<R>*)d_frame.p;
+    }
     if (omega && (rc = d_om.alloc((size_t)n * sizeof(R)))) return rc;
     if (u_emit && (rc = d_u.alloc((size_t)n * 4 * sizeof(R)))) return rc;
     if (g && (rc = d_g.alloc((size_t)n * sizeof(R)))) return rc;
@@ -241,6 +249,14 @@ int api::eval_disk_emission(rtgr_context* ctx, const rtgr_scene* scene, const rt
 
 RTGR_INSTANTIATE_F64_F32(api::trace_emission_device);
 RTGR_INSTANTIATE_F64_F32(api::trace_emission);
+template <class R>
+int api::eval_disk_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const R* s0, const R* s_end, uint64_t n,
+                            R* omega, R* u_emit, R* g, R* rgb) {
+    return eval_disk_emission_observer<R>(ctx, scene, emit, nullptr, s0, s_end, n, omega, u_emit, g, rgb);
+}
+RTGR_INSTANTIATE_F64_F32(emission_resolve);
+RTGR_INSTANTIATE_F64_F32(emission_scene);
+RTGR_INSTANTIATE_F64_F32(api::eval_disk_emission_observer);
 RTGR_INSTANTIATE_F64_F32(api::eval_disk_emission);
 
 }  // namespace rtgr

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs<R> A) {
     else make_pixel<R>(A.sc, A.cam, A.ni, A.nj, idx % A.ni, idx / A.ni, s0);
     for (int c = 0; c < 8; c++) se[c] = A.state_end[idx * 8 + c];
     R omega, uem[4], g, col[3];
-    disk_emission<R>(A.sc, A.em, s0, se, omega, uem, g, col);
+    disk_emission<R>(A.sc, A.em, s0, se, omega, uem, g, col, A.obs);
     if (A.omega) A.omega[idx] = omega;
     if (A.u_emit) for (int c = 0; c < 4; c++) A.u_emit[idx * 4 + c] = uem[c];
     if (A.g) A.g[idx] = g;

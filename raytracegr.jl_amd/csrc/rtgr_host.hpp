@@ -180,6 +180,11 @@ struct StreamState {
     // scratch of rtgr_trace_emission_device_* without anti-aliasing (rtgr_emission_host.hip), likewise: the counters, then the end states /
     // hit map / status bytes the emission and shading kernels read and the caller did not ask for
     void* emit_frame = nullptr; size_t emit_frame_bytes = 0;
+    // scratch of rtgr_trace_observer_device_* / rtgr_make_observer_canvas_device_* (rtgr_observer_host.hip), likewise: per FRAME the
+    // counters, the observer's frame record, then the end states / hit map / status bytes the shading and emission kernels read and the
+    // caller did not ask for; per BATCH the ray states of its rows
+    void* obs_frame = nullptr; size_t obs_frame_bytes = 0;
+    void* obs_batch = nullptr; size_t obs_batch_bytes = 0;
 };
 
 struct Staging;  // host entry points (rtgr_internal.hpp)
@@ -353,10 +358,34 @@ struct DevEmission {
     R orbit, T_in, p, gain, r_in;
     R theta[3], weight[3];
 };
+// the observer camera (rtgr_observer.hip; include/rtgr.h "observer camera").  The caller's rtgr_observer as the frame kernel reads it,
+// converted by the host for one scalar type: hx, hy = tan(fov / 2) for RTGR_PROJ_PERSPECTIVE, fov / 2 for RTGR_PROJ_EQUIRECT.
+template <class R>
+struct DevObserver {
+    R pos[4], vel[4], look[4], up[4];
+    R orbit, hx, hy;
+    uint32_t kind, projection;
+};
+// … and what the frame kernel makes of it, once per call, in the stream's scratch: the metric at pos, the tetrad (rows e_0, e_right, e_up,
+// e_look), Omega of a circular orbit (NaN for the other kinds) and whether the frame is valid.  The ray kernel and the emission kernel
+// read it with scalar loads.
+template <class R>
+struct ObsFrame {
+    R pos[4];
+    R g[4][4];
+    R e[4][4];
+    R omega, hx, hy;
+    uint32_t valid, projection;
+};
+// the frame kernel (one wave), and the ray kernel: the states of the n pixels from `first` on (row-major, i fastest) of the ni x nj canvas
+template <class R>
+int observer_frame_launch(const DevScene<R>& sc, const DevObserver<R>& ob, ObsFrame<R>* d_frame, hipStream_t st);
+template <class R>
+int observer_rays_launch(const ObsFrame<R>* d_frame, uint64_t ni, uint64_t nj, uint64_t first, uint64_t n, R* d_state0, hipStream_t st);
 // the emission kernel's argument block.  Frame mode (hit32 given): n pixels, colour planes plane_stride apart (pixel_stride 1), g: the
 // frequency ratio per pixel (may be null); state0: the rays' start states when they were caller-supplied (the sub-rays of anti-aliasing),
 // null: pixel idx of the ni x nj canvas of cam.  Point mode (hit32 null; rtgr_eval_disk_emission_*): n pairs (state0, state_end), every
-// output optional, rgb n x 3 (plane_stride 1, pixel_stride 3).
+// output optional, rgb n x 3 (plane_stride 1, pixel_stride 3).  (Aggregate initialisation without the last member leaves obs null.)
 template <class R>
 struct EmitArgs {
     R* rgb;
@@ -370,6 +399,7 @@ struct EmitArgs {
     DevScene<R> sc;
     DevCamera<R> cam;
     DevEmission<R> em;
+    const ObsFrame<R>* obs;   // null: u_obs is the static observer at the ray's start; else the e_0 of this frame (rtgr_trace_observer_*)
 };
 template <class R>
 int emit_launch(const EmitArgs<R>& A, hipStream_t st);

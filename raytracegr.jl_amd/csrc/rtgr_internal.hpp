@@ -11,6 +11,8 @@
 //                           sampler hook (kernels: rtgr_shade.hip)
 //   rtgr_emission_host.hip  disk emission: the emitted trace (a plain, shaded and / or anti-aliased trace + the emission kernel), the
 //                           pointwise hook (kernels: rtgr_emit.hip)
+//   rtgr_observer_host.hip  the observer camera: the checks of an rtgr_observer, the observer trace (the frame and ray kernels + a plain trace of
+//                           their states, batch by batch, + the shading / emission kernels), the canvas and frame hooks (kernels: rtgr_observer.hip)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -153,6 +155,12 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
 // device D and scalar type R (takes D.mu), and the checks of a shaded frame's arguments
 template <class R> int shade_resolve(DeviceCtx& D, const rtgr_scene* scene, const rtgr_shade* shade, ShadeDesc<R>& sd);
 int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refined, const rtgr_aa_stats* stats, uint64_t ni, uint64_t nj);
+// disk emission (rtgr_emission_host.hip), shared with the observer trace: the caller's parameters into the record the kernels read
+// (`shade`, may be null: the binds of the same call), and the scene as the emission kernel reads it (D.mu held; refuses a 4-D grid)
+template <class R> int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, const rtgr_disk_emission* emit, DevEmission<R>& em);
+template <class R> int emission_scene(DeviceCtx& D, const rtgr_scene* scene, DevScene<R>& sc, hipStream_t st);
+// the observer camera (rtgr_observer_host.hip): the checks of an rtgr_observer against its scene, and the record the frame kernel reads
+template <class R> int observer_resolve(const rtgr_scene* scene, const rtgr_observer* obs, DevObserver<R>& ob);
 
 // scratch device buffers of the small host-pointer hooks (eval_*, make_canvas, the probe): RAII, synchronous
 struct DevBuf {
@@ -296,6 +304,12 @@ template <class R> int eval_texture(rtgr_context* ctx, uint64_t texture, uint32_
 template <class R> int trace_emission_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream);
 template <class R> int trace_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_aa* aa, R* rgb, const rtgr_ray_outputs* out, R* g, uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats);
 template <class R> int eval_disk_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const R* s0, const R* s_end, uint64_t n, R* omega, R* u_emit, R* g, R* rgb);
+template <class R> int eval_disk_emission_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_observer* obs, const R* s0, const R* s_end, uint64_t n, R* omega, R* u_emit, R* g, R* rgb);
+template <class R> int trace_observer_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, rtgr_counters* ctr, void* stream);
+template <class R> int trace_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, R* rgb, const rtgr_ray_outputs* out, R* g, rtgr_counters* ctr);
+template <class R> int make_observer_canvas_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* d_state0, void* stream);
+template <class R> int make_observer_canvas(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* state0);
+template <class R> int eval_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, R* frame, R* omega, int* valid);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 

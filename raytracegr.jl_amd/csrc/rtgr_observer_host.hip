@@ -1,0 +1,311 @@
+// rtgr_observer_host.hip — the observer camera (include/rtgr.h "observer camera"): the checks of an rtgr_observer, the observer trace —
+// the frame kernel, then batch by batch the ray kernel, a plain trace_device of those states into a window of the caller's planes, the
+// shading kernel (if textures are bound) and the emission kernel (if a disk emits) — and the hooks.  Host code only: the kernels are
+// rtgr_observer.hip's, rtgr_shade.hip's and rtgr_emit.hip's, the frame's model rtgr_observer.hpp's.
+#include "rtgr_internal.hpp"
+
+namespace rtgr {
+
+constexpr uint64_t OBS_DEFAULT_BATCH = 1ull << 22;   // rays per batch (rtgr_observer.max_batch_rays = 0), as rtgr_aa's
+constexpr size_t OBS_HEAD = 256;                     // head of the frame scratch: rtgr_counters (64 bytes) …
+constexpr size_t OBS_FRAME = 512;                    // … then the frame record (ObsFrame<double>: 320 bytes)
+static_assert(sizeof(ObsFrame<double>) <= OBS_FRAME && sizeof(rtgr_counters) <= OBS_HEAD, "the head of the observer scratch holds both");
+constexpr double OBS_PI = 3.14159265358979323846;
+
+static bool finite4(const double v[4]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && std::isfinite(v[3]); }
+
+// the caller's record, checked against its scene, into the record the frame kernel reads, for scalar type R
+template <class R>
+int observer_resolve(const rtgr_scene* scene, const rtgr_observer* obs, DevObserver<R>& ob) {
+    if (!scene) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
+    if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
+    if ((scene->metric & ~(uint32_t)RTGR_METRIC_GENERIC) == RTGR_USER)
+        return fail(RTGR_ERR_BAD_ARG, "an observer camera in a scene whose METRIC is RTGR_USER is not supported (its kernels live in the run-time unit); "
+                                      "user objects under a built-in metric are");
+    if (obs->kind != RTGR_OBS_STATIC && obs->kind != RTGR_OBS_VELOCITY && obs->kind != RTGR_OBS_CIRCULAR)
+        return fail(RTGR_ERR_BAD_ARG, "unknown rtgr_observer.kind " + std::to_string(obs->kind) + " (RTGR_OBS_STATIC = 0, RTGR_OBS_VELOCITY = 1, RTGR_OBS_CIRCULAR = 2)");
+    if (obs->projection != RTGR_PROJ_PERSPECTIVE && obs->projection != RTGR_PROJ_EQUIRECT)
+        return fail(RTGR_ERR_BAD_ARG, "unknown rtgr_observer.projection " + std::to_string(obs->projection) + " (RTGR_PROJ_PERSPECTIVE = 0, RTGR_PROJ_EQUIRECT = 1)");
+    if (obs->flags != 0) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer.flags must be 0");
+    if (obs->pad != 0) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer.pad must be 0");
+    if (!finite4(obs->pos)) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer.pos must be finite");
+    if (!finite4(obs->look)) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer.look must be finite");
+    if (!finite4(obs->up)) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer.up must be finite");
+    if (obs->kind == RTGR_OBS_VELOCITY && !finite4(obs->vel)) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer.vel of RTGR_OBS_VELOCITY must be finite");
+    if (!std::isfinite(obs->fov_x) || !std::isfinite(obs->fov_y)) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer.fov_x and fov_y must be finite");
+    if (obs->projection == RTGR_PROJ_PERSPECTIVE) {
+        if (!(obs->fov_x > 0.0 && obs->fov_x < OBS_PI && obs->fov_y > 0.0 && obs->fov_y < OBS_PI))
+            return fail(RTGR_ERR_BAD_ARG, "rtgr_observer: fov_x and fov_y of RTGR_PROJ_PERSPECTIVE must lie in (0, pi) radians");
+    } else if (!(obs->fov_x > 0.0 && obs->fov_x <= 2.0 * OBS_PI && obs->fov_y > 0.0 && obs->fov_y <= OBS_PI)) {
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_observer: RTGR_PROJ_EQUIRECT needs 0 < fov_x <= 2 pi and 0 < fov_y <= pi radians");
+    }
+    if (obs->kind == RTGR_OBS_CIRCULAR) {
+        if (!std::isfinite(obs->orbit)) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer.orbit must be finite");
+        if (obs->orbit != 1.0 && obs->orbit != -1.0)
+            return fail(RTGR_ERR_BAD_ARG, "rtgr_observer.orbit of RTGR_OBS_CIRCULAR names a root: +1 (Omega_+) or -1 (Omega_-)");
+        if (obs->pos[3] != 0.0) return fail(RTGR_ERR_BAD_ARG, "RTGR_OBS_CIRCULAR: the orbit lies in the equatorial plane, rtgr_observer.pos[3] (z) must be 0");
+    }
+    std::memset(&ob, 0, sizeof ob);
+    for (int c = 0; c < 4; c++) { ob.pos[c] = (R)obs->pos[c]; ob.vel[c] = (R)obs->vel[c]; ob.look[c] = (R)obs->look[c]; ob.up[c] = (R)obs->up[c]; }
+    if (obs->kind != RTGR_OBS_VELOCITY) for (int c = 0; c < 4; c++) ob.vel[c] = R(0);
+    ob.orbit = obs->kind == RTGR_OBS_CIRCULAR ? (R)obs->orbit : R(0);
+    ob.hx = (R)(obs->projection == RTGR_PROJ_PERSPECTIVE ? std::tan(0.5 * obs->fov_x) : 0.5 * obs->fov_x);
+    ob.hy = (R)(obs->projection == RTGR_PROJ_PERSPECTIVE ? std::tan(0.5 * obs->fov_y) : 0.5 * obs->fov_y);
+    ob.kind = obs->kind; ob.projection = obs->projection;
+    return RTGR_OK;
+}
+RTGR_INSTANTIATE_F64_F32(observer_resolve);
+
+static int observer_canvas_check(uint64_t ni, uint64_t nj) {
+    if (ni == 0 || nj == 0 || ni > (1ull << 32) || nj > (1ull << 32) || ni * nj > (1ull << 34))
+        return fail(RTGR_ERR_BAD_ARG, "bad canvas: need ni, nj > 0 and at most 2^34 pixels for an observer frame");
+    return RTGR_OK;
+}
+
+// what every entry of the observer trace refuses before it touches a device
+static int observer_trace_check(const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_disk_emission* emit,
+                                const void* rgb, const rtgr_ray_outputs* out, const void* g) {
+    if (!scene) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
+    if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
+    if (!rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
+    int rc;
+    if ((rc = observer_canvas_check(ni, nj))) return rc;
+    if (out && out->redshift)
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_ray_outputs.redshift is defined against the static observer of make_canvas: an observer trace does not deliver it "
+                                      "(the frequency ratio against THIS observer and an orbiting disk is d_g, with emit)");
+    if (g && !emit) return fail(RTGR_ERR_BAD_ARG, "g is the frequency ratio of an emitting disk: it must be NULL when emit is NULL");
+    return RTGR_OK;
+}
+
+// the scene as the observer's kernels read it (D.mu held): its metric, which must not depend on time through a 4-D grid
+template <class R>
+static int observer_scene(DeviceCtx& D, const rtgr_scene* scene, DevScene<R>& sc, hipStream_t st) {
+    const UserModule* user = nullptr;
+    int rc;
+    if ((rc = convert_scene<R>(D, scene, sc, &user, st))) return rc;
+    if (sampled_on(sc.metric, 4))
+        return fail(RTGR_ERR_BAD_ARG, "an observer camera in a time-dependent (4-D) grid metric is not supported");
+    return RTGR_OK;
+}
+
+// the call on device D, stream st; d_rgb, d_g and the members of `out` are pointers of that device
+template <class R>
+static int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
+                             const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, rtgr_counters* ctr,
+                             hipStream_t st) {
+    int rc;
+    if ((rc = observer_trace_check(scene, obs, ni, nj, emit, d_rgb, out, d_g))) return rc;
+    DevObserver<R> ob;
+    if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
+    EmitArgs<R> E;
+    std::memset(&E, 0, sizeof E);
+    if (emit && (rc = emission_resolve<R>(scene, shade, emit, E.em))) return rc;
+    ShadeArgs<R> A;
+    if (shade && (rc = shade_resolve<R>(D, scene, shade, A.desc))) return rc;
+    const bool shading = shade && A.desc.nbind != 0, post = shading || emit;
+    DeviceGuard guard(D.dev);
+    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    if (capturing && ctr)
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_observer_*: the stream is being captured and `ctr` asks for a synchronisation at the end of the call "
+                                      "(which cannot be captured): pass ctr = NULL");
+    const uint64_t n = ni * nj;
+    const uint64_t budget = obs->max_batch_rays ? obs->max_batch_rays : OBS_DEFAULT_BATCH;
+    const uint64_t rows = budget / ni ? (budget / ni < nj ? budget / ni : nj) : 1;   // rows per batch
+    if (rows < nj && (tl_knobs_override ? tl_knobs_override->tile : D.knobs.tile))
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_observer_*: option tile = 1 writes whole frames only and this observer frame takes more than one batch "
+                                      "(rtgr_observer.max_batch_rays): raise max_batch_rays to the frame's rays, or use the persistent pipeline (tile = 0)");
+    const bool want_state = post && !(out && out->state_end), want_hit32 = post && !(out && out->hit32), want_status = shading && !(out && out->status);
+    // ---- frame scratch: [counters] [frame record] [end states] [hit32] [status]; batch scratch: the states of `rows` rows -----------------
+    const size_t off_state = OBS_HEAD + OBS_FRAME, off_hit = off_state + (want_state ? align256(n * 8 * sizeof(R)) : 0),
+                 off_status = off_hit + (want_hit32 ? align256(n * sizeof(uint32_t)) : 0), frame_bytes = off_status + (want_status ? align256(n) : 0);
+    const size_t batch_bytes = align256((size_t)rows * ni * 8 * sizeof(R));
+    DevScene<R> sc;
+    StreamState* ss = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(D.mu);
+        if ((rc = emit ? emission_scene<R>(D, scene, sc, st) : observer_scene<R>(D, scene, sc, st))) return rc;
+        if ((rc = stream_state(D, st, &ss))) return rc;   // (entries of the map stay where they are: `ss` outlives the lock)
+        if (capturing && (frame_bytes > ss->obs_frame_bytes || batch_bytes > ss->obs_batch_bytes))
+            return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_observer_*: the stream's observer scratch must grow but the stream is being captured: make a call of "
+                                          "this size on the stream before hipStreamBeginCapture");
+        if ((rc = aa_need(*ss, ss->obs_frame, ss->obs_frame_bytes, frame_bytes))) return rc;
+        if ((rc = aa_need(*ss, ss->obs_batch, ss->obs_batch_bytes, batch_bytes))) return rc;
+    }
+    char* frame = (char*)ss->obs_frame;
+    R* d_states = (R*)ss->obs_batch;
+    ObsFrame<R>* d_frame = (ObsFrame<R>*)(frame + OBS_HEAD);
+    rtgr_counters* d_ctr = ctr ? (rtgr_counters*)frame : nullptr;
+    if (ctr) HIP_TRY(hipMemsetAsync(frame, 0, OBS_HEAD, st));
+    {
+        std::lock_guard<std::mutex> lk(D.mu);
+        KernelTimer timer(D, st, 0);
+        if ((rc = observer_frame_launch<R>(sc, ob, d_frame, st))) return rc;
+    }
+    rtgr_ray_outputs o1;
+    if (out) o1 = *out; else std::memset(&o1, 0, sizeof o1);
+    if (want_state) o1.state_end = frame + off_state;
+    if (want_hit32) o1.hit32 = (uint32_t*)(frame + off_hit);
+    if (want_status) o1.status = (uint8_t*)(frame + off_status);
+    // ---- batch by batch: whole rows [ja, jb) --------------------------------------------------------------------------------------
+    for (uint64_t ja = 0; ja < nj; ja += rows) {
+        const uint64_t jb = ja + rows < nj ? ja + rows : nj, first = ja * ni, m = (jb - ja) * ni;
+        {
+            std::lock_guard<std::mutex> lk(D.mu);
+            KernelTimer timer(D, st, 0);
+            if ((rc = observer_rays_launch<R>(d_frame, ni, nj, first, m, d_states, st))) return rc;
+        }
+        Window win;
+        win.plane_stride = n; win.out_offset = first;
+        if ((rc = trace_device<R>(D, scene, opt, d_states, nullptr, ni, nj, ja, jb, d_rgb, &o1, d_ctr, st, 1, 0, rows < nj ? &win : nullptr))) return rc;
+        if (shading) {   // the batch as a window of the frame: planes n apart
+            std::lock_guard<std::mutex> lk(D.mu);
+            KernelTimer timer(D, st, 0);
+            A.rgb = d_rgb + first; A.hit32 = o1.hit32 + first; A.status = o1.status + first; A.state_end = (const R*)o1.state_end + first * 8;
+            A.n = m; A.plane_stride = n;
+            if ((rc = shade_launch<R>(A, st))) return rc;
+        }
+        if (emit) {      // … each pixel emitted from its own start state, against this observer's e_0
+            std::lock_guard<std::mutex> lk(D.mu);
+            KernelTimer timer(D, st, 0);
+            E.sc = sc;
+            E.rgb = d_rgb + first; E.g = d_g ? d_g + first : nullptr; E.omega = nullptr; E.u_emit = nullptr; E.hit32 = o1.hit32 + first;
+            E.state_end = (const R*)o1.state_end + first * 8; E.state0 = d_states; E.obs = d_frame;
+            E.n = m; E.plane_stride = n; E.pixel_stride = 1; E.ni = ni; E.nj = nj;
+            if ((rc = emit_launch<R>(E, st))) return rc;
+        }
+    }
+    if (ctr) {
+        HIP_TRY(hipMemcpyAsync(ctr, d_ctr, sizeof *ctr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return RTGR_OK;
+}
+
+template <class R>
+int api::trace_observer_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
+                               const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, rtgr_counters* ctr,
+                               void* stream) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if ((rc = observer_trace_check(scene, obs, ni, nj, emit, d_rgb, out, d_g))) return rc;
+    DeviceCtx* D = nullptr;
+    if ((rc = device_of(c, d_rgb, &D))) return rc;
+    return trace_observer_on<R>(*D, scene, opt, obs, ni, nj, shade, emit, d_rgb, out, d_g, ctr, (hipStream_t)stream);
+}
+
+// host pointers: the same call on device 0 of the context, on its staging's compute stream, and the frame copied out
+template <class R>
+int api::trace_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
+                        const rtgr_shade* shade, const rtgr_disk_emission* emit, R* rgb, const rtgr_ray_outputs* out, R* g, rtgr_counters* ctr) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if ((rc = observer_trace_check(scene, obs, ni, nj, emit, rgb, out, g))) return rc;
+    DeviceCtx& D = *c->devs[0];
+    DeviceGuard guard(D.dev);
+    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    Staging* S = nullptr;
+    { std::lock_guard<std::mutex> lk(D.mu); if ((rc = staging_of(D, &S))) return rc; }
+    std::lock_guard<std::mutex> call_lock(S->mu);
+    HIP_TRY(hipStreamSynchronize(S->s_comp));   // (a previous call that failed half-way; the stream is idle otherwise)
+    const uint64_t n = ni * nj;
+    std::vector<RayArray> arrs = ray_arrays(rgb, out, sizeof(R));
+    const size_t off_g = ray_arrays_layout(arrs, n);
+    if ((rc = S->d_out.need(off_g + (g ? align256(n * sizeof(R)) : 0)))) return rc;
+    char* base = (char*)S->d_out.p;
+    const rtgr_ray_outputs o = ray_outputs_at(base, arrs, out);
+    R* d_g = g ? (R*)(base + off_g) : nullptr;
+    if ((rc = trace_observer_on<R>(D, scene, opt, obs, ni, nj, shade, emit, (R*)(base + arrs[0].off), out ? &o : nullptr, d_g, ctr, S->s_comp))) {
+        (void)hipStreamSynchronize(S->s_comp);
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(S->s_comp));
+    for (const RayArray& a : arrs) HIP_TRY(hipMemcpy(a.ptr, base + a.off, (size_t)n * a.elem * a.planes, hipMemcpyDeviceToHost));
+    if (g) HIP_TRY(hipMemcpy(g, d_g, (size_t)n * sizeof(R), hipMemcpyDeviceToHost));
+    return RTGR_OK;
+}
+
+// the states of rows [j0, j1) on device D, stream st: the frame kernel into the stream's scratch, the ray kernel into the caller's array
+template <class R>
+int api::make_observer_canvas_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, uint64_t j0,
+                                     uint64_t j1, R* d_state0, void* stream) {
+    if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
+    if (!d_state0) return fail(RTGR_ERR_BAD_ARG, "NULL argument");
+    RESOLVE_DEVICE(d_state0);
+    if ((rc = observer_canvas_check(ni, nj))) return rc;
+    if (j1 <= j0 || j1 > nj) return fail(RTGR_ERR_BAD_ARG, "bad canvas range");
+    DevObserver<R> ob;
+    if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard guard(D->dev);
+    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    std::lock_guard<std::mutex> lk(D->mu);
+    DevScene<R> sc;
+    if ((rc = observer_scene<R>(*D, scene, sc, st))) return rc;
+    StreamState* ss = nullptr;
+    if ((rc = stream_state(*D, st, &ss))) return rc;
+    if (capturing && OBS_HEAD + OBS_FRAME > ss->obs_frame_bytes)
+        return fail(RTGR_ERR_BAD_ARG, "rtgr_make_observer_canvas_device_*: the stream's observer scratch must grow but the stream is being captured");
+    if ((rc = aa_need(*ss, ss->obs_frame, ss->obs_frame_bytes, OBS_HEAD + OBS_FRAME))) return rc;
+    ObsFrame<R>* d_frame = (ObsFrame<R>*)((char*)ss->obs_frame + OBS_HEAD);
+    if ((rc = observer_frame_launch<R>(sc, ob, d_frame, st))) return rc;
+    return observer_rays_launch<R>(d_frame, ni, nj, j0 * ni, (j1 - j0) * ni, d_state0, st);
+}
+template <class R>
+int api::make_observer_canvas(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1,
+                              R* state0) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
+    if (!state0) return fail(RTGR_ERR_BAD_ARG, "NULL argument");
+    if ((rc = observer_canvas_check(ni, nj))) return rc;
+    if (j1 <= j0 || j1 > nj) return fail(RTGR_ERR_BAD_ARG, "bad canvas range");
+    const uint64_t n = ni * (j1 - j0);
+    DeviceGuard guard(c->devs[0]->dev);
+    DevBuf b;
+    if ((rc = b.alloc(n * 8 * sizeof(R)))) return rc;
+    if ((rc = make_observer_canvas_device<R>(c, scene, obs, ni, nj, j0, j1, (R*)b.p, nullptr))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(state0, b.p, n * 8 * sizeof(R), hipMemcpyDeviceToHost));
+    return RTGR_OK;
+}
+
+// the frame the kernels would use, on device 0 of the context (host pointers, blocking): the frame kernel itself
+template <class R>
+int api::eval_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, R* frame, R* omega, int* valid) {
+    rtgr_context* c = nullptr;
+    int rc = resolve_ctx(ctx, &c);
+    if (rc) return rc;
+    DevObserver<R> ob;
+    if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
+    DeviceCtx& D = *c->devs[0];
+    DeviceGuard guard(D.dev);
+    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    std::lock_guard<std::mutex> lk(D.mu);
+    DevScene<R> sc;
+    if ((rc = observer_scene<R>(D, scene, sc, nullptr))) return rc;
+    DevBuf b;
+    if ((rc = b.alloc(sizeof(ObsFrame<R>)))) return rc;
+    if ((rc = observer_frame_launch<R>(sc, ob, (ObsFrame<R>*)b.p, nullptr))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    ObsFrame<R> F;
+    HIP_TRY(hipMemcpy(&F, b.p, sizeof F, hipMemcpyDeviceToHost));
+    if (frame) std::memcpy(frame, F.e, sizeof F.e);
+    if (omega) *omega = F.omega;
+    if (valid) *valid = F.valid ? 1 : 0;
+    return RTGR_OK;
+}
+
+RTGR_INSTANTIATE_F64_F32(api::trace_observer_device);
+RTGR_INSTANTIATE_F64_F32(api::trace_observer);
+RTGR_INSTANTIATE_F64_F32(api::make_observer_canvas_device);
+RTGR_INSTANTIATE_F64_F32(api::make_observer_canvas);
+RTGR_INSTANTIATE_F64_F32(api::eval_observer);
+
+}  // namespace rtgr
