@@ -282,7 +282,7 @@ def check_scene(metric, objs, cam, ni=48, nj=48, opt=None, ctx=None):
     arguments (dict) or an rtgr_camera.  Raises RtgrError naming the number of rays that differ; returns None when the frames agree."""
     lib = _lib()
     sc = make_scene(metric, objs, ctx)
-    camera = cam if isinstance(cam, rtgr_camera) else make_camera(**cam)
+    camera = _camera(cam)
     opt = opt or solver_defaults()
     _abi.check(lib, lib.rtgr_scene_check(ctx, C.byref(sc), C.byref(opt), C.byref(camera), ni, nj, 0))
 
@@ -313,6 +313,11 @@ def make_camera(pos, widthx, widthy, normal):
         cam.pos[a], cam.widthx[a], cam.widthy[a], cam.normal[a] = (float(pos[a]), float(widthx[a]),
                                                                    float(widthy[a]), float(normal[a]))
     return cam
+
+
+def _camera(cam):
+    """make_camera arguments (a dict) or an rtgr_camera -> rtgr_camera"""
+    return cam if isinstance(cam, rtgr_camera) else make_camera(**cam)
 
 
 # ---- Pixel / Canvas (src/RayTraceGR.jl:445-455) -----------------------------------------------------------------
@@ -352,6 +357,29 @@ class Canvas:
 def _lib():
     lib = _abi.load()
     return lib
+
+
+def _ray_details(res, n, dtype, nobj):
+    """`details`: the per-ray output arrays of n rays into `res`, bound into the rtgr_ray_outputs returned (a list of more than 255
+    objects: `hit` is 32 bits wide and goes where the library calls it hit32)."""
+    outs = rtgr_ray_outputs()
+    wide = nobj > 255
+    res.update(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
+               hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
+    for name in ("state_end", "lambda_end", "status", "hit", "n_accept", "n_reject"):
+        setattr(outs, "hit32" if (wide and name == "hit") else name, res[name].ctypes.data)
+    return outs
+
+
+def _aa_arg(aa, res, n):
+    """The `aa` argument of a frame — None, dict(k=…, contrast=…, max_batch_rays=…) or an rtgr_aa — as the library takes it:
+    -> (rtgr_aa, the address of res["refined"] (added here), rtgr_aa_stats), or three None"""
+    if aa is None:
+        return None, None, None
+    aap = aa if isinstance(aa, _abi.rtgr_aa) else _abi.rtgr_aa(k=int(aa.get("k", 4)), flags=0, contrast=float(aa.get("contrast", 1.0 / 255.0)),
+                                                                 max_batch_rays=int(aa.get("max_batch_rays", 0)))
+    res["refined"] = np.zeros(n, np.uint8)
+    return aap, res["refined"].ctypes.data, _abi.rtgr_aa_stats()
 
 
 def make_canvas(metric, pos, widthx, widthy, normal, ni, nj, dtype=np.float64, ctx=None):
@@ -407,19 +435,13 @@ def trace_frames(metric, objs, cams, ni, nj, opt=None, dtype=np.float64, ctx=Non
     sc = make_scene(metric, objs, ctx)
     opt = opt or solver_defaults(dtype)
     K, n = len(cams), ni * nj
-    carr = (rtgr_camera * K)(*[c if isinstance(c, rtgr_camera) else make_camera(**c) for c in cams])
+    carr = (rtgr_camera * K)(*[_camera(c) for c in cams])
     rgb = [np.zeros((3, n), dtype) for _ in range(K)]
     ptrs = (C.c_void_p * K)(*[r.ctypes.data for r in rgb])
     ctrs = (rtgr_counters * K)()
     outs, per = None, [dict() for _ in range(K)]
     if details:
-        outs = (rtgr_ray_outputs * K)()
-        wide = sc.nobj > 255
-        for k in range(K):
-            per[k] = dict(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
-                          hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
-            for name, arr in per[k].items():
-                setattr(outs[k], "hit32" if (wide and name == "hit") else name, arr.ctypes.data)
+        outs = (rtgr_ray_outputs * K)(*[_ray_details(per[k], n, dtype, sc.nobj) for k in range(K)])
     fn = lib.rtgr_trace_frames_f64 if dtype == np.float64 else lib.rtgr_trace_frames_f32
     _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), K, carr, None, ni, nj, ptrs, outs, ctrs))
     return [dict(per[k], rgb=rgb[k], counters=ctrs[k].as_dict()) for k in range(K)]
@@ -434,22 +456,15 @@ def trace_aa(metric, objs, cam, ni, nj, k=4, contrast=1.0 / 255.0, opt=None, dty
     lib = _lib()
     sc = make_scene(metric, objs, ctx)
     opt = opt or solver_defaults(dtype)
-    camera = cam if isinstance(cam, rtgr_camera) else make_camera(**cam)
+    camera = _camera(cam)
     n = ni * nj
-    aa = _abi.rtgr_aa(k=int(k), flags=0, contrast=float(contrast), max_batch_rays=int(max_batch_rays))
-    res = dict(rgb=np.zeros((3, n), dtype), refined=np.zeros(n, np.uint8))
-    outs = None
-    if details:
-        outs = rtgr_ray_outputs()
-        wide = sc.nobj > 255
-        res.update(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
-                   hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
-        for name in ("state_end", "lambda_end", "status", "hit", "n_accept", "n_reject"):
-            setattr(outs, "hit32" if (wide and name == "hit") else name, res[name].ctypes.data)
-    ctr, stats = rtgr_counters(), _abi.rtgr_aa_stats()
+    res = dict(rgb=np.zeros((3, n), dtype))
+    aa, refined, stats = _aa_arg(dict(k=k, contrast=contrast, max_batch_rays=max_batch_rays), res, n)
+    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
+    ctr = rtgr_counters()
     fn = lib.rtgr_trace_aa_f64 if dtype == np.float64 else lib.rtgr_trace_aa_f32
-    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(camera), ni, nj, C.byref(aa), res["rgb"].ctypes.data, outs,
-                       res["refined"].ctypes.data, C.byref(ctr), C.byref(stats)))
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(camera), ni, nj, C.byref(aa), res["rgb"].ctypes.data, outs, refined,
+                       C.byref(ctr), C.byref(stats)))
     res["counters"], res["stats"] = ctr.as_dict(), stats.as_dict()
     return res
 
@@ -529,24 +544,12 @@ def trace_shaded(metric, objs, cam, ni, nj, textures=None, r_escape=0.0, aa=None
     lib = _lib()
     sc = make_scene(metric, objs, ctx)
     opt = opt or solver_defaults(dtype)
-    camera = cam if isinstance(cam, rtgr_camera) else make_camera(**cam)
+    camera = _camera(cam)
     n = ni * nj
     sh = make_shade(textures, r_escape)
     res = dict(rgb=np.zeros((3, n), dtype))
-    aap = refined = stats = None
-    if aa is not None:
-        aap = aa if isinstance(aa, _abi.rtgr_aa) else _abi.rtgr_aa(k=int(aa.get("k", 4)), flags=0, contrast=float(aa.get("contrast", 1.0 / 255.0)),
-                                                                     max_batch_rays=int(aa.get("max_batch_rays", 0)))
-        res["refined"] = np.zeros(n, np.uint8)
-        refined, stats = res["refined"].ctypes.data, _abi.rtgr_aa_stats()
-    outs = None
-    if details:
-        outs = rtgr_ray_outputs()
-        wide = sc.nobj > 255
-        res.update(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
-                   hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
-        for name in ("state_end", "lambda_end", "status", "hit", "n_accept", "n_reject"):
-            setattr(outs, "hit32" if (wide and name == "hit") else name, res[name].ctypes.data)
+    aap, refined, stats = _aa_arg(aa, res, n)
+    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
     ctr = rtgr_counters()
     fn = lib.rtgr_trace_shaded_f64 if dtype == np.float64 else lib.rtgr_trace_shaded_f32
     _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(camera), ni, nj, C.byref(sh), aap, res["rgb"].ctypes.data, outs, refined,
@@ -589,24 +592,12 @@ def trace_emission(metric, objs, cam, ni, nj, emission, textures=None, r_escape=
     lib = _lib()
     sc = make_scene(metric, objs, ctx)
     opt = opt or solver_defaults(dtype)
-    camera = cam if isinstance(cam, rtgr_camera) else make_camera(**cam)
+    camera = _camera(cam)
     n = ni * nj
     sh = make_shade(textures, r_escape) if textures else None
     res = dict(rgb=np.zeros((3, n), dtype), g=np.zeros(n, dtype))
-    aap = refined = stats = None
-    if aa is not None:
-        aap = aa if isinstance(aa, _abi.rtgr_aa) else _abi.rtgr_aa(k=int(aa.get("k", 4)), flags=0, contrast=float(aa.get("contrast", 1.0 / 255.0)),
-                                                                     max_batch_rays=int(aa.get("max_batch_rays", 0)))
-        res["refined"] = np.zeros(n, np.uint8)
-        refined, stats = res["refined"].ctypes.data, _abi.rtgr_aa_stats()
-    outs = None
-    if details:
-        outs = rtgr_ray_outputs()
-        wide = sc.nobj > 255
-        res.update(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
-                   hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
-        for name in ("state_end", "lambda_end", "status", "hit", "n_accept", "n_reject"):
-            setattr(outs, "hit32" if (wide and name == "hit") else name, res[name].ctypes.data)
+    aap, refined, stats = _aa_arg(aa, res, n)
+    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
     ctr = rtgr_counters()
     fn = lib.rtgr_trace_emission_f64 if dtype == np.float64 else lib.rtgr_trace_emission_f32
     _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(camera), ni, nj, None if sh is None else C.byref(sh), C.byref(emission), aap, res["rgb"].ctypes.data, outs,
@@ -702,14 +693,7 @@ def trace_observer(metric, objs, observer, ni, nj, emission=None, textures=None,
     res = dict(rgb=np.zeros((3, n), dtype))
     if emission is not None:
         res["g"] = np.zeros(n, dtype)
-    outs = None
-    if details:
-        outs = rtgr_ray_outputs()
-        wide = sc.nobj > 255
-        res.update(state_end=np.zeros((n, 8), dtype), lambda_end=np.zeros(n, dtype), status=np.zeros(n, np.uint8),
-                   hit=np.zeros(n, np.uint32 if wide else np.uint8), n_accept=np.zeros(n, np.uint32), n_reject=np.zeros(n, np.uint32))
-        for name in ("state_end", "lambda_end", "status", "hit", "n_accept", "n_reject"):
-            setattr(outs, "hit32" if (wide and name == "hit") else name, res[name].ctypes.data)
+    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
     ctr = rtgr_counters()
     fn = lib.rtgr_trace_observer_f64 if dtype == np.float64 else lib.rtgr_trace_observer_f32
     _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(observer), ni, nj, None if sh is None else C.byref(sh),

@@ -10,7 +10,7 @@
 namespace rtgr {
 
 constexpr uint64_t AA_DEFAULT_BATCH = 1ull << 22;   // sub-rays per batch (rtgr_aa.max_batch_rays = 0)
-constexpr size_t AA_HEAD = 256;                     // head of the frame scratch: rtgr_counters (64 bytes), then the refined count
+constexpr EntryWords AA_WORDS = {"rtgr_trace_aa_*", "anti-aliasing", true};
 
 static int aa_check(const rtgr_scene* scene, const rtgr_camera* cam, const rtgr_aa* aa, uint64_t ni, uint64_t nj) {
     if (!scene) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
@@ -19,23 +19,9 @@ static int aa_check(const rtgr_scene* scene, const rtgr_camera* cam, const rtgr_
     if (aa->flags != 0) return fail(RTGR_ERR_BAD_ARG, "rtgr_aa.flags must be 0");
     if (aa->contrast != aa->contrast) return fail(RTGR_ERR_BAD_ARG, "rtgr_aa.contrast is NaN (< 0: every pixel, +Inf: class edges only)");
     if (!cam) return fail(RTGR_ERR_BAD_ARG, "anti-aliasing needs a camera (cam is NULL): the sub-rays are generated from it");
-    if ((scene->metric & ~RTGR_METRIC_GENERIC) == RTGR_USER)
-        return fail(RTGR_ERR_BAD_ARG, "anti-aliasing of a scene whose METRIC is RTGR_USER is not supported (its camera kernel lives in the run-time "
-                                      "unit); user objects under a built-in metric are");
-    if (ni == 0 || nj == 0 || ni > (1ull << 32) || nj > (1ull << 32) || ni * nj > (1ull << 34))
-        return fail(RTGR_ERR_BAD_ARG, "bad canvas: need ni, nj > 0 and at most 2^34 pixels for an anti-aliased frame");
-    return RTGR_OK;
-}
-
-// grow-only scratch of a stream, retired like its workspace (D.mu held; never called during capture: the entry point refuses first)
-int aa_need(StreamState& ss, void*& p, size_t& have, size_t bytes) {
-    if (bytes <= have) return RTGR_OK;
-    void* q = nullptr;
-    HIP_TRY(hipMalloc(&q, bytes));
-    if (p) ss.retired.push_back(p);   // kernels of an earlier call may still be in flight on it
-    p = q;
-    have = bytes;
-    return RTGR_OK;
+    int rc;
+    if ((rc = builtin_metric_check(scene, "anti-aliasing of", "its camera kernel lives"))) return rc;
+    return canvas_check(ni, nj, "an anti-aliased frame");
 }
 
 // the call on device D, stream st; d_rgb, the members of `out` and d_refined are pointers of that device
@@ -53,53 +39,43 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
                                       "between its two passes (a synchronisation cannot be captured)");
     const uint64_t n = ni * nj;
     const uint32_t k = aa->k, kk = k * k;
-    const bool want_status = !(out && out->status), want_hit32 = !(out && out->hit32);
-    const ShadeDesc<R>* shade = after ? after->shade : nullptr;
-    const DevEmission<R>* emit = after ? after->emit : nullptr;
-    const bool post = shade || emit;
-    const bool want_state = post && !(out && out->state_end);   // (the shading and emission kernels read the end states)
+    const AfterTrace<R> none;
+    const AfterTrace<R>& aft = after ? *after : none;
+    const bool post = aft.shade || aft.emit;
 
-    // ---- frame scratch: [counters | count] [hit32] [status] [list] [end states: shaded / emitted frames only] -------------------------------
-    const size_t off_hit = AA_HEAD, off_status = off_hit + (want_hit32 ? align256(n * sizeof(uint32_t)) : 0),
-                 off_list = off_status + (want_status ? align256(n) : 0), off_state = off_list + align256(n * sizeof(uint64_t)),
-                 frame_bytes = off_state + (want_state ? align256(n * 8 * sizeof(R)) : 0);
-    StreamState* ss = nullptr;
+    // ---- frame scratch: the counters and the refined count, the list, and what the caller did not ask for of the hit map and the status
+    // bytes the edge rule reads — and of the end states the shading and emission kernels read --------------------------------------------------
+    FrameNeeds need;
+    need.list = true;
+    need.hit32 = !(out && out->hit32);
+    need.status = !(out && out->status);
+    need.state_end = post && !(out && out->state_end);
+    FrameScratch fs;
     DevScene<R> sc;
     DevCamera<R> cm;
     {
         std::lock_guard<std::mutex> lk(D.mu);
-        if ((rc = stream_state(D, st, &ss))) return rc;   // (entries of the map stay where they are: `ss` outlives the lock)
-        if ((rc = aa_need(*ss, ss->aa_frame, ss->aa_frame_bytes, frame_bytes))) return rc;
+        if ((rc = frame_scratch(D, st, false, AA_WORDS, n, sizeof(R), need, 0, out, ctr, fs))) return rc;
     }
-    char* frame = (char*)ss->aa_frame;
-    rtgr_counters* d_ctr = (rtgr_counters*)frame;
-    unsigned long long* d_count = (unsigned long long*)(frame + sizeof(rtgr_counters));
-    uint64_t* d_list = (uint64_t*)(frame + off_list);
-    HIP_TRY(hipMemsetAsync(frame, 0, AA_HEAD, st));
+    StreamState* ss = fs.ss;
+    unsigned long long* d_count = (unsigned long long*)(fs.base + sizeof(rtgr_counters));
+    uint64_t* d_list = (uint64_t*)(fs.base + fs.at.list);
+    const rtgr_ray_outputs& o1 = fs.o1;
 
     // ---- pass 1: the plain frame, with the hit map and the status bytes the edge rule reads --------------------------------------
-    rtgr_ray_outputs o1;
-    if (out) o1 = *out; else std::memset(&o1, 0, sizeof o1);
-    if (want_hit32) o1.hit32 = (uint32_t*)(frame + off_hit);
-    if (want_status) o1.status = (uint8_t*)(frame + off_status);
-    if (want_state) o1.state_end = frame + off_state;
-    if ((rc = trace_device<R>(D, scene, opt, nullptr, cam, ni, nj, 0, nj, d_rgb, &o1, ctr ? d_ctr : nullptr, st))) return rc;
+    if ((rc = trace_device<R>(D, scene, opt, nullptr, cam, ni, nj, 0, nj, d_rgb, &o1, fs.d_ctr, st))) return rc;
     {
         std::lock_guard<std::mutex> lk(D.mu);
         const UserModule* user = nullptr;
         if ((rc = convert_scene<R>(D, scene, sc, &user, st))) return rc;   // (what the sub-ray and emission kernels read of the scene: its metric)
         convert_camera<R>(cam, cm);
     }
-    if (shade) {   // the edge rule reads the SHADED colours
-        std::lock_guard<std::mutex> lk(D.mu);
-        KernelTimer timer(D, st, 0);
-        if ((rc = shade_launch<R>(ShadeArgs<R>{d_rgb, o1.hit32, o1.status, (const R*)o1.state_end, n, n, *shade}, st))) return rc;
-    }
-    if (emit) {    // … and the EMITTED ones; the pixel-centre rays start from the camera's own pixels
-        std::lock_guard<std::mutex> lk(D.mu);
-        KernelTimer timer(D, st, 0);
-        if ((rc = emit_launch<R>(EmitArgs<R>{d_rgb, after->d_g, nullptr, nullptr, o1.hit32, (const R*)o1.state_end, nullptr, n, n, 1, ni, nj, sc, cm, *emit}, st))) return rc;
-    }
+    TracedPixels<R> px;   // the edge rule reads the SHADED and EMITTED colours; the pixel-centre rays start from the camera's own pixels
+    px.rgb = d_rgb; px.plane_stride = n; px.g = aft.d_g;
+    px.hit32 = o1.hit32; px.status = o1.status; px.state_end = (const R*)o1.state_end;
+    px.n = n; px.ni = ni; px.nj = nj;
+    px.sc = &sc; px.cam = &cm;
+    if (post && (rc = after_trace<R>(D, st, aft, px))) return rc;
 
     // ---- the edge rule -------------------------------------------------------------------------------------------------------------
     {
@@ -124,12 +100,12 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
                  batch_bytes = off_status2 + (post ? align256((size_t)m_max * kk) : 0);
     if (count) {
         std::lock_guard<std::mutex> lk(D.mu);
-        if ((rc = aa_need(*ss, ss->aa_batch, ss->aa_batch_bytes, batch_bytes))) return rc;
+        if ((rc = scratch_need(*ss, ss->batch, ss->batch_bytes, batch_bytes))) return rc;
     }
     for (uint64_t b = 0; b < batches; b++) {
         const uint64_t first = b * per, m = count - first < per ? count - first : per;
-        R* d_states = (R*)ss->aa_batch;
-        R* d_sub = (R*)((char*)ss->aa_batch + off_sub);
+        R* d_states = (R*)ss->batch;
+        R* d_sub = (R*)((char*)ss->batch + off_sub);
         {
             std::lock_guard<std::mutex> lk(D.mu);
             KernelTimer timer(D, st, 0);
@@ -138,20 +114,19 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
         rtgr_ray_outputs o2;
         std::memset(&o2, 0, sizeof o2);
         if (post) {
-            o2.state_end = (char*)ss->aa_batch + off_end;
-            o2.hit32 = (uint32_t*)((char*)ss->aa_batch + off_hit2);
-            o2.status = (uint8_t*)((char*)ss->aa_batch + off_status2);
+            o2.state_end = (char*)ss->batch + off_end;
+            o2.hit32 = (uint32_t*)((char*)ss->batch + off_hit2);
+            o2.status = (uint8_t*)((char*)ss->batch + off_status2);
         }
-        if ((rc = trace_device<R>(D, scene, opt, d_states, nullptr, m * kk, 1, 0, 1, d_sub, post ? &o2 : nullptr, ctr ? d_ctr : nullptr, st))) return rc;
-        if (shade) {   // the sub-rays as a one-row canvas of m k² pixels
-            std::lock_guard<std::mutex> lk(D.mu);
-            KernelTimer timer(D, st, 0);
-            if ((rc = shade_launch<R>(ShadeArgs<R>{d_sub, o2.hit32, o2.status, (const R*)o2.state_end, m * kk, m * kk, *shade}, st))) return rc;
-        }
-        if (emit) {    // … each emitted from its own sub-ray state
-            std::lock_guard<std::mutex> lk(D.mu);
-            KernelTimer timer(D, st, 0);
-            if ((rc = emit_launch<R>(EmitArgs<R>{d_sub, nullptr, nullptr, nullptr, o2.hit32, (const R*)o2.state_end, d_states, m * kk, m * kk, 1, 0, 0, sc, cm, *emit}, st))) return rc;
+        if ((rc = trace_device<R>(D, scene, opt, d_states, nullptr, m * kk, 1, 0, 1, d_sub, post ? &o2 : nullptr, fs.d_ctr, st))) return rc;
+        if (post) {   // the sub-rays as a one-row canvas of m k² pixels, each emitted from its own sub-ray state
+            TracedPixels<R> sub;
+            sub.rgb = d_sub; sub.plane_stride = m * kk;
+            sub.hit32 = o2.hit32; sub.status = o2.status; sub.state_end = (const R*)o2.state_end;
+            sub.state0 = d_states;
+            sub.n = m * kk;
+            sub.sc = &sc; sub.cam = &cm;
+            if ((rc = after_trace<R>(D, st, aft, sub))) return rc;
         }
         {
             std::lock_guard<std::mutex> lk(D.mu);
@@ -159,10 +134,7 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
             if ((rc = aa_reduce<R>(d_sub, d_list + first, m, k, d_rgb, n, st))) return rc;
         }
     }
-    if (ctr) {
-        HIP_TRY(hipMemcpyAsync(ctr, d_ctr, sizeof *ctr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    if ((rc = counters_back(fs, ctr, st))) return rc;
     if (stats) { stats->pixels = n; stats->refined = count; stats->sub_rays = count * kk; stats->batches = batches; }
     return RTGR_OK;
 }
@@ -191,28 +163,9 @@ int api::trace_aa(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver*
     if (!rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     if ((rc = aa_check(scene, cam, aa, ni, nj))) return rc;
     if ((rc = check_redshift_outputs(out))) return rc;
-    DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-    Staging* S = nullptr;
-    { std::lock_guard<std::mutex> lk(D.mu); if ((rc = staging_of(D, &S))) return rc; }
-    std::lock_guard<std::mutex> call_lock(S->mu);
-    HIP_TRY(hipStreamSynchronize(S->s_comp));   // (a previous call that failed half-way; the stream is idle otherwise)
-    const uint64_t n = ni * nj;
-    std::vector<RayArray> arrs = ray_arrays(rgb, out, sizeof(R));
-    const size_t off_refined = ray_arrays_layout(arrs, n);
-    if ((rc = S->d_out.need(off_refined + (refined ? align256(n) : 0)))) return rc;
-    char* base = (char*)S->d_out.p;
-    const rtgr_ray_outputs o = ray_outputs_at(base, arrs, out);
-    uint8_t* d_refined = refined ? (uint8_t*)(base + off_refined) : nullptr;
-    if ((rc = trace_aa_on<R>(D, scene, opt, cam, ni, nj, aa, (R*)(base + arrs[0].off), out ? &o : nullptr, d_refined, ctr, stats, S->s_comp, nullptr))) {
-        (void)hipStreamSynchronize(S->s_comp);
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(S->s_comp));
-    for (const RayArray& a : arrs) HIP_TRY(hipMemcpy(a.ptr, base + a.off, (size_t)n * a.elem * a.planes, hipMemcpyDeviceToHost));
-    if (refined) HIP_TRY(hipMemcpy(refined, d_refined, n, hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    return staged_frame<R>(c, ni * nj, rgb, out, refined, nullptr, [&](DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs* d_out, uint8_t* d_refined, R*, hipStream_t st) {
+        return trace_aa_on<R>(D, scene, opt, cam, ni, nj, aa, d_rgb, d_out, d_refined, ctr, stats, st, nullptr);
+    });
 }
 RTGR_INSTANTIATE_F64_F32(trace_aa_on);
 RTGR_INSTANTIATE_F64_F32(api::trace_aa_device);

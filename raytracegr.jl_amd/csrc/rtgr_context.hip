@@ -48,8 +48,6 @@ static Knobs knobs_from_env() {  // once per context
 // ---------------------------------------------------------------------------------------------------------------------
 // workspaces
 // ---------------------------------------------------------------------------------------------------------------------
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <class R>
 size_t workspace_bytes(uint64_t rays, bool with_state) {
     const int recw = with_state ? REC_TAIL_STATE : REC_TAIL;   // the event records' tails; their heads overlay the hand-over records
@@ -153,12 +151,8 @@ void free_device_state(DeviceCtx& d, bool all) {
         if (all) {
             if (kv.second.ws) (void)hipFree(kv.second.ws);
             if (kv.second.queue) (void)hipFree(kv.second.queue);
-            if (kv.second.aa_frame) (void)hipFree(kv.second.aa_frame);
-            if (kv.second.aa_batch) (void)hipFree(kv.second.aa_batch);
-            if (kv.second.shade_frame) (void)hipFree(kv.second.shade_frame);
-            if (kv.second.emit_frame) (void)hipFree(kv.second.emit_frame);
-            if (kv.second.obs_frame) (void)hipFree(kv.second.obs_frame);
-            if (kv.second.obs_batch) (void)hipFree(kv.second.obs_batch);
+            if (kv.second.frame) (void)hipFree(kv.second.frame);
+            if (kv.second.batch) (void)hipFree(kv.second.batch);
         }
     }
     for (auto& g : d.retired_grids) { (void)hipFree(g.d64); (void)hipFree(g.d32); }   // unloaded grid metrics (idle device: see above)

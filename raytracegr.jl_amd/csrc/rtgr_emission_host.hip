@@ -1,21 +1,19 @@
-// rtgr_emission_host.hip — disk emission (include/rtgr.h "disk emission"): the checks of an rtgr_disk_emission, the emitted trace — a
-// plain trace_device, or the anti-aliased one of rtgr_aa_host.hip, with the shading kernel (if textures are bound) and the emission
-// kernel behind it — and the pointwise hook.  Host code only: the kernels are rtgr_emit.hip's, the model rtgr_emission.hpp's.
+// rtgr_emission_host.hip — disk emission (include/rtgr.h "disk emission"): the checks of an rtgr_disk_emission, the entry points of the
+// emitted trace — the camera frame of rtgr_frame_host.hip with an emitting disk — and the pointwise hook.  Host code only: the kernels
+// are rtgr_emit.hip's, the model rtgr_emission.hpp's.
 #include "rtgr_internal.hpp"
 
 namespace rtgr {
 
-constexpr size_t EMIT_HEAD = 256;   // head of the frame scratch: rtgr_counters (64 bytes)
+constexpr EntryWords EMISSION_WORDS = {"rtgr_trace_emission_*", "emission", true};
 
 // the caller's parameters into the record the kernels read, for scalar type R; `shade` (may be null): the binds of the same call
 template <class R>
 int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, const rtgr_disk_emission* emit, DevEmission<R>& em) {
     if (!scene) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
     if (!emit) return fail(RTGR_ERR_BAD_ARG, "rtgr_disk_emission is NULL (emit)");
-    const uint32_t metric = scene->metric & ~(uint32_t)RTGR_METRIC_GENERIC;
-    if (metric == RTGR_USER)
-        return fail(RTGR_ERR_BAD_ARG, "disk emission in a scene whose METRIC is RTGR_USER is not supported (its kernels live in the run-time unit); "
-                                      "user objects under a built-in metric are");
+    int rc;
+    if ((rc = builtin_metric_check(scene, "disk emission in", "its kernels live"))) return rc;
     if (scene->nobj > RTGR_OBJECTS_LIMIT || (!scene->objects && scene->nobj > RTGR_MAX_OBJECTS))
         return fail(RTGR_ERR_BAD_ARG, "bad object list: more than RTGR_MAX_OBJECTS objects need rtgr_scene.objects");
     if (emit->object == 0 || emit->object > scene->nobj)
@@ -53,98 +51,6 @@ int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, const rtg
     return RTGR_OK;
 }
 
-// the scene as the emission kernel reads it (D.mu held); a time-dependent grid has no stationary emitter
-template <class R>
-int emission_scene(DeviceCtx& D, const rtgr_scene* scene, DevScene<R>& sc, hipStream_t st) {
-    const UserModule* user = nullptr;
-    int rc;
-    if ((rc = convert_scene<R>(D, scene, sc, &user, st))) return rc;
-    if (sampled_on(sc.metric, 4))
-        return fail(RTGR_ERR_BAD_ARG, "disk emission in a time-dependent (4-D) grid metric is not supported: the emitter's orbit needs a stationary metric");
-    return RTGR_OK;
-}
-
-// the call on device D, stream st; d_rgb, d_g, the members of `out` and d_refined are pointers of that device
-template <class R>
-static int trace_emission_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
-                             const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, R* d_g,
-                             uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, hipStream_t st) {
-    int rc;
-    if ((rc = shaded_check(cam, aa, d_refined, stats, ni, nj))) return rc;
-    if ((rc = check_redshift_outputs(out))) return rc;
-    EmitArgs<R> E;
-    if ((rc = emission_resolve<R>(scene, shade, emit, E.em))) return rc;
-    ShadeArgs<R> A;
-    if (shade && (rc = shade_resolve<R>(D, scene, shade, A.desc))) return rc;
-    const bool shading = shade && A.desc.nbind != 0;
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-    if (aa) {
-        {
-            std::lock_guard<std::mutex> lk(D.mu);
-            if ((rc = emission_scene<R>(D, scene, E.sc, st))) return rc;
-        }
-        AfterTrace<R> after;
-        after.shade = shading ? &A.desc : nullptr;
-        after.emit = &E.em;
-        after.d_g = d_g;
-        return trace_aa_on<R>(D, scene, opt, cam, ni, nj, aa, d_rgb, out, d_refined, ctr, stats, st, &after);
-    }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    if (capturing && ctr)
-        return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_emission_*: the stream is being captured and `ctr` asks for a synchronisation at the end of the call "
-                                      "(which cannot be captured): pass ctr = NULL");
-    const uint64_t n = ni * nj;
-    const bool want_state = !(out && out->state_end), want_hit32 = !(out && out->hit32), want_status = shading && !(out && out->status);
-    // ---- frame scratch: [counters] [end states] [hit32] [status] -------------------------------------------------------------------
-    const size_t off_state = EMIT_HEAD, off_hit = off_state + (want_state ? align256(n * 8 * sizeof(R)) : 0),
-                 off_status = off_hit + (want_hit32 ? align256(n * sizeof(uint32_t)) : 0), frame_bytes = off_status + (want_status ? align256(n) : 0);
-    char* frame = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(D.mu);
-        if ((rc = emission_scene<R>(D, scene, E.sc, st))) return rc;
-        convert_camera<R>(cam, E.cam);
-        if (ctr || frame_bytes > EMIT_HEAD) {
-            StreamState* ss = nullptr;
-            if ((rc = stream_state(D, st, &ss))) return rc;
-            if (capturing && frame_bytes > ss->emit_frame_bytes)
-                return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_emission_*: the stream's emission scratch must grow but the stream is being captured: make a call of "
-                                              "this size on the stream before hipStreamBeginCapture");
-            if ((rc = aa_need(*ss, ss->emit_frame, ss->emit_frame_bytes, frame_bytes))) return rc;
-            frame = (char*)ss->emit_frame;
-        }
-    }
-    rtgr_counters* d_ctr = ctr ? (rtgr_counters*)frame : nullptr;
-    if (ctr) HIP_TRY(hipMemsetAsync(frame, 0, EMIT_HEAD, st));
-    // ---- the plain frame, with what the shading and emission kernels read of it ------------------------------------------------------
-    rtgr_ray_outputs o1;
-    if (out) o1 = *out; else std::memset(&o1, 0, sizeof o1);
-    if (want_state) o1.state_end = frame + off_state;
-    if (want_hit32) o1.hit32 = (uint32_t*)(frame + off_hit);
-    if (want_status) o1.status = (uint8_t*)(frame + off_status);
-    if ((rc = trace_device<R>(D, scene, opt, nullptr, cam, ni, nj, 0, nj, d_rgb, &o1, d_ctr, st))) return rc;
-    if (shading) {
-        std::lock_guard<std::mutex> lk(D.mu);
-        KernelTimer timer(D, st, 0);
-        A.rgb = d_rgb; A.hit32 = o1.hit32; A.status = o1.status; A.state_end = (const R*)o1.state_end;
-        A.n = n; A.plane_stride = n;
-        if ((rc = shade_launch<R>(A, st))) return rc;
-    }
-    {
-        std::lock_guard<std::mutex> lk(D.mu);
-        KernelTimer timer(D, st, 0);
-        E.rgb = d_rgb; E.g = d_g; E.omega = nullptr; E.u_emit = nullptr; E.hit32 = o1.hit32; E.state_end = (const R*)o1.state_end; E.state0 = nullptr; E.obs = nullptr;
-        E.n = n; E.plane_stride = n; E.pixel_stride = 1; E.ni = ni; E.nj = nj;
-        if ((rc = emit_launch<R>(E, st))) return rc;
-    }
-    if (ctr) {
-        HIP_TRY(hipMemcpyAsync(ctr, d_ctr, sizeof *ctr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return RTGR_OK;
-}
-
 template <class R>
 int api::trace_emission_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
                                const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out,
@@ -157,7 +63,7 @@ int api::trace_emission_device(rtgr_context* ctx, const rtgr_scene* scene, const
     if ((rc = shaded_check(cam, aa, d_refined, stats, ni, nj))) return rc;
     DeviceCtx* D = nullptr;
     if ((rc = device_of(c, d_rgb, &D))) return rc;
-    return trace_emission_on<R>(*D, scene, opt, cam, ni, nj, shade, emit, aa, d_rgb, out, d_g, d_refined, ctr, stats, (hipStream_t)stream);
+    return trace_camera_frame_on<R>(*D, scene, opt, cam, ni, nj, shade, emit, aa, d_rgb, out, d_g, d_refined, ctr, stats, (hipStream_t)stream, EMISSION_WORDS);
 }
 
 // host pointers: the same call on device 0 of the context, on its staging's compute stream, and the frame copied out
@@ -172,32 +78,9 @@ int api::trace_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_s
     if (!emit) return fail(RTGR_ERR_BAD_ARG, "rtgr_disk_emission is NULL (emit)");
     if ((rc = shaded_check(cam, aa, refined, stats, ni, nj))) return rc;
     if ((rc = check_redshift_outputs(out))) return rc;
-    DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-    Staging* S = nullptr;
-    { std::lock_guard<std::mutex> lk(D.mu); if ((rc = staging_of(D, &S))) return rc; }
-    std::lock_guard<std::mutex> call_lock(S->mu);
-    HIP_TRY(hipStreamSynchronize(S->s_comp));   // (a previous call that failed half-way; the stream is idle otherwise)
-    const uint64_t n = ni * nj;
-    std::vector<RayArray> arrs = ray_arrays(rgb, out, sizeof(R));
-    const size_t off_refined = ray_arrays_layout(arrs, n);
-    const size_t off_g = off_refined + (refined ? align256(n) : 0);
-    if ((rc = S->d_out.need(off_g + (g ? align256(n * sizeof(R)) : 0)))) return rc;
-    char* base = (char*)S->d_out.p;
-    const rtgr_ray_outputs o = ray_outputs_at(base, arrs, out);
-    uint8_t* d_refined = refined ? (uint8_t*)(base + off_refined) : nullptr;
-    R* d_g = g ? (R*)(base + off_g) : nullptr;
-    if ((rc = trace_emission_on<R>(D, scene, opt, cam, ni, nj, shade, emit, aa, (R*)(base + arrs[0].off), out ? &o : nullptr, d_g, d_refined, ctr, stats,
-                                   S->s_comp))) {
-        (void)hipStreamSynchronize(S->s_comp);
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(S->s_comp));
-    for (const RayArray& a : arrs) HIP_TRY(hipMemcpy(a.ptr, base + a.off, (size_t)n * a.elem * a.planes, hipMemcpyDeviceToHost));
-    if (refined) HIP_TRY(hipMemcpy(refined, d_refined, n, hipMemcpyDeviceToHost));
-    if (g) HIP_TRY(hipMemcpy(g, d_g, (size_t)n * sizeof(R), hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    return staged_frame<R>(c, ni * nj, rgb, out, refined, g, [&](DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs* d_out, uint8_t* d_refined, R* d_g, hipStream_t st) {
+        return trace_camera_frame_on<R>(D, scene, opt, cam, ni, nj, shade, emit, aa, d_rgb, d_out, d_g, d_refined, ctr, stats, st, EMISSION_WORDS);
+    });
 }
 
 // the model at n pairs of states, on device 0 of the context (host pointers): the emission kernel itself, in point mode.  obs (may be
@@ -219,7 +102,7 @@ int api::eval_disk_emission_observer(rtgr_context* ctx, const rtgr_scene* scene,
     DeviceGuard guard(D.dev);
     if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(D.mu);
-    if ((rc = emission_scene<R>(D, scene, E.sc, nullptr))) return rc;
+    if ((rc = stationary_scene<R>(D, scene, E.sc, nullptr, EMISSION_NEEDS_STATIONARY))) return rc;
     if (n == 0) return RTGR_OK;
     const size_t sbytes = (size_t)n * 8 * sizeof(R);
     DevBuf d_s0, d_se, d_om, d_u, d_g, d_rgb, d_frame;
@@ -255,7 +138,6 @@ int api::eval_disk_emission(rtgr_context* ctx, const rtgr_scene* scene, const rt
     return eval_disk_emission_observer<R>(ctx, scene, emit, nullptr, s0, s_end, n, omega, u_emit, g, rgb);
 }
 RTGR_INSTANTIATE_F64_F32(emission_resolve);
-RTGR_INSTANTIATE_F64_F32(emission_scene);
 RTGR_INSTANTIATE_F64_F32(api::eval_disk_emission_observer);
 RTGR_INSTANTIATE_F64_F32(api::eval_disk_emission);
 

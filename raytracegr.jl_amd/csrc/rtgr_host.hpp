@@ -169,22 +169,14 @@ struct StreamState {
     size_t ws_bytes = 0;
     unsigned long long* queue = nullptr;  // 8 work-queue heads; stream order makes one slot per stream enough
     std::vector<void*> retired;           // superseded workspaces: kept alive for graphs captured earlier
-    // scratch of rtgr_trace_aa_device_* on this stream (rtgr_aa_host.hip), grow-only and retired like the workspace: per FRAME the
-    // counters + the refined count, the hit / status arrays the caller did not ask for and the index list of the refined pixels; per
-    // BATCH the sub-ray states and the sub-colours
-    void* aa_frame = nullptr; size_t aa_frame_bytes = 0;
-    void* aa_batch = nullptr; size_t aa_batch_bytes = 0;
-    // scratch of rtgr_trace_shaded_device_* without anti-aliasing (rtgr_texture_host.hip), likewise: the counters, then the end states /
-    // hit map / status bytes the shading kernel reads and the caller did not ask for
-    void* shade_frame = nullptr; size_t shade_frame_bytes = 0;
-    // scratch of rtgr_trace_emission_device_* without anti-aliasing (rtgr_emission_host.hip), likewise: the counters, then the end states /
-    // hit map / status bytes the emission and shading kernels read and the caller did not ask for
-    void* emit_frame = nullptr; size_t emit_frame_bytes = 0;
-    // scratch of rtgr_trace_observer_device_* / rtgr_make_observer_canvas_device_* (rtgr_observer_host.hip), likewise: per FRAME the
-    // counters, the observer's frame record, then the end states / hit map / status bytes the shading and emission kernels read and the
-    // caller did not ask for; per BATCH the ray states of its rows
-    void* obs_frame = nullptr; size_t obs_frame_bytes = 0;
-    void* obs_batch = nullptr; size_t obs_batch_bytes = 0;
+    // scratch of the frame calls on this stream (rtgr_frame_host.hip: frame_scratch), grow-only and retired like the workspace.  One of
+    // each for every entry point — anti-aliased, shaded, emitted and observer frames, rtgr_make_observer_canvas_device_*: a call has
+    // at most one of each live and the calls on a stream are ordered.  Per FRAME (FrameLayout, rtgr_internal.hpp): the counters and
+    // the refined count, the observer's frame record, the index list of the refined pixels, then the end states / hit map / status
+    // bytes the post-trace kernels read and the caller did not ask for.  Per BATCH: the sub-ray states, sub-colours and what the
+    // post-trace kernels read of the sub-rays (rtgr_aa_host.hip), or the ray states of an observer's rows (rtgr_observer_host.hip)
+    void* frame = nullptr; size_t frame_bytes = 0;
+    void* batch = nullptr; size_t batch_bytes = 0;
 };
 
 struct Staging;  // host entry points (rtgr_internal.hpp)
@@ -262,7 +254,7 @@ struct LaunchEnv {
     const Knobs* knobs = nullptr;      // this call's own launch options (the load-time probe, rtgr_scene_check); null: the device's
 };
 
-size_t align256(size_t b);
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 template <class R> size_t workspace_bytes(uint64_t rays, bool with_state);
 template <class R> uint64_t pick_chunk(const DeviceCtx& d, const StreamState& ss, uint64_t n, bool with_state);
 int ensure_workspace(DeviceCtx& d, StreamState& ss, size_t bytes, hipStream_t st);
@@ -403,13 +395,28 @@ struct EmitArgs {
 };
 template <class R>
 int emit_launch(const EmitArgs<R>& A, hipStream_t st);
-// What is applied to a traced frame before anyone reads its colours (trace_aa_on, rtgr_aa_host.hip): the textures of a shaded frame,
-// then the emission of a disk — either may be null.  d_g: the frequency ratios of the pixel-centre rays (pass 1), or null.
+// What is applied to a traced frame before anyone reads its colours: the textures of a shaded frame, then the emission of a disk —
+// either may be null.  d_g: the frequency ratios of the pixel-centre rays (pass 1 of trace_aa_on, rtgr_aa_host.hip), or null.
 template <class R>
 struct AfterTrace {
     const ShadeDesc<R>* shade = nullptr;
     const DevEmission<R>* emit = nullptr;
     R* d_g = nullptr;
+};
+// … and the run of pixels a trace just wrote that it is applied to (after_trace, rtgr_frame_host.hip), every member by name
+template <class R>
+struct TracedPixels {
+    R* rgb = nullptr;                     // the run's colours: three planes …
+    uint64_t plane_stride = 0;            // … this far apart
+    R* g = nullptr;                       // the frequency ratio per pixel, or null
+    const uint32_t* hit32 = nullptr;      // what the trace delivered of the run
+    const uint8_t* status = nullptr;      // (read by the shading kernel only)
+    const R* state_end = nullptr;
+    const R* state0 = nullptr;            // the rays' start states when they were caller-supplied; null: pixel idx of the ni x nj canvas of cam
+    const ObsFrame<R>* obs = nullptr;     // the observer whose e_0 is u_obs; null: the static observer at the ray's start
+    uint64_t n = 0, ni = 0, nj = 0;
+    const DevScene<R>* sc = nullptr;      // what the emission kernel reads of the scene and the camera (null where nothing emits;
+    const DevCamera<R>* cam = nullptr;    // cam also where state0 is given)
 };
 
 }  // namespace rtgr

@@ -6,13 +6,15 @@
 //   rtgr_sharded.hip        one call over every device of a context: cyclic rows, peer copies to device 0
 //   rtgr_hooks.hip          make_canvas and the parity hooks (rtgr_eval_*), image quantisation
 //   rtgr_units.hip          run-time compiled units: build, audit, load-time probe, load, scene check
+//   rtgr_frame_host.hip     what the frame calls below share: a stream's frame scratch, the post-trace stage (textures, then the emitting disk),
+//                           the camera frame of rtgr_trace_shaded_* / rtgr_trace_emission_*, the staged host-pointer call, the small checks
 //   rtgr_aa_host.hip        adaptive anti-aliasing: the plain frame, the edge rule, a sparse second trace (kernels: rtgr_aa.hip)
-//   rtgr_texture_host.hip   image textures: load / unload, the shaded trace (a plain or anti-aliased trace + the shading kernel), the
-//                           sampler hook (kernels: rtgr_shade.hip)
-//   rtgr_emission_host.hip  disk emission: the emitted trace (a plain, shaded and / or anti-aliased trace + the emission kernel), the
-//                           pointwise hook (kernels: rtgr_emit.hip)
+//   rtgr_texture_host.hip   image textures: load / unload, the binds of a call into the records the shading kernel reads, the entry points of the
+//                           shaded trace, the sampler hook (kernels: rtgr_shade.hip)
+//   rtgr_emission_host.hip  disk emission: the checks of an rtgr_disk_emission, the entry points of the emitted trace, the pointwise hook
+//                           (kernels: rtgr_emit.hip)
 //   rtgr_observer_host.hip  the observer camera: the checks of an rtgr_observer, the observer trace (the frame and ray kernels + a plain trace of
-//                           their states, batch by batch, + the shading / emission kernels), the canvas and frame hooks (kernels: rtgr_observer.hip)
+//                           their states, batch by batch, + the post-trace stage), the canvas and frame hooks (kernels: rtgr_observer.hip)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -24,6 +26,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <limits>
 #include <thread>
 
@@ -142,23 +145,84 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
                  rtgr_counters* d_counters, hipStream_t st, uint64_t jstride = 1, uint64_t nrows_strided = 0,
                  const Window* win = nullptr);
 
-// ---- adaptive anti-aliasing on one device (rtgr_aa_host.hip), optionally of a SHADED frame (rtgr_texture_host.hip) ---------------
-// grow-only scratch of a stream, retired like its workspace (D.mu held; never called during capture: the entry points refuse first)
-int aa_need(StreamState& ss, void*& p, size_t& have, size_t bytes);
+// ---- what the frame calls share (rtgr_frame_host.hip) ------------------------------------------------------------------------------
+// The frame scratch of a stream (StreamState::frame): what a frame call keeps there, each block 256-aligned and an absent one no bytes.
+// Pure arithmetic: the head — rtgr_counters (64 bytes), then the refined count of an anti-aliased frame — always; `obs`: the observer's
+// frame record; `list`: the index list of the refined pixels; then the end states / hit map / status bytes to borrow, n rays of each.
+constexpr size_t FRAME_HEAD = 256, FRAME_OBS = 512;
+struct FrameNeeds { bool state_end = false, hit32 = false, status = false, list = false, obs = false; };
+struct FrameLayout { size_t obs, list, state_end, hit32, status, bytes; };
+static_assert(sizeof(rtgr_counters) + sizeof(unsigned long long) <= FRAME_HEAD && sizeof(ObsFrame<double>) <= FRAME_OBS, "the head holds them");
+inline FrameLayout frame_layout(uint64_t n, size_t scalar, const FrameNeeds& need) {
+    FrameLayout at;
+    at.obs = FRAME_HEAD;
+    at.list = at.obs + (need.obs ? FRAME_OBS : 0);
+    at.state_end = at.list + (need.list ? align256((size_t)n * sizeof(uint64_t)) : 0);
+    at.hit32 = at.state_end + (need.state_end ? align256((size_t)n * 8 * scalar) : 0);
+    at.status = at.hit32 + (need.hit32 ? align256((size_t)n * sizeof(uint32_t)) : 0);
+    at.bytes = at.status + (need.status ? align256((size_t)n) : 0);
+    return at;
+}
+// the words of an entry point in its refusals: its name ("rtgr_trace_shaded_*"), what it calls its scratch ("shading"), and whether
+// the refusal to grow it says what to do instead
+struct EntryWords { const char* entry; const char* scratch; bool advise; };
+// A frame call's share of the stream's scratch, as frame_scratch leaves it: `o1` is the caller's rtgr_ray_outputs with the members the
+// call must borrow pointed into the scratch; d_ctr the device counters when the caller counts (the head is zeroed on the stream), else null.
+struct FrameScratch {
+    StreamState* ss = nullptr;   // (entries of the map stay where they are: it outlives the lock)
+    char* base = nullptr;        // null: the call needs nothing of the scratch
+    FrameLayout at;
+    rtgr_ray_outputs o1;
+    rtgr_counters* d_ctr = nullptr;
+};
+// grow-only scratch of a stream, retired like its workspace (D.mu held; never called during capture: frame_scratch refuses first)
+int scratch_need(StreamState& ss, void*& p, size_t& have, size_t bytes);
+// whether st is being captured; a call that counts (ctr) synchronises at its end and is refused then, by a message with "ctr"
+int capture_check(hipStream_t st, const EntryWords& who, const rtgr_counters* ctr, bool* capturing);
+// (D.mu held)  The stream's state, its frame scratch grown to what `need` asks for n rays of `scalar` bytes and its batch scratch to
+// batch_bytes — refused while the stream is captured — and the head zeroed when someone counts in it (ctr, or the refined count)
+int frame_scratch(DeviceCtx& D, hipStream_t st, bool capturing, const EntryWords& who, uint64_t n, size_t scalar, const FrameNeeds& need,
+                  size_t batch_bytes, const rtgr_ray_outputs* out, const rtgr_counters* ctr, FrameScratch& fs);
+// the end of a call that counts: the counters to the caller, behind a synchronisation
+int counters_back(const FrameScratch& fs, rtgr_counters* ctr, hipStream_t st);
+// THE post-trace stage: `after` applied to the pixels a trace just wrote on st — the shading kernel if there are binds, then the emission
+// kernel if a disk emits; takes D.mu, each launch timed in slot 0
+template <class R> int after_trace(DeviceCtx& D, hipStream_t st, const AfterTrace<R>& after, const TracedPixels<R>& px);
+// the small checks: the canvas of `what` ("a shaded frame"), the scene's metric not the user's own (`what`: "disk emission in", `why`: "its
+// kernels live"), and the scene as a kernel that needs a stationary metric reads it (D.mu held; a 4-D grid is refused with `refusal`)
+int canvas_check(uint64_t ni, uint64_t nj, const char* what);
+int builtin_metric_check(const rtgr_scene* scene, const char* what, const char* why);
+template <class R> int stationary_scene(DeviceCtx& D, const rtgr_scene* scene, DevScene<R>& sc, hipStream_t st, const char* refusal);
+constexpr const char* EMISSION_NEEDS_STATIONARY =
+    "disk emission in a time-dependent (4-D) grid metric is not supported: the emitter's orbit needs a stationary metric";
+// The frame of a camera with textures and / or an emitting disk (rtgr_trace_shaded_* / rtgr_trace_emission_*) on device D, stream st; d_rgb,
+// d_g, the members of `out` and d_refined are pointers of that device.  emit == NULL: a shaded frame, which needs `shade`; aa: the
+// anti-aliased frame of rtgr_aa_host.hip with both as its AfterTrace
+template <class R>
+int trace_camera_frame_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
+                          const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, R* d_g,
+                          uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, hipStream_t st, const EntryWords& who);
+// A host-pointer frame call: `call` — a device-side frame call, given device 0 of the context, its staging's compute stream and device
+// arrays for rgb, `out` and (where not null) refined and g — and all of them copied out.  n: the pixels of the frame
+template <class R>
+using StagedCall = std::function<int(DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs* d_out, uint8_t* d_refined, R* d_g, hipStream_t st)>;
+template <class R>
+int staged_frame(rtgr_context* c, uint64_t n, R* rgb, const rtgr_ray_outputs* out, uint8_t* refined, R* g, const StagedCall<R>& call);
+
+// ---- adaptive anti-aliasing on one device (rtgr_aa_host.hip) ------------------------------------------------------------------------
 // the call on device D, stream st; d_rgb, the members of `out` and d_refined are pointers of that device.  after == nullptr: the plain
 // anti-aliased frame; otherwise both passes are shaded with its (resolved) binds and / or emitted with its disk (AfterTrace, rtgr_host.hpp)
 template <class R>
 int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
                 const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats,
                 hipStream_t st, const AfterTrace<R>* after);
-// image textures (rtgr_texture_host.hip), shared with the emitted trace: the caller's binds into the records the shading kernel reads, for
-// device D and scalar type R (takes D.mu), and the checks of a shaded frame's arguments
+// image textures (rtgr_texture_host.hip): the caller's binds into the records the shading kernel reads, for device D and scalar type R
+// (takes D.mu), and the checks of a camera frame's arguments
 template <class R> int shade_resolve(DeviceCtx& D, const rtgr_scene* scene, const rtgr_shade* shade, ShadeDesc<R>& sd);
 int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refined, const rtgr_aa_stats* stats, uint64_t ni, uint64_t nj);
-// disk emission (rtgr_emission_host.hip), shared with the observer trace: the caller's parameters into the record the kernels read
-// (`shade`, may be null: the binds of the same call), and the scene as the emission kernel reads it (D.mu held; refuses a 4-D grid)
+// disk emission (rtgr_emission_host.hip): the caller's parameters into the record the kernels read (`shade`, may be null: the binds of
+// the same call)
 template <class R> int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, const rtgr_disk_emission* emit, DevEmission<R>& em);
-template <class R> int emission_scene(DeviceCtx& D, const rtgr_scene* scene, DevScene<R>& sc, hipStream_t st);
 // the observer camera (rtgr_observer_host.hip): the checks of an rtgr_observer against its scene, and the record the frame kernel reads
 template <class R> int observer_resolve(const rtgr_scene* scene, const rtgr_observer* obs, DevObserver<R>& ob);
 

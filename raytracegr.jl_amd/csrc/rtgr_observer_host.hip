@@ -1,15 +1,17 @@
 // rtgr_observer_host.hip — the observer camera (include/rtgr.h "observer camera"): the checks of an rtgr_observer, the observer trace —
 // the frame kernel, then batch by batch the ray kernel, a plain trace_device of those states into a window of the caller's planes, the
-// shading kernel (if textures are bound) and the emission kernel (if a disk emits) — and the hooks.  Host code only: the kernels are
-// rtgr_observer.hip's, rtgr_shade.hip's and rtgr_emit.hip's, the frame's model rtgr_observer.hpp's.
+// post-trace stage of rtgr_frame_host.hip (the shading kernel if textures are bound, the emission kernel if a disk emits) — and the hooks.
+// Host code only: the kernels are rtgr_observer.hip's, rtgr_shade.hip's and rtgr_emit.hip's, the frame's model rtgr_observer.hpp's.
 #include "rtgr_internal.hpp"
 
 namespace rtgr {
 
 constexpr uint64_t OBS_DEFAULT_BATCH = 1ull << 22;   // rays per batch (rtgr_observer.max_batch_rays = 0), as rtgr_aa's
-constexpr size_t OBS_HEAD = 256;                     // head of the frame scratch: rtgr_counters (64 bytes) …
-constexpr size_t OBS_FRAME = 512;                    // … then the frame record (ObsFrame<double>: 320 bytes)
-static_assert(sizeof(ObsFrame<double>) <= OBS_FRAME && sizeof(rtgr_counters) <= OBS_HEAD, "the head of the observer scratch holds both");
+constexpr EntryWords OBSERVER_WORDS = {"rtgr_trace_observer_*", "observer", true};
+constexpr EntryWords OBSERVER_CANVAS_WORDS = {"rtgr_make_observer_canvas_device_*", "observer", false};
+constexpr const char* OBSERVER_CANVAS = "an observer frame";
+// (its metric must not depend on time through a 4-D grid: stationary_scene)
+constexpr const char* OBSERVER_NEEDS_STATIONARY = "an observer camera in a time-dependent (4-D) grid metric is not supported";
 constexpr double OBS_PI = 3.14159265358979323846;
 
 static bool finite4(const double v[4]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && std::isfinite(v[3]); }
@@ -19,9 +21,8 @@ template <class R>
 int observer_resolve(const rtgr_scene* scene, const rtgr_observer* obs, DevObserver<R>& ob) {
     if (!scene) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
     if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
-    if ((scene->metric & ~(uint32_t)RTGR_METRIC_GENERIC) == RTGR_USER)
-        return fail(RTGR_ERR_BAD_ARG, "an observer camera in a scene whose METRIC is RTGR_USER is not supported (its kernels live in the run-time unit); "
-                                      "user objects under a built-in metric are");
+    int rc;
+    if ((rc = builtin_metric_check(scene, "an observer camera in", "its kernels live"))) return rc;
     if (obs->kind != RTGR_OBS_STATIC && obs->kind != RTGR_OBS_VELOCITY && obs->kind != RTGR_OBS_CIRCULAR)
         return fail(RTGR_ERR_BAD_ARG, "unknown rtgr_observer.kind " + std::to_string(obs->kind) + " (RTGR_OBS_STATIC = 0, RTGR_OBS_VELOCITY = 1, RTGR_OBS_CIRCULAR = 2)");
     if (obs->projection != RTGR_PROJ_PERSPECTIVE && obs->projection != RTGR_PROJ_EQUIRECT)
@@ -56,12 +57,6 @@ int observer_resolve(const rtgr_scene* scene, const rtgr_observer* obs, DevObser
 }
 RTGR_INSTANTIATE_F64_F32(observer_resolve);
 
-static int observer_canvas_check(uint64_t ni, uint64_t nj) {
-    if (ni == 0 || nj == 0 || ni > (1ull << 32) || nj > (1ull << 32) || ni * nj > (1ull << 34))
-        return fail(RTGR_ERR_BAD_ARG, "bad canvas: need ni, nj > 0 and at most 2^34 pixels for an observer frame");
-    return RTGR_OK;
-}
-
 // what every entry of the observer trace refuses before it touches a device
 static int observer_trace_check(const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_disk_emission* emit,
                                 const void* rgb, const rtgr_ray_outputs* out, const void* g) {
@@ -69,22 +64,11 @@ static int observer_trace_check(const rtgr_scene* scene, const rtgr_observer* ob
     if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
     if (!rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     int rc;
-    if ((rc = observer_canvas_check(ni, nj))) return rc;
+    if ((rc = canvas_check(ni, nj, OBSERVER_CANVAS))) return rc;
     if (out && out->redshift)
         return fail(RTGR_ERR_BAD_ARG, "rtgr_ray_outputs.redshift is defined against the static observer of make_canvas: an observer trace does not deliver it "
                                       "(the frequency ratio against THIS observer and an orbiting disk is d_g, with emit)");
     if (g && !emit) return fail(RTGR_ERR_BAD_ARG, "g is the frequency ratio of an emitting disk: it must be NULL when emit is NULL");
-    return RTGR_OK;
-}
-
-// the scene as the observer's kernels read it (D.mu held): its metric, which must not depend on time through a 4-D grid
-template <class R>
-static int observer_scene(DeviceCtx& D, const rtgr_scene* scene, DevScene<R>& sc, hipStream_t st) {
-    const UserModule* user = nullptr;
-    int rc;
-    if ((rc = convert_scene<R>(D, scene, sc, &user, st))) return rc;
-    if (sampled_on(sc.metric, 4))
-        return fail(RTGR_ERR_BAD_ARG, "an observer camera in a time-dependent (4-D) grid metric is not supported");
     return RTGR_OK;
 }
 
@@ -97,57 +81,47 @@ static int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_s
     if ((rc = observer_trace_check(scene, obs, ni, nj, emit, d_rgb, out, d_g))) return rc;
     DevObserver<R> ob;
     if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
-    EmitArgs<R> E;
-    std::memset(&E, 0, sizeof E);
-    if (emit && (rc = emission_resolve<R>(scene, shade, emit, E.em))) return rc;
-    ShadeArgs<R> A;
-    if (shade && (rc = shade_resolve<R>(D, scene, shade, A.desc))) return rc;
-    const bool shading = shade && A.desc.nbind != 0, post = shading || emit;
+    DevEmission<R> em;
+    if (emit && (rc = emission_resolve<R>(scene, shade, emit, em))) return rc;
+    ShadeDesc<R> sd;
+    sd.nbind = 0;
+    if (shade && (rc = shade_resolve<R>(D, scene, shade, sd))) return rc;
+    AfterTrace<R> after;
+    after.shade = sd.nbind ? &sd : nullptr;
+    after.emit = emit ? &em : nullptr;
+    const bool post = after.shade || after.emit;
     DeviceGuard guard(D.dev);
     if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    if (capturing && ctr)
-        return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_observer_*: the stream is being captured and `ctr` asks for a synchronisation at the end of the call "
-                                      "(which cannot be captured): pass ctr = NULL");
+    bool capturing;
+    if ((rc = capture_check(st, OBSERVER_WORDS, ctr, &capturing))) return rc;
     const uint64_t n = ni * nj;
     const uint64_t budget = obs->max_batch_rays ? obs->max_batch_rays : OBS_DEFAULT_BATCH;
     const uint64_t rows = budget / ni ? (budget / ni < nj ? budget / ni : nj) : 1;   // rows per batch
     if (rows < nj && (tl_knobs_override ? tl_knobs_override->tile : D.knobs.tile))
         return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_observer_*: option tile = 1 writes whole frames only and this observer frame takes more than one batch "
                                       "(rtgr_observer.max_batch_rays): raise max_batch_rays to the frame's rays, or use the persistent pipeline (tile = 0)");
-    const bool want_state = post && !(out && out->state_end), want_hit32 = post && !(out && out->hit32), want_status = shading && !(out && out->status);
-    // ---- frame scratch: [counters] [frame record] [end states] [hit32] [status]; batch scratch: the states of `rows` rows -----------------
-    const size_t off_state = OBS_HEAD + OBS_FRAME, off_hit = off_state + (want_state ? align256(n * 8 * sizeof(R)) : 0),
-                 off_status = off_hit + (want_hit32 ? align256(n * sizeof(uint32_t)) : 0), frame_bytes = off_status + (want_status ? align256(n) : 0);
-    const size_t batch_bytes = align256((size_t)rows * ni * 8 * sizeof(R));
+    // ---- frame scratch: the counters, the frame record, and what the shading and emission kernels read and the caller did not ask for;
+    // batch scratch: the states of `rows` rows --------------------------------------------------------------------------------------------
+    FrameNeeds need;
+    need.obs = true;
+    need.state_end = post && !(out && out->state_end);
+    need.hit32 = post && !(out && out->hit32);
+    need.status = after.shade && !(out && out->status);
     DevScene<R> sc;
-    StreamState* ss = nullptr;
+    FrameScratch fs;
     {
         std::lock_guard<std::mutex> lk(D.mu);
-        if ((rc = emit ? emission_scene<R>(D, scene, sc, st) : observer_scene<R>(D, scene, sc, st))) return rc;
-        if ((rc = stream_state(D, st, &ss))) return rc;   // (entries of the map stay where they are: `ss` outlives the lock)
-        if (capturing && (frame_bytes > ss->obs_frame_bytes || batch_bytes > ss->obs_batch_bytes))
-            return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_observer_*: the stream's observer scratch must grow but the stream is being captured: make a call of "
-                                          "this size on the stream before hipStreamBeginCapture");
-        if ((rc = aa_need(*ss, ss->obs_frame, ss->obs_frame_bytes, frame_bytes))) return rc;
-        if ((rc = aa_need(*ss, ss->obs_batch, ss->obs_batch_bytes, batch_bytes))) return rc;
+        if ((rc = stationary_scene<R>(D, scene, sc, st, emit ? EMISSION_NEEDS_STATIONARY : OBSERVER_NEEDS_STATIONARY))) return rc;
+        if ((rc = frame_scratch(D, st, capturing, OBSERVER_WORDS, n, sizeof(R), need, align256((size_t)rows * ni * 8 * sizeof(R)), out, ctr, fs))) return rc;
     }
-    char* frame = (char*)ss->obs_frame;
-    R* d_states = (R*)ss->obs_batch;
-    ObsFrame<R>* d_frame = (ObsFrame<R>*)(frame + OBS_HEAD);
-    rtgr_counters* d_ctr = ctr ? (rtgr_counters*)frame : nullptr;
-    if (ctr) HIP_TRY(hipMemsetAsync(frame, 0, OBS_HEAD, st));
+    R* d_states = (R*)fs.ss->batch;
+    ObsFrame<R>* d_frame = (ObsFrame<R>*)(fs.base + fs.at.obs);
+    const rtgr_ray_outputs& o1 = fs.o1;
     {
         std::lock_guard<std::mutex> lk(D.mu);
         KernelTimer timer(D, st, 0);
         if ((rc = observer_frame_launch<R>(sc, ob, d_frame, st))) return rc;
     }
-    rtgr_ray_outputs o1;
-    if (out) o1 = *out; else std::memset(&o1, 0, sizeof o1);
-    if (want_state) o1.state_end = frame + off_state;
-    if (want_hit32) o1.hit32 = (uint32_t*)(frame + off_hit);
-    if (want_status) o1.status = (uint8_t*)(frame + off_status);
     // ---- batch by batch: whole rows [ja, jb) --------------------------------------------------------------------------------------
     for (uint64_t ja = 0; ja < nj; ja += rows) {
         const uint64_t jb = ja + rows < nj ? ja + rows : nj, first = ja * ni, m = (jb - ja) * ni;
@@ -158,29 +132,18 @@ static int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_s
         }
         Window win;
         win.plane_stride = n; win.out_offset = first;
-        if ((rc = trace_device<R>(D, scene, opt, d_states, nullptr, ni, nj, ja, jb, d_rgb, &o1, d_ctr, st, 1, 0, rows < nj ? &win : nullptr))) return rc;
-        if (shading) {   // the batch as a window of the frame: planes n apart
-            std::lock_guard<std::mutex> lk(D.mu);
-            KernelTimer timer(D, st, 0);
-            A.rgb = d_rgb + first; A.hit32 = o1.hit32 + first; A.status = o1.status + first; A.state_end = (const R*)o1.state_end + first * 8;
-            A.n = m; A.plane_stride = n;
-            if ((rc = shade_launch<R>(A, st))) return rc;
-        }
-        if (emit) {      // … each pixel emitted from its own start state, against this observer's e_0
-            std::lock_guard<std::mutex> lk(D.mu);
-            KernelTimer timer(D, st, 0);
-            E.sc = sc;
-            E.rgb = d_rgb + first; E.g = d_g ? d_g + first : nullptr; E.omega = nullptr; E.u_emit = nullptr; E.hit32 = o1.hit32 + first;
-            E.state_end = (const R*)o1.state_end + first * 8; E.state0 = d_states; E.obs = d_frame;
-            E.n = m; E.plane_stride = n; E.pixel_stride = 1; E.ni = ni; E.nj = nj;
-            if ((rc = emit_launch<R>(E, st))) return rc;
+        if ((rc = trace_device<R>(D, scene, opt, d_states, nullptr, ni, nj, ja, jb, d_rgb, &o1, fs.d_ctr, st, 1, 0, rows < nj ? &win : nullptr))) return rc;
+        if (post) {   // the batch as a window of the frame: planes n apart; each pixel emitted from its own start state, against this observer's e_0
+            TracedPixels<R> px;
+            px.rgb = d_rgb + first; px.plane_stride = n; px.g = d_g ? d_g + first : nullptr;
+            px.hit32 = o1.hit32 + first; px.status = o1.status ? o1.status + first : nullptr; px.state_end = (const R*)o1.state_end + first * 8;
+            px.state0 = d_states; px.obs = d_frame;
+            px.n = m; px.ni = ni; px.nj = nj;
+            px.sc = &sc;
+            if ((rc = after_trace<R>(D, st, after, px))) return rc;
         }
     }
-    if (ctr) {
-        HIP_TRY(hipMemcpyAsync(ctr, d_ctr, sizeof *ctr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return RTGR_OK;
+    return counters_back(fs, ctr, st);
 }
 
 template <class R>
@@ -204,28 +167,9 @@ int api::trace_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_s
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
     if ((rc = observer_trace_check(scene, obs, ni, nj, emit, rgb, out, g))) return rc;
-    DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-    Staging* S = nullptr;
-    { std::lock_guard<std::mutex> lk(D.mu); if ((rc = staging_of(D, &S))) return rc; }
-    std::lock_guard<std::mutex> call_lock(S->mu);
-    HIP_TRY(hipStreamSynchronize(S->s_comp));   // (a previous call that failed half-way; the stream is idle otherwise)
-    const uint64_t n = ni * nj;
-    std::vector<RayArray> arrs = ray_arrays(rgb, out, sizeof(R));
-    const size_t off_g = ray_arrays_layout(arrs, n);
-    if ((rc = S->d_out.need(off_g + (g ? align256(n * sizeof(R)) : 0)))) return rc;
-    char* base = (char*)S->d_out.p;
-    const rtgr_ray_outputs o = ray_outputs_at(base, arrs, out);
-    R* d_g = g ? (R*)(base + off_g) : nullptr;
-    if ((rc = trace_observer_on<R>(D, scene, opt, obs, ni, nj, shade, emit, (R*)(base + arrs[0].off), out ? &o : nullptr, d_g, ctr, S->s_comp))) {
-        (void)hipStreamSynchronize(S->s_comp);
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(S->s_comp));
-    for (const RayArray& a : arrs) HIP_TRY(hipMemcpy(a.ptr, base + a.off, (size_t)n * a.elem * a.planes, hipMemcpyDeviceToHost));
-    if (g) HIP_TRY(hipMemcpy(g, d_g, (size_t)n * sizeof(R), hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    return staged_frame<R>(c, ni * nj, rgb, out, nullptr, g, [&](DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs* d_out, uint8_t*, R* d_g, hipStream_t st) {
+        return trace_observer_on<R>(D, scene, opt, obs, ni, nj, shade, emit, d_rgb, d_out, d_g, ctr, st);
+    });
 }
 
 // the states of rows [j0, j1) on device D, stream st: the frame kernel into the stream's scratch, the ray kernel into the caller's array
@@ -235,24 +179,23 @@ int api::make_observer_canvas_device(rtgr_context* ctx, const rtgr_scene* scene,
     if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
     if (!d_state0) return fail(RTGR_ERR_BAD_ARG, "NULL argument");
     RESOLVE_DEVICE(d_state0);
-    if ((rc = observer_canvas_check(ni, nj))) return rc;
+    if ((rc = canvas_check(ni, nj, OBSERVER_CANVAS))) return rc;
     if (j1 <= j0 || j1 > nj) return fail(RTGR_ERR_BAD_ARG, "bad canvas range");
     DevObserver<R> ob;
     if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
     hipStream_t st = (hipStream_t)stream;
     DeviceGuard guard(D->dev);
     if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    bool capturing;
+    if ((rc = capture_check(st, OBSERVER_CANVAS_WORDS, nullptr, &capturing))) return rc;
     std::lock_guard<std::mutex> lk(D->mu);
     DevScene<R> sc;
-    if ((rc = observer_scene<R>(*D, scene, sc, st))) return rc;
-    StreamState* ss = nullptr;
-    if ((rc = stream_state(*D, st, &ss))) return rc;
-    if (capturing && OBS_HEAD + OBS_FRAME > ss->obs_frame_bytes)
-        return fail(RTGR_ERR_BAD_ARG, "rtgr_make_observer_canvas_device_*: the stream's observer scratch must grow but the stream is being captured");
-    if ((rc = aa_need(*ss, ss->obs_frame, ss->obs_frame_bytes, OBS_HEAD + OBS_FRAME))) return rc;
-    ObsFrame<R>* d_frame = (ObsFrame<R>*)((char*)ss->obs_frame + OBS_HEAD);
+    if ((rc = stationary_scene<R>(*D, scene, sc, st, OBSERVER_NEEDS_STATIONARY))) return rc;
+    FrameNeeds need;
+    need.obs = true;
+    FrameScratch fs;
+    if ((rc = frame_scratch(*D, st, capturing, OBSERVER_CANVAS_WORDS, 0, sizeof(R), need, 0, nullptr, nullptr, fs))) return rc;
+    ObsFrame<R>* d_frame = (ObsFrame<R>*)(fs.base + fs.at.obs);
     if ((rc = observer_frame_launch<R>(sc, ob, d_frame, st))) return rc;
     return observer_rays_launch<R>(d_frame, ni, nj, j0 * ni, (j1 - j0) * ni, d_state0, st);
 }
@@ -264,7 +207,7 @@ int api::make_observer_canvas(rtgr_context* ctx, const rtgr_scene* scene, const 
     if (rc) return rc;
     if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
     if (!state0) return fail(RTGR_ERR_BAD_ARG, "NULL argument");
-    if ((rc = observer_canvas_check(ni, nj))) return rc;
+    if ((rc = canvas_check(ni, nj, OBSERVER_CANVAS))) return rc;
     if (j1 <= j0 || j1 > nj) return fail(RTGR_ERR_BAD_ARG, "bad canvas range");
     const uint64_t n = ni * (j1 - j0);
     DeviceGuard guard(c->devs[0]->dev);
@@ -289,7 +232,7 @@ int api::eval_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_ob
     if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
     std::lock_guard<std::mutex> lk(D.mu);
     DevScene<R> sc;
-    if ((rc = observer_scene<R>(D, scene, sc, nullptr))) return rc;
+    if ((rc = stationary_scene<R>(D, scene, sc, nullptr, OBSERVER_NEEDS_STATIONARY))) return rc;
     DevBuf b;
     if ((rc = b.alloc(sizeof(ObsFrame<R>)))) return rc;
     if ((rc = observer_frame_launch<R>(sc, ob, (ObsFrame<R>*)b.p, nullptr))) return rc;

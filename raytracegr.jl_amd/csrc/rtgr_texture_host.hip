@@ -1,7 +1,7 @@
 // rtgr_texture_host.hip — image textures (include/rtgr.h "image textures"): load (checks, upload to every device of the context in Float64
-// and Float32) and unload (retire: a hipGraph captured earlier may still replay the texels; rtgr_trim frees them), the shaded trace —
-// a plain trace_device, or the anti-aliased one of rtgr_aa_host.hip, with the shading kernel behind it — and the sampler hook.  Host
-// code only: the kernels are rtgr_shade.hip's, the mapping and the sampler rtgr_texture.hpp's.
+// and Float32) and unload (retire: a hipGraph captured earlier may still replay the texels; rtgr_trim frees them), the binds of a call
+// into the records the shading kernel reads, the entry points of the shaded trace — the camera frame of rtgr_frame_host.hip without an
+// emitting disk — and the sampler hook.  Host code only: the kernels are rtgr_shade.hip's, the mapping and the sampler rtgr_texture.hpp's.
 #include "rtgr_internal.hpp"
 
 namespace rtgr {
@@ -10,7 +10,7 @@ namespace rtgr {
 // unit or grid of the context.
 static std::atomic<uint64_t> g_next_texture{1};
 constexpr uint64_t TEXTURE_ID_TAG = 0x7000000000000000ull, TEXTURE_ID_MASK = 0xF000000000000000ull;
-constexpr size_t SHADE_HEAD = 256;   // head of the frame scratch: rtgr_counters (64 bytes)
+constexpr EntryWords SHADED_WORDS = {"rtgr_trace_shaded_*", "shading", true};
 
 int api::texture_load(rtgr_context* ctx, const rtgr_texture_desc* desc, const double* texels, uint64_t* id_out) {
     rtgr_context* c = nullptr;
@@ -149,72 +149,7 @@ int shade_resolve(DeviceCtx& D, const rtgr_scene* scene, const rtgr_shade* shade
 int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refined, const rtgr_aa_stats* stats, uint64_t ni, uint64_t nj) {
     if (!cam) return fail(RTGR_ERR_BAD_ARG, "a shaded frame needs a camera (cam is NULL)");
     if (!aa && (refined || stats)) return fail(RTGR_ERR_BAD_ARG, "refined and stats belong to anti-aliasing: they must be NULL when aa is NULL");
-    if (ni == 0 || nj == 0 || ni > (1ull << 32) || nj > (1ull << 32) || ni * nj > (1ull << 34))
-        return fail(RTGR_ERR_BAD_ARG, "bad canvas: need ni, nj > 0 and at most 2^34 pixels for a shaded frame");
-    return RTGR_OK;
-}
-
-// the call on device D, stream st; d_rgb, the members of `out` and d_refined are pointers of that device
-template <class R>
-static int trace_shaded_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
-                           const rtgr_shade* shade, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined, rtgr_counters* ctr,
-                           rtgr_aa_stats* stats, hipStream_t st) {
-    int rc;
-    if ((rc = shaded_check(cam, aa, d_refined, stats, ni, nj))) return rc;
-    if ((rc = check_redshift_outputs(out))) return rc;
-    ShadeArgs<R> A;
-    if ((rc = shade_resolve<R>(D, scene, shade, A.desc))) return rc;
-    if (aa) {
-        AfterTrace<R> after;
-        after.shade = &A.desc;
-        return trace_aa_on<R>(D, scene, opt, cam, ni, nj, aa, d_rgb, out, d_refined, ctr, stats, st, &after);
-    }
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    if (capturing && ctr)
-        return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_shaded_*: the stream is being captured and `ctr` asks for a synchronisation at the end of the call "
-                                      "(which cannot be captured): pass ctr = NULL");
-    const uint64_t n = ni * nj;
-    const bool shading = A.desc.nbind != 0;
-    const bool want_state = shading && !(out && out->state_end), want_hit32 = shading && !(out && out->hit32),
-               want_status = shading && !(out && out->status);
-    // ---- frame scratch: [counters] [end states] [hit32] [status] -------------------------------------------------------------------
-    const size_t off_state = SHADE_HEAD, off_hit = off_state + (want_state ? align256(n * 8 * sizeof(R)) : 0),
-                 off_status = off_hit + (want_hit32 ? align256(n * sizeof(uint32_t)) : 0), frame_bytes = off_status + (want_status ? align256(n) : 0);
-    char* frame = nullptr;
-    if (ctr || frame_bytes > SHADE_HEAD) {
-        std::lock_guard<std::mutex> lk(D.mu);
-        StreamState* ss = nullptr;
-        if ((rc = stream_state(D, st, &ss))) return rc;
-        if (capturing && frame_bytes > ss->shade_frame_bytes)
-            return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_shaded_*: the stream's shading scratch must grow but the stream is being captured: make a call of "
-                                          "this size on the stream before hipStreamBeginCapture");
-        if ((rc = aa_need(*ss, ss->shade_frame, ss->shade_frame_bytes, frame_bytes))) return rc;
-        frame = (char*)ss->shade_frame;
-    }
-    rtgr_counters* d_ctr = ctr ? (rtgr_counters*)frame : nullptr;
-    if (ctr) HIP_TRY(hipMemsetAsync(frame, 0, SHADE_HEAD, st));
-    // ---- the plain frame, with what the shading kernel reads of it ------------------------------------------------------------------
-    rtgr_ray_outputs o1;
-    if (out) o1 = *out; else std::memset(&o1, 0, sizeof o1);
-    if (want_state) o1.state_end = frame + off_state;
-    if (want_hit32) o1.hit32 = (uint32_t*)(frame + off_hit);
-    if (want_status) o1.status = (uint8_t*)(frame + off_status);
-    if ((rc = trace_device<R>(D, scene, opt, nullptr, cam, ni, nj, 0, nj, d_rgb, (out || shading) ? &o1 : nullptr, d_ctr, st))) return rc;
-    if (shading) {
-        std::lock_guard<std::mutex> lk(D.mu);
-        KernelTimer timer(D, st, 0);
-        A.rgb = d_rgb; A.hit32 = o1.hit32; A.status = o1.status; A.state_end = (const R*)o1.state_end;
-        A.n = n; A.plane_stride = n;
-        if ((rc = shade_launch<R>(A, st))) return rc;
-    }
-    if (ctr) {
-        HIP_TRY(hipMemcpyAsync(ctr, d_ctr, sizeof *ctr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return RTGR_OK;
+    return canvas_check(ni, nj, "a shaded frame");
 }
 
 template <class R>
@@ -228,7 +163,7 @@ int api::trace_shaded_device(rtgr_context* ctx, const rtgr_scene* scene, const r
     if ((rc = shaded_check(cam, aa, d_refined, stats, ni, nj))) return rc;
     DeviceCtx* D = nullptr;
     if ((rc = device_of(c, d_rgb, &D))) return rc;
-    return trace_shaded_on<R>(*D, scene, opt, cam, ni, nj, shade, aa, d_rgb, out, d_refined, ctr, stats, (hipStream_t)stream);
+    return trace_camera_frame_on<R>(*D, scene, opt, cam, ni, nj, shade, nullptr, aa, d_rgb, out, nullptr, d_refined, ctr, stats, (hipStream_t)stream, SHADED_WORDS);
 }
 
 // host pointers: the same call on device 0 of the context, on its staging's compute stream, and the frame copied out
@@ -242,28 +177,9 @@ int api::trace_shaded(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_sol
     if (!rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     if ((rc = shaded_check(cam, aa, refined, stats, ni, nj))) return rc;
     if ((rc = check_redshift_outputs(out))) return rc;
-    DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-    Staging* S = nullptr;
-    { std::lock_guard<std::mutex> lk(D.mu); if ((rc = staging_of(D, &S))) return rc; }
-    std::lock_guard<std::mutex> call_lock(S->mu);
-    HIP_TRY(hipStreamSynchronize(S->s_comp));   // (a previous call that failed half-way; the stream is idle otherwise)
-    const uint64_t n = ni * nj;
-    std::vector<RayArray> arrs = ray_arrays(rgb, out, sizeof(R));
-    const size_t off_refined = ray_arrays_layout(arrs, n);
-    if ((rc = S->d_out.need(off_refined + (refined ? align256(n) : 0)))) return rc;
-    char* base = (char*)S->d_out.p;
-    const rtgr_ray_outputs o = ray_outputs_at(base, arrs, out);
-    uint8_t* d_refined = refined ? (uint8_t*)(base + off_refined) : nullptr;
-    if ((rc = trace_shaded_on<R>(D, scene, opt, cam, ni, nj, shade, aa, (R*)(base + arrs[0].off), out ? &o : nullptr, d_refined, ctr, stats, S->s_comp))) {
-        (void)hipStreamSynchronize(S->s_comp);
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(S->s_comp));
-    for (const RayArray& a : arrs) HIP_TRY(hipMemcpy(a.ptr, base + a.off, (size_t)n * a.elem * a.planes, hipMemcpyDeviceToHost));
-    if (refined) HIP_TRY(hipMemcpy(refined, d_refined, n, hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    return staged_frame<R>(c, ni * nj, rgb, out, refined, nullptr, [&](DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs* d_out, uint8_t* d_refined, R*, hipStream_t st) {
+        return trace_camera_frame_on<R>(D, scene, opt, cam, ni, nj, shade, nullptr, aa, d_rgb, d_out, nullptr, d_refined, ctr, stats, st, SHADED_WORDS);
+    });
 }
 
 // the sampler at n points, on device 0 of the context (host pointers): rgb goes up too — a "no sample" point keeps its entry
