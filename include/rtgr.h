@@ -39,7 +39,8 @@
  *    may run concurrently.  Results are bit-identical to serial execution either way (tests: two streams, two threads).
  *  - A workspace only grows.  The superseded allocation stays alive until rtgr_trim / rtgr_destroy, so a hipGraph
  *    captured earlier never dangles; growth DURING stream capture is refused with RTGR_ERR_BAD_ARG (hipMalloc cannot be
- *    captured): call rtgr_reserve_workspace before capturing.
+ *    captured): call rtgr_reserve_workspace before capturing.  The device tables of object lists longer than
+ *    RTGR_MAX_OBJECTS are covered by the same promise: one that a captured call uses stays until rtgr_trim / rtgr_destroy.
  */
 #ifndef RTGR_H
 #define RTGR_H

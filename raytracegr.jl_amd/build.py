@@ -3,7 +3,7 @@
     python raytracegr.jl_amd/build.py [--force] [--resource-usage] [--save-temps] [--via-listing] [-DNAME[=V] ...]
 
 The library is several translation units (csrc/tu_*.hip hold the kernels of one metric-variant group each,
-csrc/rtgr_misc.hip, rtgr_aa.hip, rtgr_shade.hip, rtgr_emit.hip and rtgr_observer.hip the small kernels; the host side is kernel-free: csrc/rtgr_context.hip, rtgr_host_pipeline.hip, rtgr_sharded.hip,
+csrc/rtgr_misc.hip, rtgr_aa.hip, rtgr_shade.hip, rtgr_emit.hip and rtgr_observer.hip the small kernels; the host side is kernel-free: csrc/rtgr_context.hip, rtgr_tables.hip, rtgr_scene_host.hip, rtgr_host_pipeline.hip, rtgr_sharded.hip,
 rtgr_hooks.hip, rtgr_units.hip, rtgr_frame_host.hip, rtgr_aa_host.hip, rtgr_texture_host.hip, rtgr_emission_host.hip, rtgr_observer_host.hip and the extern "C" shims of csrc/rtgr_abi.hip — rtgr_internal.hpp says what is where); they are compiled in parallel
 into raytracegr.jl_amd/build/obj/ and linked with `hipcc -shared`.
 
@@ -25,7 +25,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 UNITS = ["tu_f64_ksref.hip", "tu_f64_kstrue.hip", "tu_f64_generic.hip", "tu_f64_mink.hip", "tu_f32_closed.hip",
-         "tu_f32_generic.hip", "tu_f64_grid.hip", "tu_f32_grid.hip", "tu_f64_grid4.hip", "tu_f32_grid4.hip", "rtgr_misc.hip", "rtgr_aa.hip", "rtgr_shade.hip", "rtgr_emit.hip", "rtgr_observer.hip", "rtgr_context.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip",
+         "tu_f32_generic.hip", "tu_f64_grid.hip", "tu_f32_grid.hip", "tu_f64_grid4.hip", "tu_f32_grid4.hip", "rtgr_misc.hip", "rtgr_aa.hip", "rtgr_shade.hip", "rtgr_emit.hip", "rtgr_observer.hip", "rtgr_context.hip", "rtgr_tables.hip", "rtgr_scene_host.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip",
          "rtgr_units.hip", "rtgr_grid.hip", "rtgr_frame_host.hip", "rtgr_aa_host.hip", "rtgr_texture_host.hip", "rtgr_emission_host.hip", "rtgr_observer_host.hip", "rtgr_abi.hip"]
 # THE list of device headers (csrc/): what every kernel — the library's and a run-time unit's — is made of.  A new device header goes
 # here and into rtgr_units.hip header_hash_of (the C++ build route of a unit, which runs without Python; tests/test_build_checks.py
@@ -43,7 +43,7 @@ OBJ = os.path.join(HERE, "build", "obj")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 LLVM_BIN = os.path.join(os.path.dirname(os.path.realpath(HIPCC)), "..", "lib", "llvm", "bin")
 # no kernel in them: they never need the listing route
-HOST_ONLY_UNITS = ("rtgr_context.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip", "rtgr_units.hip", "rtgr_grid.hip", "rtgr_frame_host.hip", "rtgr_aa_host.hip", "rtgr_texture_host.hip", "rtgr_emission_host.hip", "rtgr_observer_host.hip", "rtgr_abi.hip")
+HOST_ONLY_UNITS = ("rtgr_context.hip", "rtgr_tables.hip", "rtgr_scene_host.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip", "rtgr_units.hip", "rtgr_grid.hip", "rtgr_frame_host.hip", "rtgr_aa_host.hip", "rtgr_texture_host.hip", "rtgr_emission_host.hip", "rtgr_observer_host.hip", "rtgr_abi.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 

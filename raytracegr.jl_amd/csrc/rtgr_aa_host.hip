@@ -33,8 +33,7 @@ int trace_aa_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, c
     if ((rc = aa_check(scene, cam, aa, ni, nj))) return rc;
     DeviceGuard guard(D.dev);
     if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (stream_capturing(st))
         return fail(RTGR_ERR_BAD_ARG, "rtgr_trace_aa_*: the stream is being captured, and the call must read the number of refined pixels back "
                                       "between its two passes (a synchronisation cannot be captured)");
     const uint64_t n = ni * nj;

@@ -18,7 +18,7 @@ struct DevObject {
 
 // The object list (src/RayTraceGR.jl:433-441: a Vector of any length).  The first RTGR_MAX_OBJECTS objects sit in the kernels' argument
 // block (scalar loads from the kernarg segment), the rest — rare — in a device table the context keeps per distinct list
-// (rtgr_context.hip: object_table); `more` is null when nobj <= RTGR_MAX_OBJECTS.  Kernels walk the list with for_each_object /
+// (rtgr_tables.hip: object_table); `more` is null when nobj <= RTGR_MAX_OBJECTS.  Kernels walk the list with for_each_object /
 // for_each_by_kind (rtgr_objects.hpp), never by index.
 // ORDER.  The caller's order matters to the colour rule only (first-smaller-wins and the scale omin / length(objs),
 // src/RayTraceGR.jl:520-530); the event condition is a minimum (:433-441) and the FAR pass's reach test a conjunction — neither
@@ -67,11 +67,11 @@ struct DevScene {
     const DevObject<R>* more;   // objects RTGR_MAX_OBJECTS .. nobj-1 (the table holds the WHOLE list: table = more - RTGR_MAX_OBJECTS)
     uint32_t nloose;    // (ngroups > 0) spheres [0, nloose) belong to no group
     uint32_t nsuper;    // > 0: the groups themselves come in that many runs of neighbouring groups with a bounding sphere each (a second level)
-    DevGrid<R> grid;    // metric == RTGR_GRID: the samples (rtgr_context.hip: grid tables)
+    DevGrid<R> grid;    // metric == RTGR_GRID: the samples (rtgr_tables.hip: grid tables)
 };
 // GROUPS (long lists: DESIGN.md §4.7).  The FAR pass's reach test asks of every object, every step, "can this step reach you?"; of a
 // list of 64 small spheres the answer is no for all but one or two.  The host therefore sorts the spheres of a long list into groups of
-// up to RTGR_GROUP_MAX neighbours (median splits of their centres: rtgr_context.hip) and gives every group a bounding sphere; a step
+// up to RTGR_GROUP_MAX neighbours (median splits of their centres: rtgr_scene_host.hip) and gives every group a bounding sphere; a step
 // that provably stays outside a group's bounding sphere cannot change the sign of any member's distance, and the members are only
 // asked when some lane of the wave cannot prove that.  A group is a DevObject in sphere form — p[1..3] the centre, p[8] the radius,
 // `type` the position of its first member in the device list, `orig` their number — and the groups follow the objects in the table:

@@ -41,8 +41,7 @@ int scratch_need(StreamState& ss, void*& p, size_t& have, size_t bytes) {
 }
 
 int capture_check(hipStream_t st, const EntryWords& who, const rtgr_counters* ctr, bool* capturing) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    *capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    *capturing = stream_capturing(st);
     if (*capturing && ctr)
         return fail(RTGR_ERR_BAD_ARG, std::string(who.entry) + ": the stream is being captured and `ctr` asks for a synchronisation at the end of the call "
                                       "(which cannot be captured): pass ctr = NULL");

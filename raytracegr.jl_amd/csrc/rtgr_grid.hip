@@ -1,16 +1,16 @@
-// rtgr_grid.hip — metrics sampled on a grid (RTGR_GRID, include/rtgr.h; 3-D and time-dependent 4-D): load (checks, upload to every device of the context in
-// Float64 and Float32) and unload (retire: a hipGraph captured earlier may still replay the samples; rtgr_trim frees them).  Host code
-// only: the interpolant is rtgr_grid_interp.hpp's (grid_eval, grid4_eval), the kernels are tu_f64_grid.hip's / tu_f32_grid.hip's and
+// rtgr_grid.hip — metrics sampled on a grid (RTGR_GRID, include/rtgr.h; 3-D and time-dependent 4-D): the checks of a load and the images it
+// uploads, in Float64 and Float32, and the unload — both through the one path of rtgr_tables.hip (retire: a hipGraph captured earlier may
+// still replay the samples; rtgr_trim frees them).  Host code only: the interpolant is rtgr_grid_interp.hpp's (grid_eval, grid4_eval), the kernels are tu_f64_grid.hip's / tu_f32_grid.hip's and
 // tu_f64_grid4.hip's / tu_f32_grid4.hip's; what the kernels read of the axes is built from GridAxes in rtgr_host.hpp (dev_grid, dev_grid_time).
-#include <atomic>
 #include <cmath>
 #include "rtgr_internal.hpp"
 
 namespace rtgr {
 
-// Grid ids: a counter of their own, in a range of their own (top bits 0xA...), and never the id of a resident unit of the context.
-static std::atomic<uint64_t> g_next_grid{1};
+// Grid ids: a counter of their own, in a range of their own (top bits 0xA...), and never the id of a resident unit or table of the
+// context (table_load).
 constexpr uint64_t GRID_ID_TAG = 0xA000000000000000ull;
+static TableIds g_grid_ids{GRID_ID_TAG, GRID_ID_TAG};
 
 // det of the symmetric 4x4 given by its upper triangle tt tx ty tz xx xy xz yy yz zz (long double: a Lorentzian sample near
 // degenerate must not be refused for rounding)
@@ -23,8 +23,8 @@ static long double det_upper(const double* c) {
     return s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
 }
 
-// The load of either kind.  Checks the axes and every sample, then uploads Float64 and Float32 copies to every device (a 4-D table
-// behind the GRID4_HEADER bytes of its time axis' descriptor, rtgr_args.hpp) and publishes the table under a fresh id.
+// The load of either kind.  Checks the axes and every sample, then has Float64 and Float32 copies uploaded to every device (a 4-D table
+// behind the GRID4_HEADER bytes of its time axis' descriptor, rtgr_args.hpp) and the table published under a fresh id (table_load).
 static int grid_load(rtgr_context* c, const char* who, const GridAxes& A, const double* g, uint64_t* id_out) {
     const bool nt = A.dims == 4;
     const uint32_t* n = A.n + 1;   // the spatial axes
@@ -60,55 +60,20 @@ static int grid_load(rtgr_context* c, const char* who, const GridAxes& A, const 
                                                   : "holds a non-finite value"));
         }
     }
-    // a 4-D table starts with its time axis' descriptor (DevGridTime, read by the kernels), in each scalar type
-    const size_t head = nt ? (size_t)GRID4_HEADER : 0;
+    // a 4-D table starts with the GRID4_HEADER bytes of its time axis' descriptor (DevGridTime, read by the kernels), in each scalar type
     const DevGridTime<double> t64 = dev_grid_time<double>(A);
     const DevGridTime<float> t32 = dev_grid_time<float>(A);
     static_assert(sizeof(DevGridTime<double>) <= GRID4_HEADER && sizeof(DevGridTime<float>) <= GRID4_HEADER, "GRID4_HEADER");
-    const size_t b64 = (size_t)npts * 10 * sizeof(double), b32 = (size_t)npts * 10 * sizeof(float);
-    std::lock_guard<std::mutex> load_lock(c->modules_mu);   // (units and grids are loaded / unloaded under the same lock)
-    uint64_t id = 0;
-    for (;;) {
-        id = GRID_ID_TAG | (g_next_grid.fetch_add(1) & ~GRID_ID_TAG);
-        bool taken = false;
-        for (auto& d : c->devs) {
-            std::lock_guard<std::mutex> lk(d->mu);
-            taken = taken || d->find_module(id) || d->find_grid(id);
-        }
-        if (!taken) break;
-    }
-    // allocate and upload everywhere first; the tables become visible to scenes only when every device has its copy
-    std::vector<GridTable> made(c->devs.size());
-    auto release = [&]() {
-        for (size_t k = 0; k < made.size(); k++) {
-            DeviceGuard guard(c->devs[k]->dev);
-            if (made[k].d64) (void)hipFree(made[k].d64);
-            if (made[k].d32) (void)hipFree(made[k].d32);
-        }
-    };
-    for (size_t k = 0; k < c->devs.size(); k++) {
-        DeviceGuard guard(c->devs[k]->dev);
-        if (!guard.ok) { release(); return fail(RTGR_ERR_HIP, "hipSetDevice failed"); }
-        GridTable& t = made[k];
-        t.id = id;
-        t.axes = A;
-        hipError_t e = hipMalloc(&t.d64, head + b64);
-        if (e == hipSuccess) e = hipMalloc(&t.d32, head + b32);
-        if (e == hipSuccess && nt) e = hipMemcpy(t.d64, &t64, sizeof t64, hipMemcpyHostToDevice);
-        if (e == hipSuccess && nt) e = hipMemcpy(t.d32, &t32, sizeof t32, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy((char*)t.d64 + head, g, b64, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy((char*)t.d32 + head, g32.data(), b32, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            release();
-            return fail(RTGR_ERR_HIP, std::string(who) + ": upload to device " + std::to_string(k) + ": " + hipGetErrorString(e));
-        }
-    }
-    for (size_t k = 0; k < c->devs.size(); k++) {
-        std::lock_guard<std::mutex> lk(c->devs[k]->mu);
-        c->devs[k]->grids.push_back(made[k]);
-    }
-    *id_out = id;
-    return RTGR_OK;
+    char head64[GRID4_HEADER] = {}, head32[GRID4_HEADER] = {};
+    std::memcpy(head64, &t64, sizeof t64);
+    std::memcpy(head32, &t32, sizeof t32);
+    GridTable t;
+    t.axes = A;
+    TableImage image64, image32;
+    if (nt) { image64.push_back({head64, sizeof head64}); image32.push_back({head32, sizeof head32}); }
+    image64.push_back({g, (size_t)npts * 10 * sizeof(double)});
+    image32.push_back({g32.data(), (size_t)npts * 10 * sizeof(float)});
+    return table_load(c, who, g_grid_ids, &DeviceCtx::grids, t, image64, image32, id_out);
 }
 
 int api::grid_metric_load(rtgr_context* ctx, const rtgr_grid* grid, const double* g, uint64_t* id_out) {
@@ -137,34 +102,9 @@ int api::grid_metric_unload(rtgr_context* ctx, uint64_t id) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
-    std::lock_guard<std::mutex> load_lock(c->modules_mu);
-    bool found = false;
-    for (auto& d : c->devs) {
-        std::lock_guard<std::mutex> lk(d->mu);
-        for (size_t k = 0; k < d->grids.size(); k++)
-            if (d->grids[k].id == id) {
-                d->retired_grids.push_back(d->grids[k]);   // (not freed: a captured hipGraph may replay it until rtgr_trim)
-                d->grids.erase(d->grids.begin() + (long)k);
-                found = true;
-                break;
-            }
-    }
+    const bool found = table_unload(c, &DeviceCtx::grids, id, false);   // (id 0 names no grid)
     if (!found) return fail(RTGR_ERR_BAD_ARG, "rtgr_grid_metric_unload: no grid metric with id " + std::to_string(id) + " is loaded in this context");
     return RTGR_OK;
 }
 
 }  // namespace rtgr
-
-// A test hook, not part of include/rtgr.h (tests/test_grid_metric.py): grid tables on device `index` of the context — resident and
-// retired (unloaded, waiting for rtgr_trim).
-extern "C" int rtgr_testhook_grid_tables(rtgr_context* ctx, int index, uint32_t* resident, uint32_t* retired) {
-    rtgr_context* c = nullptr;
-    int rc = rtgr::resolve_ctx(ctx, &c);
-    if (rc) return rc;
-    if (index < 0 || (size_t)index >= c->devs.size() || !resident || !retired) return rtgr::fail(RTGR_ERR_BAD_ARG, "bad argument");
-    rtgr::DeviceCtx& d = *c->devs[(size_t)index];
-    std::lock_guard<std::mutex> lk(d.mu);
-    *resident = (uint32_t)d.grids.size();
-    *retired = (uint32_t)d.retired_grids.size();
-    return RTGR_OK;
-}

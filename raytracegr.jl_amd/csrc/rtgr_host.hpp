@@ -12,6 +12,7 @@
 //                           hand-over / event records, per-ray meta, queue order, work-queue heads).  Launches on ONE
 //                           stream are ordered by the stream and share a workspace; launches on DIFFERENT streams get
 //                           different workspaces, so they never race (round 1 had one process-global workspace)
+//       resident tables     grid metrics and image textures by id (Resident<T>), the tables of long object lists by content
 //       user modules        run-time compiled units (a metric, Object subtypes, or both), keyed by the 64-bit id a scene carries
 //                           (rtgr_scene.user_metric)
 //       staging             pinned host buffers + device buffers + 3 streams of the host-pointer entry points
@@ -22,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <memory>
@@ -42,6 +44,12 @@ int fail(int code, const std::string& msg);  // records the calling thread's las
         if (e_ != hipSuccess)                                                                       \
             return ::rtgr::fail(RTGR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
+
+// whether work enqueued on st is being recorded into a hipGraph rather than run
+inline bool stream_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+}
 
 // ---- launch policy knobs ------------------------------------------------------------------------------------------------
 // Parsed ONCE from the environment when a context is created (RTGR_<NAME>), changeable per context with
@@ -110,17 +118,50 @@ struct UserModule {
 
 struct TimedLaunch { hipEvent_t a, b; int which; };
 
+// ---- what a context keeps resident on a device for its kernels to read -------------------------------------------------------------
+// ONE lifetime rule (include/rtgr.h): memory a kernel may read is immutable and is freed by rtgr_trim / rtgr_destroy only — a
+// kernel in flight, or a hipGraph captured earlier, never sees it change or go away.  Load and unload: rtgr_tables.hip.
+//
+// The tables of one kind that are named by an id (T: GridTable, TextureTable, below — `id`, `d64`, `d32`) on one device: unloading
+// RETIRES a table — its id becomes unknown, its memory stays.  Bookkeeping only, no HIP call: whoever drains frees what is handed back
+// (tests/c/resident_tables.cpp runs it without a device).
+template <class T>
+struct Resident {
+    std::vector<T> live, retired;
+    const T* find(uint64_t id) const {
+        for (auto& t : live) if (t.id == id) return &t;
+        return nullptr;
+    }
+    void publish(const T& t) { live.push_back(t); }
+    // table `id` — every table when id is 0 and zero_means_all — from live to retired; whether there was one (an "all" always is)
+    bool retire(uint64_t id, bool zero_means_all) {
+        const bool all = id == 0 && zero_means_all;
+        const auto gone = std::stable_partition(live.begin(), live.end(), [&](const T& t) { return !all && t.id != id; });
+        const bool found = all || gone != live.end();
+        retired.insert(retired.end(), gone, live.end());
+        live.erase(gone, live.end());
+        return found;
+    }
+    size_t n_resident() const { return live.size(); }
+    size_t n_retired() const { return retired.size(); }
+    // the device pointers to free now — of the retired tables, or (all) of every table — which the container forgets
+    std::vector<void*> drain(bool all) {
+        if (all) retire(0, true);
+        std::vector<void*> out;
+        for (auto& t : retired) { out.push_back(t.d64); out.push_back(t.d32); }
+        retired.clear();
+        return out;
+    }
+};
 // A scene whose list is longer than the kernels' argument block holds (DevScene::more): the whole list, its groups and runs of groups in
-// one immutable device table per distinct (scalar type, list, layout) a device has seen, found again by content.  Immutable, so a
-// kernel in flight — or a hipGraph captured earlier — never sees it change; freed by rtgr_trim / rtgr_destroy (or all at once, behind
-// a device synchronisation, when a caller has gone through OBJECT_TABLES_MAX distinct lists or OBJECT_TABLES_BYTES of them: an
-// animation of a 100000-object list is 9 MB a frame, on the device and in the host copy the lookup compares with).
-struct ObjectTable { std::vector<char> content; void* dev = nullptr; };
-constexpr size_t OBJECT_TABLES_MAX = 512;
-constexpr size_t OBJECT_TABLES_BYTES = (size_t)1 << 30;
+// one immutable device table per distinct (scalar type, list, layout) a device has seen, found again by content.  An animation of a
+// 100000-object list is 9 MB a frame, on the device and in the host copy the lookup compares with, so past a number and a size
+// (rtgr_tables.hip: object_table) the tables are freed, behind a device synchronisation — EXCEPT those `kept`: a table found while the
+// call's stream was being captured is held by that graph and goes with rtgr_trim / rtgr_destroy, like everything a graph may replay.
+struct ObjectTable { std::vector<char> content; void* dev = nullptr; bool kept = false; };
 
 // A metric sampled on a grid (rtgr_grid_metric_load): the samples on one device, in Float64 and Float32.  Immutable; rtgr_grid_metric_unload
-// moves the table to DeviceCtx::retired_grids (a hipGraph captured earlier may still replay it), rtgr_trim / rtgr_destroy free it.
+// retires the table (Resident above: a hipGraph captured earlier may still replay it), rtgr_trim / rtgr_destroy free it.
 // The axes of either kind, described once: t, x, y, z as in rtgr_grid4 (include/rtgr.h); a 3-D grid has dims = 3 and no axis 0.
 struct GridAxes {
     int dims = 3;   // 3: RTGR_GRID as loaded by rtgr_grid_metric_load; 4: time-dependent (rtgr_grid4_metric_load; RTGR_GRID4 on the device)
@@ -157,7 +198,7 @@ template <class R> inline DevGrid<R> dev_grid(const GridTable& t) {
     return G;
 }
 // An image texture (rtgr_texture_load): the texels on one device, four scalars per texel (r, g, b, 0), row after row, in Float64 and
-// Float32.  Immutable; rtgr_texture_unload moves the table to DeviceCtx::retired_textures, rtgr_trim / rtgr_destroy free it.
+// Float32.  Immutable; rtgr_texture_unload retires the table, rtgr_trim / rtgr_destroy free it.
 struct TextureTable {
     uint64_t id = 0;
     uint32_t W = 0, H = 0;
@@ -188,10 +229,8 @@ struct DeviceCtx {
     std::mutex mu;      // held while a call enqueues its kernels: the enqueue sequences of two host threads never interleave
     std::unordered_map<hipStream_t, StreamState> streams;
     std::vector<UserModule> modules;
-    std::vector<GridTable> grids;           // resident grid metrics, by id
-    std::vector<GridTable> retired_grids;   // unloaded ones: freed by rtgr_trim / rtgr_destroy only
-    std::vector<TextureTable> textures;           // resident image textures, by id
-    std::vector<TextureTable> retired_textures;   // unloaded ones: freed by rtgr_trim / rtgr_destroy only
+    Resident<GridTable> grids;         // grid metrics, by id
+    Resident<TextureTable> textures;   // image textures, by id
     std::unordered_multimap<uint64_t, ObjectTable> object_tables;   // by FNV-1a of the content
     size_t object_table_bytes = 0;                                   // … and what they hold together
     std::unordered_map<uint64_t, int> checked_scenes;                // auto_scene_check: key of a scene -> the verdict it got (RTGR_OK or the refusal)
@@ -212,14 +251,6 @@ struct DeviceCtx {
         hipEvent_t e = nullptr;
         (void)hipEventCreate(&e);
         return e;
-    }
-    const GridTable* find_grid(uint64_t id) const {
-        for (auto& g : grids) if (g.id == id) return &g;
-        return nullptr;
-    }
-    const TextureTable* find_texture(uint64_t id) const {
-        for (auto& t : textures) if (t.id == id) return &t;
-        return nullptr;
     }
     const UserModule* find_module(uint64_t id) const {
         for (auto& m : modules) if (m.id == id) return &m;

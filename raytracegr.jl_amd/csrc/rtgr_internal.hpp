@@ -1,7 +1,12 @@
 // rtgr_internal.hpp — what the HOST translation units of librtgr_hip.so share (no kernel, no device code):
 //
-//   rtgr_context.hip        error plumbing, launch options, contexts and their per-device / per-stream state, argument checking
-//                           and conversion, dispatch to the kernels' translation units (tu_*.hip), the device entry points
+//   rtgr_context.hip        error plumbing, launch options, contexts and their per-device / per-stream state, the enqueue of one trace:
+//                           dispatch to the kernels' translation units (tu_*.hip), the device entry points
+//   rtgr_tables.hip         what a context keeps resident on its devices under one lifetime rule: the load / unload path of the tables
+//                           named by an id (grid metrics, image textures), the tables of long object lists, the table-count test hooks
+//   rtgr_scene_host.hip     argument conversion: a scene (its object list regrouped, the spheres of a long list in groups), a solver and a
+//                           camera into what the kernels read
+//   rtgr_grid.hip           metrics sampled on a grid: the checks of a load, the axes, the entry points
 //   rtgr_host_pipeline.hip  the host-pointer entry points: pinned staging + a three-stream H2D / compute / D2H pipeline
 //   rtgr_sharded.hip        one call over every device of a context: cyclic rows, peer copies to device 0
 //   rtgr_hooks.hip          make_canvas and the parity hooks (rtgr_eval_*), image quantisation
@@ -119,7 +124,25 @@ uint64_t fnv1a(const std::vector<char>& b);
     DeviceCtx* D = nullptr;                          \
     if ((rc = device_of(c, (ptr), &D))) return rc
 
-// ---- argument conversion and the device-side enqueue (rtgr_context.hip) ------------------------------------------------------
+// ---- resident tables (rtgr_tables.hip) -----------------------------------------------------------------------------------------
+void free_all(const std::vector<void*>& ptrs);   // hipFree of each (the device is current and idle)
+struct TableIds { uint64_t tag, mask; std::atomic<uint64_t> next{1}; };   // the ids of one kind: tag | (counter & ~mask)
+struct TableSegment { const void* p; size_t bytes; };
+typedef std::vector<TableSegment> TableImage;   // what is uploaded as one table: segments, one behind the other
+// THE load of a table named by an id (`kind`: its Resident in DeviceCtx): a fresh id, the Float64 and the Float32 image uploaded to every
+// device of the context — or to none: a failure rolls back —, `t` with the id and the two addresses published on each.  Takes
+// c->modules_mu, then each D.mu briefly.  `who`: the entry point, for the refusal.
+template <class T>
+int table_load(rtgr_context* c, const char* who, TableIds& ids, Resident<T> DeviceCtx::*kind, T t, const TableImage& image64,
+               const TableImage& image32, uint64_t* id_out);
+// … and the unload: the table retired on every device (same locks); whether any device knew the id
+template <class T> bool table_unload(rtgr_context* c, Resident<T> DeviceCtx::*kind, uint64_t id, bool zero_means_all);
+// (D.mu held; `st`: the stream the scene's kernels go on)  The device table with this content, uploaded on first sight — which a stream
+// under capture cannot wait for; a table found during capture is kept until rtgr_trim / rtgr_destroy
+int object_table(DeviceCtx& D, const std::vector<char>& content, hipStream_t st, const void** dev);
+std::vector<void*> drain_object_tables(DeviceCtx& d);   // every table's address, to be freed; the device forgets them
+
+// ---- argument conversion (rtgr_scene_host.hip) and the device-side enqueue (rtgr_context.hip) --------------------------------------
 void scene_variant(const rtgr_scene* s, uint32_t* metric, bool* spin);
 // The load-time probe of a unit of OBJECTS traces a scene of built-in objects (it knows no parameters of the user's) and must still run
 // the UNIT's kernels, not the library's: while this is set on the calling thread, a scene that names a unit runs with it even though
@@ -128,8 +151,7 @@ extern thread_local bool tl_probe_forces_unit;
 // … and the probe (and rtgr_scene_check) choose the launch options of THEIR calls — pass structure, queue order, grid size — without
 // touching the device's options, which other threads' calls on the same device read: null = the device's options decide.
 extern thread_local const Knobs* tl_knobs_override;
-// (D.mu held.  `st`: the stream the scene's kernels will be enqueued on — a list of more than RTGR_MAX_OBJECTS objects seen for the
-//  first time is uploaded to a device table, which a stream under capture cannot wait for)
+// (D.mu held.  `st`: the stream the scene's kernels will be enqueued on: object_table above)
 template <class R> int convert_scene(DeviceCtx& D, const rtgr_scene* s, DevScene<R>& d, const UserModule** user, hipStream_t st = nullptr);
 // the object list of a scene: rtgr_scene.objects when given, else the inline slots
 inline const rtgr_object* scene_objects(const rtgr_scene* s) { return s->objects ? s->objects : s->obj; }

@@ -13,7 +13,7 @@ namespace rtgr {
 //     template <class S> __device__ S    rtgr_user_reach(unsigned type, const S x[4], const S p[9], const S dl[4]);
 //     >= |distance(x') − distance(x)| for every x' with |x'_q − x_q| <= dl[q]
 // (include/rtgr.h "user objects").  The library's own kernels are compiled without them: a scene with an RTGR_USER_OBJECT
-// only ever runs with the kernels of its unit (convert_scene, rtgr_context.hip).
+// only ever runs with the kernels of its unit (convert_scene, rtgr_scene_host.hip).
 #ifdef RTGR_USER_OBJECTS
 template <class S> __device__ S rtgr_user_distance(unsigned type, const S x[4], const S p[9]);
 template <class S> __device__ void rtgr_user_objcolor(unsigned type, const S x[4], const S p[9], S rgb[3]);
@@ -49,7 +49,7 @@ RTGR_DEV R obj_distance(const DevObject<R>& o, const R pos[4]) {
 // objects by the sign at the step start and tests < 0 / <= 0; the minimum's sign is fixed by its members' signs).  The two
 // radial terms r_in − ϱ and ϱ − r_out are replaced by THEIR SIGNS, read off s = x² + y² without taking the root: the host
 // precomputes, in the device's scalar type, the band of s whose correctly rounded square root equals the radius
-// (p[3] = min{s : √s >= r_in}, p[4] = min{s : √s > r_in}, p[5], p[6] likewise for r_out; disk_sqrt_band, rtgr_context.hip), so
+// (p[3] = min{s : √s >= r_in}, p[4] = min{s : √s > r_in}, p[5], p[6] likewise for r_out; disk_sqrt_band, rtgr_scene_host.hip), so
 //     sign(r_in − RN(√s)) = +1 for s < p[3], 0 for p[3] <= s < p[4], −1 otherwise
 // EXACTLY — same sign, zero included, as obj_distance computes with its IEEE square root, for every s (√ is monotone and
 // correctly rounded).  Nine IEEE roots (~16 instructions each) per accepted NEAR step become compares and selects; the true

@@ -1,5 +1,6 @@
-// rtgr_texture_host.hip — image textures (include/rtgr.h "image textures"): load (checks, upload to every device of the context in Float64
-// and Float32) and unload (retire: a hipGraph captured earlier may still replay the texels; rtgr_trim frees them), the binds of a call
+// rtgr_texture_host.hip — image textures (include/rtgr.h "image textures"): the texel check and the device layout of a load, in Float64 and
+// Float32, and the unload — both through the one path of rtgr_tables.hip (retire: a hipGraph captured earlier may still replay the texels;
+// rtgr_trim frees them) —, the binds of a call
 // into the records the shading kernel reads, the entry points of the shaded trace — the camera frame of rtgr_frame_host.hip without an
 // emitting disk — and the sampler hook.  Host code only: the kernels are rtgr_shade.hip's, the mapping and the sampler rtgr_texture.hpp's.
 #include "rtgr_internal.hpp"
@@ -7,9 +8,9 @@
 namespace rtgr {
 
 // Texture ids: a counter of their own, in a range of their own (top bits 0x7…; grid ids carry 0xA…), and never the id of a resident
-// unit or grid of the context.
-static std::atomic<uint64_t> g_next_texture{1};
+// unit or table of the context (table_load).
 constexpr uint64_t TEXTURE_ID_TAG = 0x7000000000000000ull, TEXTURE_ID_MASK = 0xF000000000000000ull;
+static TableIds g_texture_ids{TEXTURE_ID_TAG, TEXTURE_ID_MASK};
 constexpr EntryWords SHADED_WORDS = {"rtgr_trace_shaded_*", "shading", true};
 
 int api::texture_load(rtgr_context* ctx, const rtgr_texture_desc* desc, const double* texels, uint64_t* id_out) {
@@ -35,65 +36,17 @@ int api::texture_load(rtgr_context* ctx, const rtgr_texture_desc* desc, const do
             t64[q * 4 + ch] = v;
             t32[q * 4 + ch] = (float)v;
         }
-    std::lock_guard<std::mutex> load_lock(c->modules_mu);   // (units, grids and textures are loaded / unloaded under the same lock)
-    uint64_t id = 0;
-    for (;;) {
-        id = TEXTURE_ID_TAG | (g_next_texture.fetch_add(1) & ~TEXTURE_ID_MASK);
-        bool taken = false;
-        for (auto& d : c->devs) {
-            std::lock_guard<std::mutex> lk(d->mu);
-            taken = taken || d->find_module(id) || d->find_grid(id) || d->find_texture(id);
-        }
-        if (!taken) break;
-    }
-    // allocate and upload everywhere first; the texture becomes visible to calls only when every device has its copy
-    std::vector<TextureTable> made(c->devs.size());
-    auto release = [&]() {
-        for (size_t k = 0; k < made.size(); k++) {
-            DeviceGuard guard(c->devs[k]->dev);
-            if (made[k].d64) (void)hipFree(made[k].d64);
-            if (made[k].d32) (void)hipFree(made[k].d32);
-        }
-    };
-    for (size_t k = 0; k < c->devs.size(); k++) {
-        DeviceGuard guard(c->devs[k]->dev);
-        if (!guard.ok) { release(); return fail(RTGR_ERR_HIP, "hipSetDevice failed"); }
-        TextureTable& t = made[k];
-        t.id = id; t.W = W; t.H = H;
-        hipError_t e = hipMalloc(&t.d64, t64.size() * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&t.d32, t32.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(t.d64, t64.data(), t64.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(t.d32, t32.data(), t32.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            release();
-            return fail(RTGR_ERR_HIP, "rtgr_texture_load: upload to device " + std::to_string(k) + ": " + hipGetErrorString(e));
-        }
-    }
-    for (size_t k = 0; k < c->devs.size(); k++) {
-        std::lock_guard<std::mutex> lk(c->devs[k]->mu);
-        c->devs[k]->textures.push_back(made[k]);
-    }
-    *id_out = id;
-    return RTGR_OK;
+    TextureTable t;
+    t.W = W; t.H = H;
+    return table_load(c, "rtgr_texture_load", g_texture_ids, &DeviceCtx::textures, t, {{t64.data(), t64.size() * sizeof(double)}},
+                      {{t32.data(), t32.size() * sizeof(float)}}, id_out);
 }
 
 int api::texture_unload(rtgr_context* ctx, uint64_t id) {
     rtgr_context* c = nullptr;
     int rc = resolve_ctx(ctx, &c);
     if (rc) return rc;
-    std::lock_guard<std::mutex> load_lock(c->modules_mu);
-    bool found = id == 0;
-    for (auto& d : c->devs) {
-        std::lock_guard<std::mutex> lk(d->mu);
-        for (size_t k = 0; k < d->textures.size();)
-            if (id == 0 || d->textures[k].id == id) {
-                d->retired_textures.push_back(d->textures[k]);   // (not freed: a captured hipGraph may replay it until rtgr_trim)
-                d->textures.erase(d->textures.begin() + (long)k);
-                found = true;
-            } else {
-                k++;
-            }
-    }
+    const bool found = table_unload(c, &DeviceCtx::textures, id, true);   // (id 0: all of them)
     if (!found) return fail(RTGR_ERR_BAD_ARG, "rtgr_texture_unload: no texture with id " + std::to_string(id) + " is loaded in this context");
     return RTGR_OK;
 }
@@ -125,7 +78,7 @@ int shade_resolve(DeviceCtx& D, const rtgr_scene* scene, const rtgr_shade* shade
         const std::string who = "rtgr_shade.bind[" + std::to_string(k) + "]";
         int rc;
         if ((rc = filter_check(b.filter))) return fail(rc, who + ": " + last_error_string());
-        const TextureTable* t = D.find_texture(b.texture);
+        const TextureTable* t = D.textures.find(b.texture);
         if (!t) return fail(RTGR_ERR_BAD_ARG, who + ": no texture with id " + std::to_string(b.texture) + " is loaded in this context");
         if (b.object > scene->nobj)
             return fail(RTGR_ERR_BAD_ARG, who + ": object " + std::to_string(b.object) + " of a list of " + std::to_string(scene->nobj) + " (1-based; 0 = rays that escape)");
@@ -199,7 +152,7 @@ int api::eval_texture(rtgr_context* ctx, uint64_t texture, uint32_t filter, cons
     TextureTable t;
     {
         std::lock_guard<std::mutex> lk(D.mu);
-        const TextureTable* found = D.find_texture(texture);
+        const TextureTable* found = D.textures.find(texture);
         if (!found) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_texture: no texture with id " + std::to_string(texture) + " is loaded in this context");
         t = *found;
     }
@@ -223,17 +176,3 @@ RTGR_INSTANTIATE_F64_F32(api::trace_shaded);
 RTGR_INSTANTIATE_F64_F32(api::eval_texture);
 
 }  // namespace rtgr
-
-// A test hook, not part of include/rtgr.h (tests/test_textures.py): texture tables on device `index` of the context — resident and
-// retired (unloaded, waiting for rtgr_trim).
-extern "C" int rtgr_testhook_texture_tables(rtgr_context* ctx, int index, uint32_t* resident, uint32_t* retired) {
-    rtgr_context* c = nullptr;
-    int rc = rtgr::resolve_ctx(ctx, &c);
-    if (rc) return rc;
-    if (index < 0 || (size_t)index >= c->devs.size() || !resident || !retired) return rtgr::fail(RTGR_ERR_BAD_ARG, "bad argument");
-    rtgr::DeviceCtx& d = *c->devs[(size_t)index];
-    std::lock_guard<std::mutex> lk(d.mu);
-    *resident = (uint32_t)d.textures.size();
-    *retired = (uint32_t)d.retired_textures.size();
-    return RTGR_OK;
-}

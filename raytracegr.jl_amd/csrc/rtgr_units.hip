@@ -748,8 +748,7 @@ int auto_scene_check(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* o
             return fail(it->second, "this scene was refused by the automatic scene check when it was first traced (rtgr_scene_check says why; option scene_check = 0 switches the check off)");
         }
     }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return RTGR_OK;   // (cannot synchronise: unchecked)
+    if (stream_capturing(st)) return RTGR_OK;   // (cannot synchronise: unchecked)
     struct Flag { Flag() { tl_in_scene_check = true; } ~Flag() { tl_in_scene_check = false; } } flag;
     const bool exact = (scene->metric & ~RTGR_METRIC_GENERIC) != RTGR_USER;
     int rc;

@@ -558,6 +558,72 @@ def test_an_animated_long_list_starts_its_tables_over(lib):
     abi.check(lib, lib.rtgr_trim(None))
 
 
+def test_a_captured_long_list_keeps_its_table_when_the_tables_start_over(lib):
+    """The table of a long list that a hipGraph was captured with is marked kept: when the tables start over (above) it stays, and the
+    graph replays the same bits; rtgr_trim frees it with everything else a graph may replay.  The list and the canvas of the test above,
+    Float64, on a side stream: traced once, captured, replayed; then OBJECT_TABLES_MAX + 8 = 520 further lists on the default stream, so
+    the tables start over at least once; the hook (resident, kept) must show that they did and that the captured one was spared."""
+    import torch
+    from raytracegr_jl_amd import sharded
+    from scenes import many_objects
+    hook = lib.rtgr_testhook_object_tables
+    hook.restype = C.c_int
+    hook.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+
+    def tables():
+        resident, kept = C.c_uint32(99), C.c_uint32(99)
+        abi.check(lib, hook(None, 0, C.byref(resident), C.byref(kept)))
+        return resident.value, kept.value
+
+    metric, _, cam = rt.example2_scene()
+    objs = many_objects(40)
+    camera = rt.make_camera(**cam)
+    opt = rt.solver_defaults()
+    ni = nj = 12
+
+    def scene(k):
+        return rt.make_scene(metric, objs + [rt.Sphere((0, 0.0, -400.0 - k, 0.0), (1, 0, 0, 0), 0.5)])   # outside the sky sphere: never seen
+
+    torch.cuda.synchronize()
+    abi.check(lib, lib.rtgr_trim(None))
+    assert tables() == (0, 0)
+    sc = scene(0)
+    side = torch.cuda.Stream()
+    out = {"rgb": torch.zeros((3, ni * nj), dtype=torch.float64, device="cuda"), "hit": torch.zeros(ni * nj, dtype=torch.uint8, device="cuda")}
+    abi.check(lib, lib.rtgr_reserve_workspace(None, out["rgb"].data_ptr(), side.cuda_stream, ni * nj, 0, 0))
+    with torch.cuda.stream(side):
+        eager = sharded.trace_slab_torch(sc, opt, camera, ni, nj, 0, nj, hit_only=True)      # first sight: the table is uploaded
+    torch.cuda.synchronize()
+    eager = {k: v.clone() for k, v in eager.items()}
+    assert len(torch.unique(eager["hit"])) > 4                                              # (the list is on screen)
+    assert tables() == (1, 0)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        sharded.trace_slab_torch(sc, opt, camera, ni, nj, 0, nj, out=out, hit_only=True)
+    assert tables() == (1, 1)
+
+    def replay_equals_eager():
+        out["rgb"].zero_()
+        out["hit"].zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        return torch.equal(out["rgb"], eager["rgb"]) and torch.equal(out["hit"], eager["hit"])
+
+    assert replay_equals_eager()
+    other = {}
+    for k in range(1, 521):
+        sharded.trace_slab_torch(scene(k), opt, camera, ni, nj, 0, nj, out=other, hit_only=True)
+    torch.cuda.synchronize()
+    assert torch.equal(other["rgb"], eager["rgb"]) and torch.equal(other["hit"], eager["hit"])
+    resident, kept = tables()
+    assert kept == 1 and resident < 521, (resident, kept)       # the tables started over, and the captured one was spared
+    assert replay_equals_eager()
+    del g
+    torch.cuda.synchronize()
+    abi.check(lib, lib.rtgr_trim(None))
+    assert tables() == (0, 0)
+
+
 def test_a_long_object_list_over_every_device_of_a_context(lib):
     """The device table of a long list (and its groups) is per device: a three-device context deals the rows of a 64-object scene
     cyclically, every device uploads its own table on first sight, and the canvas equals the single-device one bit for bit — Float64

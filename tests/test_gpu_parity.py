@@ -392,7 +392,7 @@ def test_object_lists_of_any_length_match_oracle(lib, name, n, nobj):
 
 def test_ten_thousand_objects(lib):
     """A list of 10000 small spheres (a cloud around the hole; through rtgr_scene.objects as a packed array): groups of <= 8, runs of
-    ~58 groups (the run length grows with the list: rtgr_context.hip), hit32.  Bit for bit the frames of the pass structures that ask
+    ~58 groups (the run length grows with the list: rtgr_scene_host.hip), hit32.  Bit for bit the frames of the pass structures that ask
     every one of the 10000 at every step, and the wide hit map holds indices beyond 255 and beyond 2^13."""
     rng = np.random.default_rng(21)
     n = 10000

@@ -125,7 +125,7 @@ def test_bench_dump_outputs_whole_frame_or_a_fixed_bounded_sample(tmp_path, monk
         assert np.array_equal(np.load(tmp_path / "s1" / f"{f}.npy"), np.load(tmp_path / "s2" / f"{f}.npy"))
 
 
-# ---- the groups of a long list's spheres (rtgr_context.hip: group_spheres / bounding_sphere; DevScene in rtgr_args.hpp) -------------
+# ---- the groups of a long list's spheres (rtgr_scene_host.hip: group_spheres / bounding_sphere; DevScene in rtgr_args.hpp) -------------
 def _group(spheres, f32=False):
     """spheres: (n, 4) array of centre x, y, z and radius -> (order, nloose, groups[ng, 6]) through the library's test hook"""
     import ctypes as C
