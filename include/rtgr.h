@@ -723,6 +723,94 @@ int rtgr_eval_disk_emission_observer_f32(rtgr_context* ctx, const rtgr_scene* sc
                                          const float* s_end /* n x 8 */, uint64_t n, float* omega /* n */, float* u_emit /* n x 4 */,
                                          float* g /* n */, float* rgb /* n x 3 */);
 
+/* ---- hot-spot light curves: one traced frame reduced over many observer times ---------------------------------------------------
+ * AN EXTENSION.  The emitting scenes are stationary: shifting the camera by tau in coordinate time shifts every ray by tau and changes
+ * nothing else, and a ray's end state carries the coordinate time at which it met the disk (state_end[8 p + 0], relative to the camera's
+ * event; rays are past-directed).  So ONE traced frame determines what the observer sees of a time-dependent emitter at EVERY observer
+ * time.  The emitter with a clock is an rtgr_hot_spot: a compact bright region that rides in the emitting disk of an rtgr_disk_emission.
+ *
+ * The model (csrc/rtgr_lightcurve.hpp restates it; the reduction runs in double for both entry types, Float32 planes promoted on read).
+ *   Rate.   Omega_s = the orbital rate of the disk's own emitter model at the equatorial point (0, rho_s, 0, 0): RTGR_EMIT_KEPLER the root
+ *           emit->orbit names, RTGR_EMIT_RIGID emit->orbit itself — the emission kernel itself, in point mode, on one synthetic pair of
+ *           states: the bits of rtgr_eval_disk_emission_*'s `omega` at an end state with (x, y, z) = (rho_s, 0, 0), in the entry's scalar
+ *           type, then promoted.
+ *   Clock.  The centre at coordinate time t is c(t) = rho_s (cos(phi0 + Omega_s t), sin(phi0 + Omega_s t)); the spot is rigid (no shear).
+ *           Observer sample k is the camera shifted by tau_k = t_start + k dt: pixel p then sees the disk at t_end,p + tau_k.
+ *   Emissivity at pixel p's end point (x_p, y_p), sample k:  d^2 = (x_p - c_x)^2 + (y_p - c_y)^2,
+ *           j = amp max(exp(-d^2 / (2 sigma^2)) - exp(-cut^2 / 2), 0)    (continuous at the cut).
+ *           THE CONTRACT is the expanded form: with theta_p = phi0 + Omega_s t_end,p, beta_k = Omega_s tau_k,
+ *             P0 = (x_p^2 + y_p^2) + rho_s^2,  P1 = -2 rho_s (x_p cos theta_p + y_p sin theta_p),  P2 = -2 rho_s (y_p cos theta_p - x_p sin theta_p),
+ *             d^2 = P0 + (P1 cos beta_k + P2 sin beta_k)   [= rho_p^2 + rho_s^2 - 2 rho_p rho_s cos(gamma_p - beta_k), gamma_p = psi_p - theta_p]
+ *           (its cancellation error is eps rho^2, i.e. eps rho^2 / sigma^2 relative in j), and j = 0 where d^2 >= cut^2 sigma^2.
+ *   Gas.    The gas that emits is the disk's: the pixel's frequency ratio is the g the emission kernel wrote for it (d_g).
+ *   Weight. With the pixel's a = 2 (i + 1/2) / ni - 1, b = 2 (j + 1/2) / nj - 1 (p = i + j ni), t_x = tan(fov_x / 2), t_y = tan(fov_y / 2):
+ *           obs == NULL: w_p = 1;  RTGR_PROJ_PERSPECTIVE: w_p = t_x t_y (2 / ni)(2 / nj) / (1 + a^2 t_x^2 + b^2 t_y^2)^(3/2)  (the solid angle);
+ *           RTGR_PROJ_EQUIRECT: w_p = cos(b fov_y / 2) (fov_x / ni)(fov_y / nj).
+ *   Output. lc: nt x 3 doubles (F_k, A_k, B_k), whatever the scalar type of the planes:
+ *             F_k = sum_p w_p g_p^q j_pk      A_k = sum_p w_p g_p^q j_pk a_p      B_k = sum_p w_p g_p^q j_pk b_p        (q = g_power)
+ *           over the pixels with hit32 == emit->object, g_p finite and > 0 and a finite end point; the image centroid is (A_k / F_k,
+ *           B_k / F_k).  The sums run in pixel order within fixed ranges of pixels and in range order across them, with no floating-point
+ *           atomics: bit-identical from run to run, from stream to stream and — for the traced entries — from one max_batch_rays to another.
+ *   Invalid spot: no circular orbit at rho_s (or a spacelike one), or Omega_s not finite: every entry of lc is NaN and the call still
+ *           returns RTGR_OK (it only enqueues, as an invalid observer frame does).  rtgr_eval_hot_spot_* says so up front.
+ *
+ * rtgr_light_curve_device_*: the reduction alone over planes already on the device — d_hit32 (n), d_state_end (n x 8), d_g (n), from
+ * rtgr_trace_emission_device_* with the plane camera (obs = NULL), rtgr_trace_observer_device_* or the caller.  It only enqueues; its
+ * scratch (grow-only, with the stream's state, retired until rtgr_trim) is at most 24 bytes x min(nt, 1024) x min(ceil(n / 256), 1024)
+ * + 4 KB, so the call may be captured once one call of the same nt and n was made on the stream.
+ * rtgr_trace_light_curve_device_* / rtgr_trace_light_curve_* (host pointers): the arguments of rtgr_trace_observer_* with `emit` required,
+ * plus `spot` and `lc`.  Order of work: the observer trace with emission exactly as rtgr_trace_observer_* does it — d_rgb, d_g, every
+ * per-ray output and the counters are its bits; state_end, hit32 and g go into the caller's planes where given, else into the stream's
+ * scratch — then ONE light-curve stage over the whole frame after the last batch.  The picture is the tau-independent disk: the spot
+ * does not change it.
+ * rtgr_eval_hot_spot_* (blocking, host pointers): omega_s, valid, and j at n triples (x, y, t) (xyt: n x 3; j: n doubles; tau = 0: the
+ * spot as it stands at coordinate time t) from the same device functions as the reduction.  Any output may be NULL.
+ *   RTGR_ERR_BAD_ARG (with a message; lc is left untouched): a null emit, spot, lc or plane; nt = 0 or > 2^20; sigma or cut <= 0 or NaN;
+ * amp < 0 or NaN; a non-finite rho_s, phi0, g_power, t_start or dt; rho_s outside the Disk's [r_in, r_out]; flags or pad != 0; and
+ * everything rtgr_trace_emission_* and rtgr_trace_observer_* refuse (RTGR_USER metrics, 4-D grids, ...).
+ *   Out of scope: a spot that shears, or more than one spot per call; a frame that shows the spot; spectra of the spot; non-stationary
+ * scenes; the sharded, frames-in-flight, pixel-array and single-ray entry points; anti-aliasing. */
+#define RTGR_HOT_SPOT_MAX_SAMPLES (1ull << 20)
+typedef struct rtgr_hot_spot {
+    double rho_s;      /* cylindrical radius of the spot's centre, in the plane z = 0 */
+    double phi0;       /* azimuth of the centre at coordinate time t = 0 */
+    double sigma;      /* Gaussian width, coordinate length in the plane z = 0, > 0 */
+    double cut;        /* support in units of sigma, > 0 (4 is typical) */
+    double amp;        /* emissivity at the centre, >= 0 */
+    double g_power;    /* q in the weight g^q: 4 bolometric, 3 specific intensity of a flat spectrum; finite */
+    double t_start;    /* observer time samples tau_k = t_start + k dt, k = 0 .. nt-1 */
+    double dt;         /* may be 0 or negative; finite */
+    uint64_t nt;       /* 1 .. RTGR_HOT_SPOT_MAX_SAMPLES */
+    uint32_t flags;    /* 0 */
+    uint32_t pad;      /* 0 */
+} rtgr_hot_spot;       /* 80 bytes: rho_s 0, phi0 8, sigma 16, cut 24, amp 32, g_power 40, t_start 48, dt 56, nt 64, flags 72, pad 76 */
+int rtgr_light_curve_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot,
+                                const rtgr_observer* obs /* may be NULL */, uint64_t ni, uint64_t nj, const uint32_t* d_hit32 /* n */,
+                                const double* d_state_end /* n x 8 */, const double* d_g /* n */, double* d_lc /* nt x 3 */, void* stream);
+int rtgr_light_curve_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot,
+                                const rtgr_observer* obs /* may be NULL */, uint64_t ni, uint64_t nj, const uint32_t* d_hit32 /* n */,
+                                const float* d_state_end /* n x 8 */, const float* d_g /* n */, double* d_lc /* nt x 3 */, void* stream);
+int rtgr_trace_light_curve_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                      uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                                      const rtgr_hot_spot* spot, double* d_rgb, const rtgr_ray_outputs* out, double* d_g /* n, may be NULL */,
+                                      double* d_lc /* nt x 3 */, rtgr_counters* ctr, void* stream);
+int rtgr_trace_light_curve_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                      uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                                      const rtgr_hot_spot* spot, float* d_rgb, const rtgr_ray_outputs* out, float* d_g /* n, may be NULL */,
+                                      double* d_lc /* nt x 3 */, rtgr_counters* ctr, void* stream);
+int rtgr_trace_light_curve_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                               uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot,
+                               double* rgb, const rtgr_ray_outputs* out, double* g /* n, may be NULL */, double* lc /* nt x 3 */,
+                               rtgr_counters* ctr);
+int rtgr_trace_light_curve_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                               uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot,
+                               float* rgb, const rtgr_ray_outputs* out, float* g /* n, may be NULL */, double* lc /* nt x 3 */,
+                               rtgr_counters* ctr);
+int rtgr_eval_hot_spot_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot,
+                           const double* xyt /* n x 3 */, uint64_t n, double* omega_s, int* valid, double* j /* n */);
+int rtgr_eval_hot_spot_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot,
+                           const float* xyt /* n x 3 */, uint64_t n, float* omega_s, int* valid, double* j /* n */);
+
 /* ---- camera: make_canvas (src/RayTraceGR.jl:457-478) on the device ------------------------------------------
  * Writes n x 8 ray states (pos, null past-directed 4-velocity) for rows [j0, j1).  Device / host variants. */
 int rtgr_make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni,

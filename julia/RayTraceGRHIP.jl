@@ -32,6 +32,7 @@
 #   RtgrShade        24   nbind 0, flags 4, bind 8, r_escape 16
 #   RtgrDiskEmission 96   object 0, emitter 4, flags 8, pad 12, orbit 16, T_in 24, p 32, gain 40, theta 48, weight 72
 #   RtgrObserver    176   pos 0, vel 32, look 64, up 96, fov_x 128, fov_y 136, orbit 144, kind 152, projection 156, flags 160, pad 164, max_batch_rays 168
+#   RtgrHotSpot      80   rho_s 0, phi0 8, sigma 16, cut 24, amp 32, g_power 40, t_start 48, dt 56, nt 64, flags 72, pad 76
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64          (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -153,6 +154,19 @@ struct RtgrObserver            # a pinhole camera carried by an observer (rtgr_t
     flags::UInt32               # 0
     pad::UInt32                 # 0
     max_batch_rays::UInt64      # rays per batch at most; 0 = default
+end
+struct RtgrHotSpot             # a rigid Gaussian spot riding in the emitting disk, and its observer times (rtgr_trace_light_curve_f64 / _f32)
+    rho_s::Float64              # cylindrical radius of the centre, plane z = 0
+    phi0::Float64               # azimuth of the centre at coordinate time 0
+    sigma::Float64              # Gaussian width
+    cut::Float64                # support in units of sigma
+    amp::Float64                # emissivity at the centre
+    g_power::Float64            # q of the weight g^q
+    t_start::Float64            # tau_k = t_start + k dt
+    dt::Float64
+    nt::UInt64                  # 1 .. 2^20
+    flags::UInt32               # 0
+    pad::UInt32                 # 0
 end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
@@ -943,6 +957,74 @@ function trace_rays_observer(metric, objs, observer::RtgrObserver, ni::Integer, 
         end
     end
     (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), (emission === nothing ? nothing : g)
+end
+
+"""
+    HotSpot(rho_s, sigma; phi0 = 0, cut = 4, amp = 1, g_power = 4, t_start = 0, dt = 1, nt = 1) -> RtgrHotSpot
+
+A rigid Gaussian spot of width `sigma` that rides in the emitting disk at cylindrical radius `rho_s` with the orbital rate of the disk's
+own emitter model, seen at the observer times `t_start + k dt`, `k < nt` (include/rtgr.h "hot-spot light curves").
+"""
+function HotSpot(rho_s::Real, sigma::Real; phi0::Real = 0, cut::Real = 4, amp::Real = 1, g_power::Real = 4, t_start::Real = 0, dt::Real = 1,
+                 nt::Integer = 1)
+    RtgrHotSpot(Float64(rho_s), Float64(phi0), Float64(sigma), Float64(cut), Float64(amp), Float64(g_power), Float64(t_start), Float64(dt),
+                UInt64(nt), UInt32(0), UInt32(0))
+end
+
+# the spot's orbital rate in the disk of `emit` (rtgr_eval_hot_spot_f64/_f32, blocking) — or an error when no valid orbit exists at rho_s
+function eval_hot_spot(scene, emit, spot; T::Type = Float64, ctx = nothing)
+    omega = Ref{T}(T(0))
+    valid = Ref{Cint}(0)
+    if T === Float64
+        check(ccall((:rtgr_eval_hot_spot_f64, librtgr), Cint,
+                    (Ctx, Ptr{RtgrScene}, Ptr{RtgrDiskEmission}, Ptr{RtgrHotSpot}, Ptr{Float64}, UInt64, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}),
+                    handle(ctx), scene, emit, spot, C_NULL, 0, omega, valid, C_NULL))
+    else
+        check(ccall((:rtgr_eval_hot_spot_f32, librtgr), Cint,
+                    (Ctx, Ptr{RtgrScene}, Ptr{RtgrDiskEmission}, Ptr{RtgrHotSpot}, Ptr{Float32}, UInt64, Ptr{Float32}, Ptr{Cint}, Ptr{Float64}),
+                    handle(ctx), scene, emit, spot, C_NULL, 0, omega, valid, C_NULL))
+    end
+    valid[] == 0 && error("HotSpot: no valid circular orbit of the disk's emitter at rho_s (none exists there, or it is not timelike)")
+    omega[]
+end
+
+"""
+    light_curve(metric, objs, observer, ni, nj, emission, spot; T = Float64, ctx = nothing) -> ((R, G, B), g, lc, tau)
+
+The LIGHT CURVE of a hot spot (`rtgr_trace_light_curve_f64/_f32`) — an extension: ONE frame of the emitting disk seen by `observer`, as
+`trace_rays_observer` with `emission`, reduced on the device over the `nt` observer times of `spot` (from `HotSpot`).  `lc` is
+`3 x nt`: the rows F, A, B per observer time `tau[k]`; the image centroid is `(A / F, B / F)` in the pixel coordinates of the frame.  The
+picture is the disk without the spot.  The observer's frame and the spot's orbit are asked for first: either being invalid is an error.
+"""
+function light_curve(metric, objs, observer::RtgrObserver, ni::Integer, nj::Integer, emission::RtgrDiskEmission, spot::RtgrHotSpot;
+                     T::Type = Float64, ctx = nothing)
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("light_curve has no CPU counterpart in the reference: ", why)
+    opt = solver_of(T)
+    obs = Ref(observer)
+    emit = Ref(emission)
+    sp = Ref(spot)
+    observer_frame(scene, obs; T = T, ctx = ctx)
+    eval_hot_spot(scene, emit, sp; T = T, ctx = ctx)
+    rgb = Array{T}(undef, ni, nj, 3)                # plane-major: rgb[:, :, c] is plane c
+    g = Array{T}(undef, ni, nj)
+    lc = Array{Float64}(undef, 3, Int(spot.nt))     # C writes nt x 3 row-major: Julia's 3 x nt
+    ctr = Ref{RtgrCounters}()
+    GC.@preserve rgb g lc begin
+        if T === Float64
+            check(ccall((:rtgr_trace_light_curve_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission}, Ptr{RtgrHotSpot},
+                         Ptr{Float64}, Ptr{RtgrRayOutputs}, Ptr{Float64}, Ptr{Float64}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, emit, sp, pointer(rgb), C_NULL, pointer(g), pointer(lc), ctr))
+        else
+            check(ccall((:rtgr_trace_light_curve_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission}, Ptr{RtgrHotSpot},
+                         Ptr{Float32}, Ptr{RtgrRayOutputs}, Ptr{Float32}, Ptr{Float64}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, emit, sp, pointer(rgb), C_NULL, pointer(g), pointer(lc), ctr))
+        end
+    end
+    tau = [spot.t_start + k * spot.dt for k in 0:Int(spot.nt)-1]
+    (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), g, lc, tau
 end
 
 """

@@ -130,6 +130,13 @@ class rtgr_observer(C.Structure):
                 ("pad", C.c_uint32), ("max_batch_rays", C.c_uint64)]
 
 
+class rtgr_hot_spot(C.Structure):
+    """a rigid Gaussian spot riding in the emitting disk, and the observer times it is seen at (rtgr_light_curve_*): 80 bytes"""
+    _fields_ = [("rho_s", C.c_double), ("phi0", C.c_double), ("sigma", C.c_double), ("cut", C.c_double), ("amp", C.c_double),
+                ("g_power", C.c_double), ("t_start", C.c_double), ("dt", C.c_double), ("nt", C.c_uint64), ("flags", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -160,6 +167,8 @@ EXPORTS = [
     "rtgr_trace_observer_device_f64", "rtgr_trace_observer_device_f32", "rtgr_trace_observer_f64", "rtgr_trace_observer_f32",
     "rtgr_make_observer_canvas_device_f64", "rtgr_make_observer_canvas_device_f32", "rtgr_make_observer_canvas_f64", "rtgr_make_observer_canvas_f32",
     "rtgr_eval_observer_f64", "rtgr_eval_observer_f32", "rtgr_eval_disk_emission_observer_f64", "rtgr_eval_disk_emission_observer_f32",
+    "rtgr_light_curve_device_f64", "rtgr_light_curve_device_f32", "rtgr_trace_light_curve_device_f64", "rtgr_trace_light_curve_device_f32",
+    "rtgr_trace_light_curve_f64", "rtgr_trace_light_curve_f32", "rtgr_eval_hot_spot_f64", "rtgr_eval_hot_spot_f32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -254,6 +263,15 @@ def _declare(lib):
         getattr(lib, f"rtgr_eval_observer_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_observer), vp, vp, P(i32)]
         getattr(lib, f"rtgr_eval_disk_emission_observer_{suf}").argtypes = [
             ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_observer), vp, vp, u64, vp, vp, vp, vp]
+        getattr(lib, f"rtgr_light_curve_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_hot_spot), P(rtgr_observer), u64, u64, vp, vp, vp, vp, vp]
+        getattr(lib, f"rtgr_trace_light_curve_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_hot_spot), vp,
+            P(rtgr_ray_outputs), vp, vp, P(rtgr_counters), vp]
+        getattr(lib, f"rtgr_trace_light_curve_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_hot_spot), vp,
+            P(rtgr_ray_outputs), vp, vp, P(rtgr_counters)]
+        getattr(lib, f"rtgr_eval_hot_spot_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_hot_spot), vp, u64, vp, P(i32), vp]
     lib.rtgr_texture_load.argtypes = [ctx, P(rtgr_texture_desc), vp, P(u64)]
     lib.rtgr_texture_unload.argtypes = [ctx, u64]
     lib.rtgr_eval_fastmath_f64.argtypes = [ctx, vp, u64, vp, vp]

@@ -703,6 +703,56 @@ def trace_observer(metric, objs, observer, ni, nj, emission=None, textures=None,
     return res
 
 
+# ---- hot-spot light curves (include/rtgr.h "hot-spot light curves") ----------------------------------------------------------------
+def HotSpot(rho_s, sigma, t_start=0.0, dt=1.0, nt=1, phi0=0.0, cut=4.0, amp=1.0, g_power=4.0):
+    """A rigid Gaussian spot riding in the emitting disk -> rtgr_hot_spot.  rho_s, phi0: its centre at coordinate time 0 (cylindrical
+    radius and azimuth in the plane z = 0); sigma: its width, cut: its support in units of sigma; amp: the emissivity at the centre;
+    g_power: q of the weight g^q (4 bolometric, 3 the specific intensity of a flat spectrum); the observer times are
+    tau_k = t_start + k dt, k < nt."""
+    return _abi.rtgr_hot_spot(rho_s=float(rho_s), phi0=float(phi0), sigma=float(sigma), cut=float(cut), amp=float(amp), g_power=float(g_power),
+                              t_start=float(t_start), dt=float(dt), nt=int(nt), flags=0, pad=0)
+
+
+def eval_hot_spot(metric, objs, emission, spot, points=None, dtype=np.float64, ctx=None):
+    """rtgr_eval_hot_spot_f64 / _f32: the spot's orbital rate in the disk of `emission` (the emitter model's own, at (rho_s, 0, 0)),
+    whether it is valid, and its emissivity j at `points` [n, 3] = (x, y, t): where the spot stands at coordinate time t.
+    -> dict(omega_s, valid, j [n] (Float64 whatever dtype))."""
+    lib = _lib()
+    sc = make_scene(metric, objs, ctx)
+    pts = np.ascontiguousarray(points if points is not None else np.zeros((0, 3)), dtype=dtype).reshape(-1, 3)
+    n = pts.shape[0]
+    omega, valid, j = np.zeros(1, dtype), C.c_int(0), np.zeros(n, np.float64)
+    fn = lib.rtgr_eval_hot_spot_f64 if dtype == np.float64 else lib.rtgr_eval_hot_spot_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(emission), C.byref(spot), pts.ctypes.data if n else None, n, omega.ctypes.data, C.byref(valid),
+                       j.ctypes.data if n else None))
+    return dict(omega_s=omega[0], valid=bool(valid.value), j=j)
+
+
+def light_curve(metric, objs, observer, ni, nj, emission, spot, textures=None, r_escape=0.0, opt=None, dtype=np.float64, ctx=None, details=False):
+    """The LIGHT CURVE of a hot spot (rtgr_trace_light_curve_f64 / _f32) — an extension: ONE frame of the emitting disk seen by
+    `observer` (as trace_observer with `emission`), reduced on the device over the nt observer times of `spot` (a HotSpot).  The
+    picture is the disk without the spot.  Raises ValueError for an observer with no valid frame and for a spot with no valid orbit.
+    -> dict(rgb [3, ni*nj], g [ni*nj], lc [nt, 3] = (F, A, B) per observer time — the image centroid is (A / F, B / F) in the pixel
+    coordinates a, b in (-1, 1) —, tau [nt], counters; details: + the per-ray outputs)."""
+    lib = _lib()
+    _valid_observer(metric, objs, observer, dtype, ctx)
+    if not eval_hot_spot(metric, objs, emission, spot, None, dtype, ctx)["valid"]:
+        raise ValueError("HotSpot: no valid circular orbit of the disk's emitter at rho_s (none exists there, or it is not timelike)")
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    n = ni * nj
+    sh = make_shade(textures, r_escape) if textures else None
+    res = dict(rgb=np.zeros((3, n), dtype), g=np.zeros(n, dtype), lc=np.zeros((int(spot.nt), 3), np.float64),
+               tau=spot.t_start + np.arange(int(spot.nt), dtype=np.float64) * spot.dt)
+    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
+    ctr = rtgr_counters()
+    fn = lib.rtgr_trace_light_curve_f64 if dtype == np.float64 else lib.rtgr_trace_light_curve_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(observer), ni, nj, None if sh is None else C.byref(sh), C.byref(emission),
+                       C.byref(spot), res["rgb"].ctypes.data, outs, res["g"].ctypes.data, res["lc"].ctypes.data, C.byref(ctr)))
+    res["counters"] = ctr.as_dict()
+    return res
+
+
 def trace_ray(metric, objs, cb, p, opt=None, ctx=None):
     """Legacy single-pixel shape `trace_ray(metric, objs, cb, p)::Pixel` (test/runtests.jl:65-79).
     `cb` is accepted for signature parity and ignored: the callback is always
@@ -812,5 +862,5 @@ def example2(ni=200, nj=200, save=True, ctx=None):
 
 __all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
-           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "dmetric", "christoffel", "geodesic", "example1", "example2",
+           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "HotSpot", "eval_hot_spot", "light_curve", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

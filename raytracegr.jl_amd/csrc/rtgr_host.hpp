@@ -218,6 +218,9 @@ struct StreamState {
     // post-trace kernels read of the sub-rays (rtgr_aa_host.hip), or the ray states of an observer's rows (rtgr_observer_host.hip)
     void* frame = nullptr; size_t frame_bytes = 0;
     void* batch = nullptr; size_t batch_bytes = 0;
+    // scratch of the light-curve calls on this stream (rtgr_lightcurve_host.hip), grow-only and retired likewise: the head (LC_HEAD),
+    // the partial sums of one pass over the time axis, then the planes a traced light curve borrows (end states, hit map, ratio)
+    void* lc = nullptr; size_t lc_bytes = 0;
 };
 
 struct Staging;  // host entry points (rtgr_internal.hpp)
@@ -449,5 +452,39 @@ struct TracedPixels {
     const DevScene<R>* sc = nullptr;      // what the emission kernel reads of the scene and the camera (null where nothing emits;
     const DevCamera<R>* cam = nullptr;    // cam also where state0 is given)
 };
+// hot-spot light curves (rtgr_lightcurve.hip; include/rtgr.h "hot-spot light curves").  The caller's rtgr_hot_spot as the kernels read
+// it, in double whatever the entry's scalar type: inv_2s2 = 1 / (2 sigma²), r2_cut = (cut sigma)², e_cut = exp(-cut² / 2).
+struct LcSpot {
+    double rho_s, phi0, inv_2s2, r2_cut, cut_sigma, e_cut, amp, q, t_start, dt;
+};
+// the pixel weight: proj 0: w = 1 (no observer); 1: perspective, hx, hy = tan(fov / 2), scale = hx hy (2 / ni)(2 / nj); 2: equirectangular,
+// hy = fov_y / 2, scale = (fov_x / ni)(fov_y / nj)
+struct LcWeight {
+    uint32_t proj, pad;
+    double hx, hy, scale;
+};
+// the planes of a traced frame the reduction reads: n = ni nj pixels, `object` what hit32 holds on the emitting disk
+template <class R>
+struct LcPlanes {
+    const uint32_t* hit32;
+    const R* state_end;
+    const R* g;
+    uint64_t n, ni, nj;
+    uint32_t object, pad;
+};
+// The head of a stream's light-curve scratch (LC_HEAD bytes): the synthetic pair of states and the synthetic observer record the emission
+// kernel evaluates in point mode, and the Omega_s it writes (scalar type R), at these offsets.  Behind it: the partial sums.
+constexpr size_t LC_HEAD = 1024, LC_HEAD_S0 = 0, LC_HEAD_SE = 64, LC_HEAD_OMEGA = 128, LC_HEAD_FRAME = 256;
+static_assert(LC_HEAD_FRAME + sizeof(ObsFrame<double>) <= LC_HEAD, "the head holds the record");
+size_t lc_partial_bytes(uint64_t n, uint64_t nt);   // what lc_reduce_launch needs behind the head for n pixels and nt samples
+// the states and the record for a spot at rho_s into the head (one wave) …
+template <class R> int lc_seed_launch(R rho_s, char* d_head, hipStream_t st);
+// … the reduction: nt x 3 doubles into d_lc, pass by pass over the time axis — the partial sums of a pass in d_partial, then their sum in
+// range order (NaN everywhere when the head's Omega_s is not finite) …
+template <class R>
+int lc_reduce_launch(const LcPlanes<R>& P, const LcSpot& S, const LcWeight& W, uint64_t nt, const char* d_head, double* d_partial, double* d_lc,
+                     hipStream_t st);
+// … and the hook: j at n triples (x, y, t), from the same device functions
+template <class R> int lc_points_launch(const R* d_xyt, uint64_t n, const LcSpot& S, const char* d_head, double* d_j, hipStream_t st);
 
 }  // namespace rtgr

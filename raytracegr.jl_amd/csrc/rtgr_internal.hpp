@@ -20,6 +20,8 @@
 //                           (kernels: rtgr_emit.hip)
 //   rtgr_observer_host.hip  the observer camera: the checks of an rtgr_observer, the observer trace (the frame and ray kernels + a plain trace of
 //                           their states, batch by batch, + the post-trace stage), the canvas and frame hooks (kernels: rtgr_observer.hip)
+//   rtgr_lightcurve_host.hip  hot-spot light curves: the checks of an rtgr_hot_spot, the stream's light-curve scratch, the stage (Omega_s from the
+//                           emission kernel in point mode, then the reduction), the traced light curve, the hook (kernels: rtgr_lightcurve.hip)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -396,6 +398,10 @@ template <class R> int trace_observer(rtgr_context* ctx, const rtgr_scene* scene
 template <class R> int make_observer_canvas_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* d_state0, void* stream);
 template <class R> int make_observer_canvas(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1, R* state0);
 template <class R> int eval_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, R* frame, R* omega, int* valid);
+template <class R> int light_curve_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const uint32_t* d_hit32, const R* d_state_end, const R* d_g, double* d_lc, void* stream);
+template <class R> int trace_light_curve_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, double* d_lc, rtgr_counters* ctr, void* stream);
+template <class R> int trace_light_curve(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot, R* rgb, const rtgr_ray_outputs* out, R* g, double* lc, rtgr_counters* ctr);
+template <class R> int eval_hot_spot(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot, const R* xyt, uint64_t n, R* omega_s, int* valid, double* j);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 
