@@ -811,6 +811,94 @@ int rtgr_eval_hot_spot_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtg
 int rtgr_eval_hot_spot_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot,
                            const float* xyt /* n x 3 */, uint64_t n, float* omega_s, int* valid, double* j /* n */);
 
+/* ---- disk spectra: line profiles and thermal spectra from one traced frame --------------------------------------------------------
+ * AN EXTENSION.  The traced frame of an emitting disk — hit32, state_end and the frequency ratio g the emission kernel wrote — holds
+ * everything a SPECTRUM of the disk needs: the broadened, skewed profile of a narrow emission line is the flux-weighted histogram of g
+ * over the disk's image, and the spectrum of the multi-colour black-body disk is the picture's own Planck law summed over the image at
+ * many frequencies instead of three.  One small deterministic stage over the disk's pixels, as the light curve's.
+ *
+ * The model (csrc/rtgr_spectrum.hpp restates it).  Everything runs in double; Float32 planes are promoted on read.
+ *   Pixel set.  A pixel p takes part iff hit32[p] == emit->object, g_p is finite and > 0, (x_p, y_p) from state_end is finite, and the
+ *           mode's own condition below holds.  rho_p = sqrt(x_p^2 + y_p^2).
+ *   Pixel terms.  w_p, a_p, b_p are the light curve's (its "Weight" above: the same device function); obs == NULL: w_p = 1.
+ *   RTGR_SPEC_LINE.  The axis is the frequency ratio g itself — a line of rest energy 1 — with nb bins over [lo, hi); 0 <= lo < hi.
+ *           s = (double)nb / (hi - lo), computed once on the host;  u = (g_p - lo) * s  (a subtraction, then a multiply: nothing to fuse).
+ *           The pixel counts iff 0 <= u < nb and rho_min <= rho_p < rho_max; its bin is b = (uint64)u.
+ *           W_p = amp w_p (rho_p / rho_min)^(-alpha) g_p^g_power   (a power-law emissivity; g_power 3: the specific intensity of a line,
+ *           4: its flux per unit g).  Output nb x 3 doubles: F_b = sum W_p, A_b = sum W_p a_p, B_b = sum W_p b_p over the pixels of
+ *           bin b — plain additions; the flux centroid per energy is (A_b / F_b, B_b / F_b).
+ *   RTGR_SPEC_THERMAL.  nb sample frequencies theta_k in the units of emit->theta; 0 < lo <= hi; rho_min, rho_max, alpha, amp and
+ *           g_power must be 0.  theta_k = lo + k (hi - lo) / (nb - 1); with RTGR_SPEC_LOG theta_k = lo exp(k log(hi / lo) / (nb - 1));
+ *           nb = 1: theta_0 = lo.  T_p = the emission record's temperature law at rho_p ("disk emission" above: the same device
+ *           function); the pixel counts iff T_p > 0.  tau_p = 1 / (g_p T_p).
+ *           F_k = c_k sum_p w_p / expm1(theta_k tau_p), A_k and B_k likewise with w_p a_p and w_p b_p, accumulated as fma(W, e, F);
+ *           c_k = emit->gain, or emit->gain theta_k^3 with RTGR_SPEC_NU3 (the flux density F_nu up to a constant), applied once, after
+ *           the sum.  So without RTGR_SPEC_NU3, weight_c F(theta = theta_c) is the w-weighted sum of the picture's channel c over the disk.
+ *   Order of operations, both modes: pixel order within a fixed range of pixels, then range order across the ranges; the ranges depend
+ *           on n = ni nj only (the light curve's).  No floating-point atomics, no cross-lane reduction: bit-identical from run to run,
+ *           from stream to stream and — for the traced entries — from one max_batch_rays to another.
+ *
+ * rtgr_spectrum_device_*: the stage alone over planes already on the device (d_hit32: n, d_state_end: n x 8, d_g: n, as for
+ * rtgr_light_curve_device_*); d_out: nb x 3 doubles.  It only enqueues; its scratch is the stream's light-curve scratch (at most
+ * 24 bytes x min(nb, 1024) x min(ceil(n / 256), 1024), grow-only, retired until rtgr_trim), so the call may be captured once a call
+ * of that size was made on the stream.
+ * rtgr_trace_spectrum_device_* / rtgr_trace_spectrum_* (host pointers): the arguments of rtgr_trace_observer_* with `emit` required,
+ * plus `spec` and the output.  rgb, g, every per-ray output and the counters are rtgr_trace_observer_*'s bit for bit; then ONE stage
+ * runs over the whole frame after the last batch.  Planes the caller did not give are borrowed from the stream's scratch.
+ * rtgr_eval_spectrum_* (blocking, host pointers), from the reduction's own device functions: xyg: n x 3 = (x, y, g);
+ * axis: nb doubles — LINE the bin centres lo + (b + 1/2)(hi - lo) / nb, THERMAL theta_k; bin: n int64 — LINE the bin of the point or
+ * -1 where it does not count, THERMAL 0 or -1; val: LINE n doubles amp (rho / rho_min)^(-alpha) g^g_power, THERMAL n x nb doubles
+ * c_k / expm1(theta_k tau); 0 where the point does not count.  n nb > 2^26 is refused.  Any output may be NULL.
+ *   RTGR_ERR_BAD_ARG (with a message; the output is left untouched): a null spec, plane or output; nb = 0 or > RTGR_SPECTRUM_MAX_BINS;
+ * an unknown kind or flags; reserved != 0; a non-finite field; LINE: RTGR_SPEC_LOG or RTGR_SPEC_NU3, amp < 0, rho_min or rho_max outside
+ * the Disk's [r_in, r_out], rho_min >= rho_max, rho_min <= 0, lo < 0, lo >= hi; THERMAL: lo <= 0, lo > hi, a non-zero line-only field
+ * (amp, alpha, rho_min, rho_max, g_power); and everything rtgr_trace_emission_* and rtgr_trace_observer_* refuse (RTGR_USER metrics,
+ * 4-D grids, ...).
+ *   Out of scope: spectra of the hot spot; line emissivity other than a power law; limb darkening; a colour-matching integral; linear
+ * (two-bin) deposit; anti-aliasing; the sharded, frames-in-flight, pixel-array and single-ray entry points. */
+enum rtgr_spectrum_kind { RTGR_SPEC_LINE = 0, RTGR_SPEC_THERMAL = 1 };
+#define RTGR_SPEC_LOG 1u
+#define RTGR_SPEC_NU3 2u
+#define RTGR_SPECTRUM_MAX_BINS (1ull << 16)
+typedef struct rtgr_spectrum {
+    uint32_t kind;     /* rtgr_spectrum_kind */
+    uint32_t flags;    /* 0 | RTGR_SPEC_LOG | RTGR_SPEC_NU3 (THERMAL only) */
+    uint64_t nb;       /* bins (LINE) or sample frequencies (THERMAL): 1 .. RTGR_SPECTRUM_MAX_BINS */
+    double lo, hi;     /* LINE: the bins cover [lo, hi) of g; THERMAL: theta_0 = lo, theta_(nb-1) = hi */
+    double amp;        /* LINE: emissivity at rho_min, >= 0 */
+    double alpha;      /* LINE: emissivity index, (rho / rho_min)^(-alpha) */
+    double rho_min;    /* LINE: the window rho_min <= rho < rho_max, inside the Disk's [r_in, r_out] */
+    double rho_max;
+    double g_power;    /* LINE: q of the weight g^q */
+    double reserved;   /* 0 */
+} rtgr_spectrum;       /* 80 bytes: kind 0, flags 4, nb 8, lo 16, hi 24, amp 32, alpha 40, rho_min 48, rho_max 56, g_power 64, reserved 72 */
+int rtgr_spectrum_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_spectrum* spec,
+                             const rtgr_observer* obs /* may be NULL */, uint64_t ni, uint64_t nj, const uint32_t* d_hit32 /* n */,
+                             const double* d_state_end /* n x 8 */, const double* d_g /* n */, double* d_out /* nb x 3 */, void* stream);
+int rtgr_spectrum_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_spectrum* spec,
+                             const rtgr_observer* obs /* may be NULL */, uint64_t ni, uint64_t nj, const uint32_t* d_hit32 /* n */,
+                             const float* d_state_end /* n x 8 */, const float* d_g /* n */, double* d_out /* nb x 3 */, void* stream);
+int rtgr_trace_spectrum_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                   uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                                   const rtgr_spectrum* spec, double* d_rgb, const rtgr_ray_outputs* out, double* d_g /* n, may be NULL */,
+                                   double* d_out /* nb x 3 */, rtgr_counters* ctr, void* stream);
+int rtgr_trace_spectrum_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                   uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                                   const rtgr_spectrum* spec, float* d_rgb, const rtgr_ray_outputs* out, float* d_g /* n, may be NULL */,
+                                   double* d_out /* nb x 3 */, rtgr_counters* ctr, void* stream);
+int rtgr_trace_spectrum_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                            uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit, const rtgr_spectrum* spec,
+                            double* rgb, const rtgr_ray_outputs* out, double* g /* n, may be NULL */, double* spectrum /* nb x 3 */,
+                            rtgr_counters* ctr);
+int rtgr_trace_spectrum_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                            uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit, const rtgr_spectrum* spec,
+                            float* rgb, const rtgr_ray_outputs* out, float* g /* n, may be NULL */, double* spectrum /* nb x 3 */,
+                            rtgr_counters* ctr);
+int rtgr_eval_spectrum_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_spectrum* spec,
+                           const double* xyg /* n x 3 */, uint64_t n, double* axis /* nb */, int64_t* bin /* n */, double* val);
+int rtgr_eval_spectrum_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_spectrum* spec,
+                           const float* xyg /* n x 3 */, uint64_t n, double* axis /* nb */, int64_t* bin /* n */, double* val);
+
 /* ---- camera: make_canvas (src/RayTraceGR.jl:457-478) on the device ------------------------------------------
  * Writes n x 8 ray states (pos, null past-directed 4-velocity) for rows [j0, j1).  Device / host variants. */
 int rtgr_make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni,

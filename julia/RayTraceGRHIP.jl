@@ -33,7 +33,8 @@
 #   RtgrDiskEmission 96   object 0, emitter 4, flags 8, pad 12, orbit 16, T_in 24, p 32, gain 40, theta 48, weight 72
 #   RtgrObserver    176   pos 0, vel 32, look 64, up 96, fov_x 128, fov_y 136, orbit 144, kind 152, projection 156, flags 160, pad 164, max_batch_rays 168
 #   RtgrHotSpot      80   rho_s 0, phi0 8, sigma 16, cut 24, amp 32, g_power 40, t_start 48, dt 56, nt 64, flags 72, pad 76
-#   Pixel{Float64}   88   pos 0, normal 32, rgb 64          (the reference's own type, src/RayTraceGR.jl:446-450)
+#   RtgrSpectrum     80   kind 0, flags 4, nb 8, lo 16, hi 24, amp 32, alpha 40, rho_min 48, rho_max 56, g_power 64, reserved 72
+#   Pixel{Float64}   88   pos 0, normal 32, rgb 64         (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
 # It is a thin `ccall` layer; host code stays Julia, the metric/object/Pixel signatures of the reference are preserved,
@@ -168,6 +169,19 @@ struct RtgrHotSpot             # a rigid Gaussian spot riding in the emitting di
     flags::UInt32               # 0
     pad::UInt32                 # 0
 end
+struct RtgrSpectrum            # a line profile or a thermal spectrum of the emitting disk (rtgr_trace_spectrum_f64 / _f32)
+    kind::UInt32                # RTGR_SPEC_LINE / RTGR_SPEC_THERMAL
+    flags::UInt32               # 0 | RTGR_SPEC_LOG | RTGR_SPEC_NU3 (thermal only)
+    nb::UInt64                  # bins (line) or sample frequencies (thermal): 1 .. 2^16
+    lo::Float64                 # line: the bins cover [lo, hi) of g; thermal: theta_0 = lo, theta_(nb-1) = hi
+    hi::Float64
+    amp::Float64                # line: emissivity at rho_min
+    alpha::Float64              # line: (rho / rho_min)^(-alpha)
+    rho_min::Float64            # line: the window rho_min <= rho < rho_max
+    rho_max::Float64
+    g_power::Float64            # line: q of the weight g^q
+    reserved::Float64           # 0
+end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
     lambda_end::Ptr{Cvoid}
@@ -206,6 +220,10 @@ const RTGR_OBS_VELOCITY = UInt32(1)
 const RTGR_OBS_CIRCULAR = UInt32(2)
 const RTGR_PROJ_PERSPECTIVE = UInt32(0)
 const RTGR_PROJ_EQUIRECT = UInt32(1)
+const RTGR_SPEC_LINE = UInt32(0)
+const RTGR_SPEC_THERMAL = UInt32(1)
+const RTGR_SPEC_LOG = UInt32(1)
+const RTGR_SPEC_NU3 = UInt32(2)
 
 function check(rc)
     rc < 0 && error("librtgr_hip: ", unsafe_string(ccall((:rtgr_last_error, librtgr), Cstring, ())))
@@ -1025,6 +1043,80 @@ function light_curve(metric, objs, observer::RtgrObserver, ni::Integer, nj::Inte
     end
     tau = [spot.t_start + k * spot.dt for k in 0:Int(spot.nt)-1]
     (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), g, lc, tau
+end
+
+"""
+    Spectrum(kind, lo, hi, nb; amp = 1, alpha = 0, rho_min = 0, rho_max = 0, g_power = 4, log_axis = false, nu3 = false) -> RtgrSpectrum
+
+A spectrum of the emitting disk (include/rtgr.h "disk spectra").  `kind = RTGR_SPEC_LINE`: the profile of a narrow line of rest energy 1,
+`nb` bins over `[lo, hi)` of the frequency ratio g, emissivity `amp (rho / rho_min)^(-alpha)` inside `rho_min <= rho < rho_max`, weight
+`g^g_power`.  `kind = RTGR_SPEC_THERMAL`: the black-body disk at `nb` sample frequencies theta_k from `lo` to `hi` (the units of the
+emission's theta), linear or — `log_axis` — geometric; `nu3` multiplies sample k by theta_k^3.  The line-only fields are sent as 0 then.
+"""
+function Spectrum(kind::UInt32, lo::Real, hi::Real, nb::Integer; amp::Real = 1, alpha::Real = 0, rho_min::Real = 0, rho_max::Real = 0,
+                  g_power::Real = 4, log_axis::Bool = false, nu3::Bool = false)
+    if kind == RTGR_SPEC_THERMAL
+        return RtgrSpectrum(kind, (log_axis ? RTGR_SPEC_LOG : UInt32(0)) | (nu3 ? RTGR_SPEC_NU3 : UInt32(0)), UInt64(nb), Float64(lo), Float64(hi),
+                            0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+    end
+    RtgrSpectrum(kind, UInt32(0), UInt64(nb), Float64(lo), Float64(hi), Float64(amp), Float64(alpha), Float64(rho_min), Float64(rho_max),
+                 Float64(g_power), 0.0)
+end
+
+# the spectral axis of `spec` in the disk of `emit` (rtgr_eval_spectrum_f64/_f32, blocking, no points): the bin centres of a line
+# profile, the sample frequencies of a thermal spectrum — and every refusal of the record, before anything is traced
+function eval_spectrum(scene, emit, spec; T::Type = Float64, ctx = nothing)
+    axis = Array{Float64}(undef, Int(spec[].nb))
+    GC.@preserve axis begin
+        if T === Float64
+            check(ccall((:rtgr_eval_spectrum_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrDiskEmission}, Ptr{RtgrSpectrum}, Ptr{Float64}, UInt64, Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}),
+                        handle(ctx), scene, emit, spec, C_NULL, 0, pointer(axis), C_NULL, C_NULL))
+        else
+            check(ccall((:rtgr_eval_spectrum_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrDiskEmission}, Ptr{RtgrSpectrum}, Ptr{Float32}, UInt64, Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}),
+                        handle(ctx), scene, emit, spec, C_NULL, 0, pointer(axis), C_NULL, C_NULL))
+        end
+    end
+    axis
+end
+
+"""
+    spectrum(metric, objs, observer, ni, nj, emission, spec; T = Float64, ctx = nothing) -> ((R, G, B), g, axis, fab)
+
+The SPECTRUM of an emitting disk (`rtgr_trace_spectrum_f64/_f32`) — an extension: ONE frame of the disk seen by `observer`, as
+`trace_rays_observer` with `emission`, reduced on the device to the line profile or the thermal spectrum `spec` names (from `Spectrum`).
+`fab` is `3 x nb`: the rows F, A, B per bin or sample of `axis`; the flux centroid there is `(A / F, B / F)` in the pixel coordinates of
+the frame.  The observer's frame and the record are asked for first: an invalid frame or a refused record is an error.
+"""
+function spectrum(metric, objs, observer::RtgrObserver, ni::Integer, nj::Integer, emission::RtgrDiskEmission, spec::RtgrSpectrum;
+                  T::Type = Float64, ctx = nothing)
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("spectrum has no CPU counterpart in the reference: ", why)
+    opt = solver_of(T)
+    obs = Ref(observer)
+    emit = Ref(emission)
+    sp = Ref(spec)
+    observer_frame(scene, obs; T = T, ctx = ctx)
+    axis = eval_spectrum(scene, emit, sp; T = T, ctx = ctx)
+    rgb = Array{T}(undef, ni, nj, 3)                # plane-major: rgb[:, :, c] is plane c
+    g = Array{T}(undef, ni, nj)
+    fab = Array{Float64}(undef, 3, Int(spec.nb))    # C writes nb x 3 row-major: Julia's 3 x nb
+    ctr = Ref{RtgrCounters}()
+    GC.@preserve rgb g fab begin
+        if T === Float64
+            check(ccall((:rtgr_trace_spectrum_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission}, Ptr{RtgrSpectrum},
+                         Ptr{Float64}, Ptr{RtgrRayOutputs}, Ptr{Float64}, Ptr{Float64}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, emit, sp, pointer(rgb), C_NULL, pointer(g), pointer(fab), ctr))
+        else
+            check(ccall((:rtgr_trace_spectrum_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission}, Ptr{RtgrSpectrum},
+                         Ptr{Float32}, Ptr{RtgrRayOutputs}, Ptr{Float32}, Ptr{Float64}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, emit, sp, pointer(rgb), C_NULL, pointer(g), pointer(fab), ctr))
+        end
+    end
+    (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), g, axis, fab
 end
 
 """

@@ -31,6 +31,10 @@ EMIT_INNER_EDGE = 1
 # enum rtgr_observer_kind, enum rtgr_projection
 OBS_STATIC, OBS_VELOCITY, OBS_CIRCULAR = 0, 1, 2
 PROJ_PERSPECTIVE, PROJ_EQUIRECT = 0, 1
+# enum rtgr_spectrum_kind, the flags of rtgr_spectrum.flags, and the limit of rtgr_spectrum.nb
+SPEC_LINE, SPEC_THERMAL = 0, 1
+SPEC_LOG, SPEC_NU3 = 1, 2
+RTGR_SPECTRUM_MAX_BINS = 1 << 16
 # enum rtgr_status
 OK, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NAN_INPUT, ERR_NOT_INIT = 0, -1, -2, -3, -4, -5
 
@@ -137,6 +141,15 @@ class rtgr_hot_spot(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+class rtgr_spectrum(C.Structure):
+    """a line profile or a thermal spectrum of the emitting disk (rtgr_spectrum_*): 80 bytes"""
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("nb", C.c_uint64), ("lo", C.c_double), ("hi", C.c_double), ("amp", C.c_double),
+                ("alpha", C.c_double), ("rho_min", C.c_double), ("rho_max", C.c_double), ("g_power", C.c_double), ("reserved", C.c_double)]
+
+
+RtgrSpectrum = rtgr_spectrum
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -169,6 +182,8 @@ EXPORTS = [
     "rtgr_eval_observer_f64", "rtgr_eval_observer_f32", "rtgr_eval_disk_emission_observer_f64", "rtgr_eval_disk_emission_observer_f32",
     "rtgr_light_curve_device_f64", "rtgr_light_curve_device_f32", "rtgr_trace_light_curve_device_f64", "rtgr_trace_light_curve_device_f32",
     "rtgr_trace_light_curve_f64", "rtgr_trace_light_curve_f32", "rtgr_eval_hot_spot_f64", "rtgr_eval_hot_spot_f32",
+    "rtgr_spectrum_device_f64", "rtgr_spectrum_device_f32", "rtgr_trace_spectrum_device_f64", "rtgr_trace_spectrum_device_f32",
+    "rtgr_trace_spectrum_f64", "rtgr_trace_spectrum_f32", "rtgr_eval_spectrum_f64", "rtgr_eval_spectrum_f32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -272,6 +287,15 @@ def _declare(lib):
             ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_hot_spot), vp,
             P(rtgr_ray_outputs), vp, vp, P(rtgr_counters)]
         getattr(lib, f"rtgr_eval_hot_spot_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_hot_spot), vp, u64, vp, P(i32), vp]
+        getattr(lib, f"rtgr_spectrum_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_spectrum), P(rtgr_observer), u64, u64, vp, vp, vp, vp, vp]
+        getattr(lib, f"rtgr_trace_spectrum_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_spectrum), vp,
+            P(rtgr_ray_outputs), vp, vp, P(rtgr_counters), vp]
+        getattr(lib, f"rtgr_trace_spectrum_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_spectrum), vp,
+            P(rtgr_ray_outputs), vp, vp, P(rtgr_counters)]
+        getattr(lib, f"rtgr_eval_spectrum_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_spectrum), vp, u64, vp, vp, vp]
     lib.rtgr_texture_load.argtypes = [ctx, P(rtgr_texture_desc), vp, P(u64)]
     lib.rtgr_texture_unload.argtypes = [ctx, u64]
     lib.rtgr_eval_fastmath_f64.argtypes = [ctx, vp, u64, vp, vp]

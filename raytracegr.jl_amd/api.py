@@ -753,6 +753,63 @@ def light_curve(metric, objs, observer, ni, nj, emission, spot, textures=None, r
     return res
 
 
+# ---- disk spectra (include/rtgr.h "disk spectra") ------------------------------------------------------------------------------------
+def Spectrum(kind, lo, hi, nb, amp=None, alpha=0.0, rho_min=0.0, rho_max=0.0, g_power=None, log=False, nu3=False):
+    """A line profile or a thermal spectrum of the emitting disk -> rtgr_spectrum.  kind "line": nb bins over [lo, hi) of the frequency
+    ratio g (a line of rest energy 1), emissivity amp (rho / rho_min)^(-alpha) inside the window rho_min <= rho < rho_max, weight g^g_power
+    (amp defaults to 1, g_power to 4).  kind "thermal": nb sample frequencies theta_k from lo to hi in the units of DiskEmission's theta
+    (h nu / k_B in kelvin), spaced linearly or, log=True, geometrically; nu3=True multiplies sample k by theta_k^3 (F_nu up to a constant)."""
+    kinds = {"line": _abi.SPEC_LINE, "thermal": _abi.SPEC_THERMAL}
+    if kind not in kinds:
+        raise ValueError(f"Spectrum: kind must be 'line' or 'thermal', got {kind!r}")
+    line = kind == "line"
+    return _abi.rtgr_spectrum(kind=kinds[kind], flags=(_abi.SPEC_LOG if log else 0) | (_abi.SPEC_NU3 if nu3 else 0), nb=int(nb), lo=float(lo), hi=float(hi),
+                              amp=float((1.0 if line else 0.0) if amp is None else amp), alpha=float(alpha), rho_min=float(rho_min), rho_max=float(rho_max),
+                              g_power=float((4.0 if line else 0.0) if g_power is None else g_power), reserved=0.0)
+
+
+def eval_spectrum(metric, objs, emission, spec, points=None, dtype=np.float64, ctx=None):
+    """rtgr_eval_spectrum_f64 / _f32: the spectral axis of `spec` (a Spectrum) and, at `points` [n, 3] = (x, y, g), what the reduction
+    makes of a pixel that ends there.  -> dict(axis [nb] (line: the bin centres; thermal: theta_k), bin [n] (line: the bin, -1 where the
+    point does not count; thermal: 0 or -1), val (line [n]: amp (rho / rho_min)^(-alpha) g^g_power; thermal [n, nb]: c_k / expm1(theta_k tau);
+    0 where the point does not count)); Float64 whatever dtype."""
+    lib = _lib()
+    sc = make_scene(metric, objs, ctx)
+    pts = np.ascontiguousarray(points if points is not None else np.zeros((0, 3)), dtype=dtype).reshape(-1, 3)
+    n, nb = pts.shape[0], int(spec.nb)
+    thermal = spec.kind == _abi.SPEC_THERMAL
+    axis, bins = np.zeros(max(nb, 0), np.float64), np.zeros(n, np.int64)
+    val = np.zeros((n, nb) if thermal else n, np.float64)
+    fn = lib.rtgr_eval_spectrum_f64 if dtype == np.float64 else lib.rtgr_eval_spectrum_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(emission), C.byref(spec), pts.ctypes.data if n else None, n, axis.ctypes.data if nb else None,
+                       bins.ctypes.data if n else None, val.ctypes.data if val.size else None))
+    return dict(axis=axis, bin=bins, val=val)
+
+
+def spectrum(metric, objs, observer, ni, nj, emission, spec, textures=None, r_escape=0.0, opt=None, dtype=np.float64, ctx=None, details=False):
+    """The SPECTRUM of an emitting disk (rtgr_trace_spectrum_f64 / _f32) — an extension: ONE frame of the disk seen by `observer` (as
+    trace_observer with `emission`), reduced on the device to the line profile or the thermal spectrum `spec` (a Spectrum) names.
+    Raises ValueError for an observer with no valid frame.  -> dict(rgb [3, ni*nj], g [ni*nj], axis [nb], F [nb], A [nb], B [nb] — the
+    flux centroid per bin or sample is (A / F, B / F) in the pixel coordinates a, b in (-1, 1) —, counters; details: + the per-ray outputs)."""
+    lib = _lib()
+    _valid_observer(metric, objs, observer, dtype, ctx)
+    axis = eval_spectrum(metric, objs, emission, spec, None, dtype, ctx)["axis"]
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    n = ni * nj
+    sh = make_shade(textures, r_escape) if textures else None
+    res = dict(rgb=np.zeros((3, n), dtype), g=np.zeros(n, dtype))
+    out = np.zeros((int(spec.nb), 3), np.float64)
+    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
+    ctr = rtgr_counters()
+    fn = lib.rtgr_trace_spectrum_f64 if dtype == np.float64 else lib.rtgr_trace_spectrum_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(observer), ni, nj, None if sh is None else C.byref(sh), C.byref(emission),
+                       C.byref(spec), res["rgb"].ctypes.data, outs, res["g"].ctypes.data, out.ctypes.data, C.byref(ctr)))
+    res.update(axis=axis, F=out[:, 0].copy(), A=out[:, 1].copy(), B=out[:, 2].copy())
+    res["counters"] = ctr.as_dict()
+    return res
+
+
 def trace_ray(metric, objs, cb, p, opt=None, ctx=None):
     """Legacy single-pixel shape `trace_ray(metric, objs, cb, p)::Pixel` (test/runtests.jl:65-79).
     `cb` is accepted for signature parity and ignored: the callback is always
@@ -862,5 +919,5 @@ def example2(ni=200, nj=200, save=True, ctx=None):
 
 __all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
-           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "HotSpot", "eval_hot_spot", "light_curve", "dmetric", "christoffel", "geodesic", "example1", "example2",
+           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "HotSpot", "eval_hot_spot", "light_curve", "Spectrum", "eval_spectrum", "spectrum", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

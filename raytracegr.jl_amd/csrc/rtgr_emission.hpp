@@ -73,6 +73,20 @@ RTGR_DEV R circular_orbit_rate(const DevScene<R>& sc, R t, R x, R y, R orbit, bo
     return (orbit * rsqrt_(disc) - B) / C;   // (orbit = ±1 picks the root)
 }
 
+// The temperature law of the model above at cylindrical radius rho.  ONE function for the picture (disk_emission) and for the disk's
+// thermal spectrum (rtgr_spectrum.hpp, in double); no operation is fused.
+template <class R>
+RTGR_DEV R emission_temperature(const DevEmission<R>& E, R rho) {
+#pragma clang fp contract(off)
+    R T = E.T_in * rpow<R>(rho / E.r_in, -E.p);
+    if (E.flags & RTGR_EMIT_INNER_EDGE) {
+        R edge = R(1) - rsqrt_(E.r_in / rho);
+        edge = edge > R(0) ? edge : R(0);
+        T = T * rsqrt_(rsqrt_(edge));
+    }
+    return T;
+}
+
 // The model above at one pair of states.  Returns whether the emitter is valid (and the frequency ratio finite); omega, uem, gred and
 // rgb are always written.  obs (may be null): the frame of an observer camera (rtgr_observer.hpp) — u_obs is then its e_0 instead of
 // the static observer at x_0.
@@ -112,12 +126,7 @@ RTGR_DEV bool disk_emission(const DevScene<R>& sc, const DevEmission<R>& E, cons
     }
     omega = Om;
     const R rho = rhypot<R>(x, y);
-    R T = E.T_in * rpow<R>(rho / E.r_in, -E.p);
-    if (E.flags & RTGR_EMIT_INNER_EDGE) {
-        R edge = R(1) - rsqrt_(E.r_in / rho);
-        edge = edge > R(0) ? edge : R(0);
-        T = T * rsqrt_(rsqrt_(edge));
-    }
+    const R T = emission_temperature<R>(E, rho);
     if (!(gr > R(0)) || !(T > R(0))) { gred = nan; return true; }
     gred = gr;
     const R gT = gr * T;

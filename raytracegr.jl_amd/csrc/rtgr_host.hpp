@@ -219,7 +219,8 @@ struct StreamState {
     void* frame = nullptr; size_t frame_bytes = 0;
     void* batch = nullptr; size_t batch_bytes = 0;
     // scratch of the light-curve calls on this stream (rtgr_lightcurve_host.hip), grow-only and retired likewise: the head (LC_HEAD),
-    // the partial sums of one pass over the time axis, then the planes a traced light curve borrows (end states, hit map, ratio)
+    // the partial sums of one pass over the time axis, then the planes a traced light curve borrows (end states, hit map, ratio).  The
+    // disk spectra (rtgr_spectrum_host.hip) use the same buffer — the two stages are ordered on the stream —, with no head
     void* lc = nullptr; size_t lc_bytes = 0;
 };
 
@@ -486,5 +487,23 @@ int lc_reduce_launch(const LcPlanes<R>& P, const LcSpot& S, const LcWeight& W, u
                      hipStream_t st);
 // … and the hook: j at n triples (x, y, t), from the same device functions
 template <class R> int lc_points_launch(const R* d_xyt, uint64_t n, const LcSpot& S, const char* d_head, double* d_j, hipStream_t st);
+// disk spectra (rtgr_spectrum.hip; include/rtgr.h "disk spectra").  The caller's rtgr_spectrum as the kernels read it, in double whatever
+// the entry's scalar type: LINE: s = nb / (hi - lo); THERMAL: span = hi - lo, or log(hi / lo) with RTGR_SPEC_LOG.  `em`: the emitter's
+// record in double (the temperature law and the gain of THERMAL).
+struct SpecDev {
+    uint32_t kind, flags;
+    uint64_t nb;
+    double lo, hi, s, span;
+    double amp, alpha, rho_min, rho_max, q;
+    DevEmission<double> em;
+};
+size_t spec_partial_bytes(uint64_t n, uint64_t nb);   // what spec_reduce_launch needs for n pixels and nb bins or samples
+// the reduction: nb x 3 doubles into d_out, pass by pass over the spectral axis — the partial sums of a pass in d_partial, then their
+// sum in range order (times c_k for THERMAL) …
+template <class R>
+int spec_reduce_launch(const LcPlanes<R>& P, const SpecDev& S, const LcWeight& W, double* d_partial, double* d_out, hipStream_t st);
+// … and the hook: the axis (nb), and bin and val at n triples (x, y, g), from the same device functions; any output may be null
+template <class R>
+int spec_points_launch(const R* d_xyg, uint64_t n, const SpecDev& S, double* d_axis, int64_t* d_bin, double* d_val, hipStream_t st);
 
 }  // namespace rtgr

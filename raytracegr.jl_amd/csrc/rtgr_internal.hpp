@@ -22,6 +22,8 @@
 //                           their states, batch by batch, + the post-trace stage), the canvas and frame hooks (kernels: rtgr_observer.hip)
 //   rtgr_lightcurve_host.hip  hot-spot light curves: the checks of an rtgr_hot_spot, the stream's light-curve scratch, the stage (Omega_s from the
 //                           emission kernel in point mode, then the reduction), the traced light curve, the hook (kernels: rtgr_lightcurve.hip)
+//   rtgr_spectrum_host.hip  disk spectra: the checks of an rtgr_spectrum, the stage's share of the stream's light-curve scratch, the stage, the
+//                           traced spectrum, the hook (kernels: rtgr_spectrum.hip)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -249,6 +251,9 @@ int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refin
 template <class R> int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, const rtgr_disk_emission* emit, DevEmission<R>& em);
 // the observer camera (rtgr_observer_host.hip): the checks of an rtgr_observer against its scene, and the record the frame kernel reads
 template <class R> int observer_resolve(const rtgr_scene* scene, const rtgr_observer* obs, DevObserver<R>& ob);
+// the pixel weight of an observer's canvas (rtgr_lightcurve_host.hip; obs may be null: w = 1): what lc_pixel_weight reads, for the light curve
+// and the disk spectra
+template <class R> int pixel_weight_resolve(const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, LcWeight& W);
 
 // scratch device buffers of the small host-pointer hooks (eval_*, make_canvas, the probe): RAII, synchronous
 struct DevBuf {
@@ -402,6 +407,10 @@ template <class R> int light_curve_device(rtgr_context* ctx, const rtgr_scene* s
 template <class R> int trace_light_curve_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, double* d_lc, rtgr_counters* ctr, void* stream);
 template <class R> int trace_light_curve(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot, R* rgb, const rtgr_ray_outputs* out, R* g, double* lc, rtgr_counters* ctr);
 template <class R> int eval_hot_spot(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot, const R* xyt, uint64_t n, R* omega_s, int* valid, double* j);
+template <class R> int spectrum_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_spectrum* spec, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const uint32_t* d_hit32, const R* d_state_end, const R* d_g, double* d_out, void* stream);
+template <class R> int trace_spectrum_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_spectrum* spec, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, double* d_out, rtgr_counters* ctr, void* stream);
+template <class R> int trace_spectrum(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_spectrum* spec, R* rgb, const rtgr_ray_outputs* out, R* g, double* spectrum, rtgr_counters* ctr);
+template <class R> int eval_spectrum(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_spectrum* spec, const R* xyg, uint64_t n, double* axis, int64_t* bin, double* val);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 

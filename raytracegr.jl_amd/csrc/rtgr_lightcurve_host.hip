@@ -37,6 +37,29 @@ static int spot_resolve(const rtgr_scene* scene, const rtgr_disk_emission* emit,
     return RTGR_OK;
 }
 
+// the pixel weight of `obs` (may be null: w = 1) on an ni x nj canvas, as lc_pixel_weight reads it — shared with the disk spectra
+// (rtgr_spectrum_host.hip)
+template <class R>
+int pixel_weight_resolve(const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, LcWeight& W) {
+    W.proj = 0; W.pad = 0; W.hx = W.hy = 0.0; W.scale = 1.0;
+    if (obs) {
+        int rc;
+        DevObserver<R> ob;
+        if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
+        if (obs->projection == RTGR_PROJ_PERSPECTIVE) {
+            W.proj = 1;
+            W.hx = std::tan(0.5 * obs->fov_x); W.hy = std::tan(0.5 * obs->fov_y);
+            W.scale = W.hx * W.hy * (2.0 / (double)ni) * (2.0 / (double)nj);
+        } else {
+            W.proj = 2;
+            W.hx = 0.5 * obs->fov_x; W.hy = 0.5 * obs->fov_y;
+            W.scale = (obs->fov_x / (double)ni) * (obs->fov_y / (double)nj);
+        }
+    }
+    return RTGR_OK;
+}
+RTGR_INSTANTIATE_F64_F32(pixel_weight_resolve);
+
 // everything a light-curve call resolves before it touches a device: the emitter, the spot, the pixel weight of `obs` (may be null)
 template <class R>
 struct LcResolved {
@@ -53,21 +76,7 @@ static int lc_resolve(const rtgr_scene* scene, const rtgr_disk_emission* emit, c
     int rc;
     if ((rc = emission_resolve<R>(scene, nullptr, emit, L.em))) return rc;
     if ((rc = spot_resolve(scene, emit, spot, L.S))) return rc;
-    L.W.proj = 0; L.W.pad = 0; L.W.hx = L.W.hy = 0.0; L.W.scale = 1.0;
-    if (obs) {
-        DevObserver<R> ob;
-        if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
-        if (obs->projection == RTGR_PROJ_PERSPECTIVE) {
-            L.W.proj = 1;
-            L.W.hx = std::tan(0.5 * obs->fov_x); L.W.hy = std::tan(0.5 * obs->fov_y);
-            L.W.scale = L.W.hx * L.W.hy * (2.0 / (double)ni) * (2.0 / (double)nj);
-        } else {
-            L.W.proj = 2;
-            L.W.hx = 0.5 * obs->fov_x; L.W.hy = 0.5 * obs->fov_y;
-            L.W.scale = (obs->fov_x / (double)ni) * (obs->fov_y / (double)nj);
-        }
-    }
-    return RTGR_OK;
+    return pixel_weight_resolve<R>(scene, obs, ni, nj, L.W);
 }
 
 // The light-curve scratch of a stream: the head, the partial sums of one pass, then `borrow` bytes (the planes a traced light curve
