@@ -66,7 +66,9 @@ template <> RTGR_DEV float rmin<float>(float a, float b) { float r; asm("v_min_f
 // Measured on gfx950 (rtgr_eval_fastmath_f64 and its GPU test, test_fast_reciprocal_and_rsqrt_accuracy; the seeds
 // themselves in round 1 with a stand-alone microbenchmark): v_rcp_f64 / v_rsq_f64 seeds are good to 2^-24.4 / 2^-24.2, so a
 // cubically convergent step (error e³ ≈ 2^-73) lands on full double precision: max relative error 1.1e-16 / 1.4e-16
-// over 2^20 operands in [2^-10, 2^10].  No denormal / inf fix-up (operands here are O(1e-3 … 1e3)).  The IEEE
+// over 2^20 operands in [2^-10, 2^10].  No denormal / inf fix-up: the operands the RHS forms — ρ², q, the radicands, r, r²,
+// r² + a², r⁴ + a²z², r²(r² + a²)² — run from 2^-55 (the horizon of M = 2^-10) to 2^180 (r = 10⁶ M, M = 2^10), far inside the normal
+// range; that whole span is under test (test_rhs_edges.py, test_fast_reciprocal_and_rsqrt_over_the_range_the_rhs_uses).  The IEEE
 // expansions hipcc emits for `1.0/x` and `sqrt(x)` cost 11 and ~14 instructions; these cost 4 and 6.
 template <class R> RTGR_DEV R frcp(R x);
 template <> RTGR_DEV double frcp<double>(double x) {
@@ -173,7 +175,9 @@ RTGR_DEV void ks_field(R x, R y, R z, R M, R a, KSField<R>& F) {
         const R tm = R(2) * M;
         F.f = tm * r3 * iden;
         // ∂f/∂r = 2M r²(3 den − 4 r⁴)/den² ;  ∂f/∂z|_r = −2M r³ 2a²z/den²
-        const R fr = tm * r2 * rfma(R(3), den, R(-4) * r2 * r2) * iden * iden;
+        // (one 1/den BEFORE the bracket: tm r² · den is r⁶, which leaves Float32 at r ≈ 2·10⁶ — ρ ≈ 2000 for the as-written
+        //  radius, r ≈ ρ²/2 — while every partial product of this order stays below r²; test_rhs_edges.py, family `far`)
+        const R fr = tm * r2 * iden * rfma(R(3), den, R(-4) * r2 * r2) * iden;
         const R fz = R(-2) * F.f * a2z * iden;
         F.df[0] = fr * dr[0];
         F.df[1] = fr * dr[1];

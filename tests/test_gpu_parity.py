@@ -147,7 +147,9 @@ def test_geodesic_rhs_matches_oracle(lib, name, path):
     relative (of the largest component), for all six metric variants and all three device formulations:
     path 0 closed contraction with IEEE division (tile kernel), path 1 generic duals (RTGR_METRIC_GENERIC / user metrics),
     path 2 EXACTLY the function the production integrate loop calls (accel_radial / accel_spin with the fast reciprocal
-    and reciprocal-square-root sequences and the textbook metric's null-congruence shortcuts)."""
+    and reciprocal-square-root sequences and the textbook metric's null-congruence shortcuts).
+    (Random directions at radius 1.7 … 12 only.  The polar axis, the equatorial plane, the horizon, radii to 10⁶ M, further
+    spins and masses, and bars a few hundred times tighter — set by a 50-digit reference: test_rhs_edges.py.)"""
     s = _rhs_states()
     sc = rt.make_scene(METRICS[name], [])
     ref = O.geodesic(sc, s)

@@ -24,11 +24,11 @@ import numpy as np
 KERR_BL_MARKER = 0x300   # rtgr_scene.user_metric of a test scene that means "the Boyer–Lindquist example" to this module
 
 
-@functools.lru_cache(maxsize=None)
-def _metric_fn(kind):
+def metric_expr(kind):
     """kind: 'mink' | 'ks_ref' (r as written, :284) | 'ks_true' (textbook r) | 'schw_iso' (the user-metric example; a scene
-    of kind RTGR_USER is taken to be that one).  Returns f(x, y, z, M, a) ->
-    (g[4][4], dg[3][4][4]) with dg[j] = ∂g/∂x_j, j = x,y,z (every metric here is stationary: ∂_t g = 0)."""
+    of kind RTGR_USER is taken to be that one) | 'kerr_bl'.  Returns ((x, y, z, M, a), g): the sympy symbols and the 4x4 matrix
+    g_ab — the ONE place the formulas are typed (the double-precision lambdas below and the 50-digit reference of
+    golden/make_rhs_edges.py are both made from it)."""
     import sympy as sp
     x, y, z, M, a = sp.symbols("x y z M a", real=True)
     eta = sp.diag(-1, 1, 1, 1)
@@ -62,6 +62,15 @@ def _metric_fn(kind):
         f = 2 * M * r ** 3 / (r ** 4 + a * a * z * z)
         k = sp.Matrix([1, (r * x + a * y) / (r * r + a * a), (r * y - a * x) / (r * r + a * a), z / r])
         g = eta + f * k * k.T
+    return (x, y, z, M, a), g
+
+
+@functools.lru_cache(maxsize=None)
+def _metric_fn(kind):
+    """Returns f(x, y, z, M, a) -> (g[4][4], dg[3][4][4]) of metric_expr(kind) in double precision, with dg[j] = ∂g/∂x_j,
+    j = x,y,z (every metric here is stationary: ∂_t g = 0)."""
+    import sympy as sp
+    (x, y, z, M, a), g = metric_expr(kind)
     dg = [sp.diff(g, v) for v in (x, y, z)]
     fn = sp.lambdify((x, y, z, M, a), [g.tolist(), [d.tolist() for d in dg]], modules="numpy", cse=True)
 
