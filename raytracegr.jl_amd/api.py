@@ -728,28 +728,41 @@ def eval_hot_spot(metric, objs, emission, spot, points=None, dtype=np.float64, c
     return dict(omega_s=omega[0], valid=bool(valid.value), j=j)
 
 
+def _trace_reduced(name, hook, metric, objs, observer, ni, nj, emission, record, rows, textures, r_escape, opt, dtype, ctx, details):
+    """What light_curve and spectrum share: rtgr_trace_<name>_f64 / _f32 on ONE frame of the emitting disk seen by `observer`, reduced on
+    the device to `rows` rows of (F, A, B) by `record` (a HotSpot, a Spectrum).  The observer is checked first, then `hook` asks the
+    feature's own hook what it must (it raises, or answers).
+    -> (dict(rgb [3, ni*nj], g [ni*nj], counters; details: + the per-ray outputs), table [rows, 3], the hook's answer)"""
+    lib = _lib()
+    _valid_observer(metric, objs, observer, dtype, ctx)
+    answer = hook()
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    n = ni * nj
+    sh = make_shade(textures, r_escape) if textures else None
+    res = dict(rgb=np.zeros((3, n), dtype), g=np.zeros(n, dtype))
+    table = np.zeros((int(rows), 3), np.float64)
+    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
+    ctr = rtgr_counters()
+    fn = getattr(lib, f"rtgr_trace_{name}_" + ("f64" if dtype == np.float64 else "f32"))
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(observer), ni, nj, None if sh is None else C.byref(sh), C.byref(emission),
+                       C.byref(record), res["rgb"].ctypes.data, outs, res["g"].ctypes.data, table.ctypes.data, C.byref(ctr)))
+    res["counters"] = ctr.as_dict()
+    return res, table, answer
+
+
 def light_curve(metric, objs, observer, ni, nj, emission, spot, textures=None, r_escape=0.0, opt=None, dtype=np.float64, ctx=None, details=False):
     """The LIGHT CURVE of a hot spot (rtgr_trace_light_curve_f64 / _f32) — an extension: ONE frame of the emitting disk seen by
     `observer` (as trace_observer with `emission`), reduced on the device over the nt observer times of `spot` (a HotSpot).  The
     picture is the disk without the spot.  Raises ValueError for an observer with no valid frame and for a spot with no valid orbit.
     -> dict(rgb [3, ni*nj], g [ni*nj], lc [nt, 3] = (F, A, B) per observer time — the image centroid is (A / F, B / F) in the pixel
     coordinates a, b in (-1, 1) —, tau [nt], counters; details: + the per-ray outputs)."""
-    lib = _lib()
-    _valid_observer(metric, objs, observer, dtype, ctx)
-    if not eval_hot_spot(metric, objs, emission, spot, None, dtype, ctx)["valid"]:
-        raise ValueError("HotSpot: no valid circular orbit of the disk's emitter at rho_s (none exists there, or it is not timelike)")
-    sc = make_scene(metric, objs, ctx)
-    opt = opt or solver_defaults(dtype)
-    n = ni * nj
-    sh = make_shade(textures, r_escape) if textures else None
-    res = dict(rgb=np.zeros((3, n), dtype), g=np.zeros(n, dtype), lc=np.zeros((int(spot.nt), 3), np.float64),
-               tau=spot.t_start + np.arange(int(spot.nt), dtype=np.float64) * spot.dt)
-    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
-    ctr = rtgr_counters()
-    fn = lib.rtgr_trace_light_curve_f64 if dtype == np.float64 else lib.rtgr_trace_light_curve_f32
-    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(observer), ni, nj, None if sh is None else C.byref(sh), C.byref(emission),
-                       C.byref(spot), res["rgb"].ctypes.data, outs, res["g"].ctypes.data, res["lc"].ctypes.data, C.byref(ctr)))
-    res["counters"] = ctr.as_dict()
+    def hook():
+        if not eval_hot_spot(metric, objs, emission, spot, None, dtype, ctx)["valid"]:
+            raise ValueError("HotSpot: no valid circular orbit of the disk's emitter at rho_s (none exists there, or it is not timelike)")
+
+    res, lc, _ = _trace_reduced("light_curve", hook, metric, objs, observer, ni, nj, emission, spot, spot.nt, textures, r_escape, opt, dtype, ctx, details)
+    res.update(lc=lc, tau=spot.t_start + np.arange(int(spot.nt), dtype=np.float64) * spot.dt)
     return res
 
 
@@ -791,22 +804,9 @@ def spectrum(metric, objs, observer, ni, nj, emission, spec, textures=None, r_es
     trace_observer with `emission`), reduced on the device to the line profile or the thermal spectrum `spec` (a Spectrum) names.
     Raises ValueError for an observer with no valid frame.  -> dict(rgb [3, ni*nj], g [ni*nj], axis [nb], F [nb], A [nb], B [nb] — the
     flux centroid per bin or sample is (A / F, B / F) in the pixel coordinates a, b in (-1, 1) —, counters; details: + the per-ray outputs)."""
-    lib = _lib()
-    _valid_observer(metric, objs, observer, dtype, ctx)
-    axis = eval_spectrum(metric, objs, emission, spec, None, dtype, ctx)["axis"]
-    sc = make_scene(metric, objs, ctx)
-    opt = opt or solver_defaults(dtype)
-    n = ni * nj
-    sh = make_shade(textures, r_escape) if textures else None
-    res = dict(rgb=np.zeros((3, n), dtype), g=np.zeros(n, dtype))
-    out = np.zeros((int(spec.nb), 3), np.float64)
-    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
-    ctr = rtgr_counters()
-    fn = lib.rtgr_trace_spectrum_f64 if dtype == np.float64 else lib.rtgr_trace_spectrum_f32
-    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(observer), ni, nj, None if sh is None else C.byref(sh), C.byref(emission),
-                       C.byref(spec), res["rgb"].ctypes.data, outs, res["g"].ctypes.data, out.ctypes.data, C.byref(ctr)))
+    res, out, axis = _trace_reduced("spectrum", lambda: eval_spectrum(metric, objs, emission, spec, None, dtype, ctx)["axis"], metric, objs, observer, ni, nj,
+                              emission, spec, spec.nb, textures, r_escape, opt, dtype, ctx, details)
     res.update(axis=axis, F=out[:, 0].copy(), A=out[:, 1].copy(), B=out[:, 2].copy())
-    res["counters"] = ctr.as_dict()
     return res
 
 

@@ -90,12 +90,6 @@ __global__ __launch_bounds__(256) void aa_reduce_kernel(const R* sub, const uint
     }
 }
 
-#define CHECK_LAUNCH()                                     \
-    do {                                                   \
-        hipError_t e_ = hipGetLastError();                 \
-        if (e_ != hipSuccess) return fail(RTGR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
-    } while (0)
-
 template <class R>
 int aa_flag(const R* d_rgb, const uint32_t* d_hit32, const uint8_t* d_status, uint64_t ni, uint64_t nj, R contrast, bool all, uint8_t* d_flag,
             uint64_t* d_list, unsigned long long* d_count, hipStream_t st) {

@@ -152,7 +152,7 @@ void free_device_state(DeviceCtx& d, bool all) {
             if (kv.second.queue) (void)hipFree(kv.second.queue);
             if (kv.second.frame) (void)hipFree(kv.second.frame);
             if (kv.second.batch) (void)hipFree(kv.second.batch);
-            if (kv.second.lc) (void)hipFree(kv.second.lc);
+            if (kv.second.reduce) (void)hipFree(kv.second.reduce);
         }
     }
     free_all(d.grids.drain(all));            // unloaded grid metrics — all: and the resident ones (the device is idle: synchronised above)

@@ -43,12 +43,6 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs<R> A) {
         for (int ch = 0; ch < 3; ch++) A.rgb[ch * A.plane_stride + idx * A.pixel_stride] = col[ch];
 }
 
-#define CHECK_LAUNCH()                                     \
-    do {                                                   \
-        hipError_t e_ = hipGetLastError();                 \
-        if (e_ != hipSuccess) return fail(RTGR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
-    } while (0)
-
 template <class R>
 int emit_launch(const EmitArgs<R>& A, hipStream_t st) {
     if (A.n == 0) return RTGR_OK;

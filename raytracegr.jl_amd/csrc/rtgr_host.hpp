@@ -44,6 +44,12 @@ int fail(int code, const std::string& msg);  // records the calling thread's las
         if (e_ != hipSuccess)                                                                       \
             return ::rtgr::fail(RTGR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
+// behind every kernel launch of the library's own kernel units
+#define CHECK_LAUNCH()                                     \
+    do {                                                   \
+        hipError_t e_ = hipGetLastError();                 \
+        if (e_ != hipSuccess) return ::rtgr::fail(RTGR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
+    } while (0)
 
 // whether work enqueued on st is being recorded into a hipGraph rather than run
 inline bool stream_capturing(hipStream_t st) {
@@ -218,10 +224,11 @@ struct StreamState {
     // post-trace kernels read of the sub-rays (rtgr_aa_host.hip), or the ray states of an observer's rows (rtgr_observer_host.hip)
     void* frame = nullptr; size_t frame_bytes = 0;
     void* batch = nullptr; size_t batch_bytes = 0;
-    // scratch of the light-curve calls on this stream (rtgr_lightcurve_host.hip), grow-only and retired likewise: the head (LC_HEAD),
-    // the partial sums of one pass over the time axis, then the planes a traced light curve borrows (end states, hit map, ratio).  The
-    // disk spectra (rtgr_spectrum_host.hip) use the same buffer — the two stages are ordered on the stream —, with no head
-    void* lc = nullptr; size_t lc_bytes = 0;
+    // scratch of the reductions of a traced frame on this stream — light curves and disk spectra (rtgr_reduce_host.hip: reduce_scratch;
+    // ReduceLayout, rtgr_internal.hpp) —, grow-only and retired likewise: the reduction's head (the light curve's LC_HEAD, none for the
+    // spectra), the partial sums of one pass over the item axis, then the planes a traced call borrows (end states, hit map, ratio).  One
+    // buffer for all of them: the stages on a stream are ordered
+    void* reduce = nullptr; size_t reduce_bytes = 0;
 };
 
 struct Staging;  // host entry points (rtgr_internal.hpp)
@@ -458,32 +465,20 @@ struct TracedPixels {
 struct LcSpot {
     double rho_s, phi0, inv_2s2, r2_cut, cut_sigma, e_cut, amp, q, t_start, dt;
 };
-// the pixel weight: proj 0: w = 1 (no observer); 1: perspective, hx, hy = tan(fov / 2), scale = hx hy (2 / ni)(2 / nj); 2: equirectangular,
-// hy = fov_y / 2, scale = (fov_x / ni)(fov_y / nj)
-struct LcWeight {
-    uint32_t proj, pad;
-    double hx, hy, scale;
-};
-// the planes of a traced frame the reduction reads: n = ni nj pixels, `object` what hit32 holds on the emitting disk
-template <class R>
-struct LcPlanes {
-    const uint32_t* hit32;
-    const R* state_end;
-    const R* g;
-    uint64_t n, ni, nj;
-    uint32_t object, pad;
-};
-// The head of a stream's light-curve scratch (LC_HEAD bytes): the synthetic pair of states and the synthetic observer record the emission
-// kernel evaluates in point mode, and the Omega_s it writes (scalar type R), at these offsets.  Behind it: the partial sums.
+// what every reduction of a traced frame reads (rtgr_reduce.hpp, which the trace's units do not include): the planes of the frame and
+// the pixel weight
+template <class R> struct ReducePlanes;
+struct PixelWeight;
+// The head of the stream's reduction scratch in a light-curve call (LC_HEAD bytes): the synthetic pair of states and the synthetic observer
+// record the emission kernel evaluates in point mode, and the Omega_s it writes (scalar type R), at these offsets.  Behind it: the partial sums.
 constexpr size_t LC_HEAD = 1024, LC_HEAD_S0 = 0, LC_HEAD_SE = 64, LC_HEAD_OMEGA = 128, LC_HEAD_FRAME = 256;
 static_assert(LC_HEAD_FRAME + sizeof(ObsFrame<double>) <= LC_HEAD, "the head holds the record");
-size_t lc_partial_bytes(uint64_t n, uint64_t nt);   // what lc_reduce_launch needs behind the head for n pixels and nt samples
 // the states and the record for a spot at rho_s into the head (one wave) …
 template <class R> int lc_seed_launch(R rho_s, char* d_head, hipStream_t st);
-// … the reduction: nt x 3 doubles into d_lc, pass by pass over the time axis — the partial sums of a pass in d_partial, then their sum in
-// range order (NaN everywhere when the head's Omega_s is not finite) …
+// … the reduction (rtgr_reduce.hpp: reduce_launch): nt x 3 doubles into d_lc, pass by pass over the time axis — the partial sums of a pass
+// in d_partial, then their sum in range order (NaN everywhere when the head's Omega_s is not finite) …
 template <class R>
-int lc_reduce_launch(const LcPlanes<R>& P, const LcSpot& S, const LcWeight& W, uint64_t nt, const char* d_head, double* d_partial, double* d_lc,
+int lc_reduce_launch(const ReducePlanes<R>& P, const LcSpot& S, const PixelWeight& W, uint64_t nt, const char* d_head, double* d_partial, double* d_lc,
                      hipStream_t st);
 // … and the hook: j at n triples (x, y, t), from the same device functions
 template <class R> int lc_points_launch(const R* d_xyt, uint64_t n, const LcSpot& S, const char* d_head, double* d_j, hipStream_t st);
@@ -497,11 +492,10 @@ struct SpecDev {
     double amp, alpha, rho_min, rho_max, q;
     DevEmission<double> em;
 };
-size_t spec_partial_bytes(uint64_t n, uint64_t nb);   // what spec_reduce_launch needs for n pixels and nb bins or samples
-// the reduction: nb x 3 doubles into d_out, pass by pass over the spectral axis — the partial sums of a pass in d_partial, then their
-// sum in range order (times c_k for THERMAL) …
+// the reduction (rtgr_reduce.hpp: reduce_launch): nb x 3 doubles into d_out, pass by pass over the spectral axis — the partial sums of a
+// pass in d_partial, then their sum in range order (times c_k for THERMAL) …
 template <class R>
-int spec_reduce_launch(const LcPlanes<R>& P, const SpecDev& S, const LcWeight& W, double* d_partial, double* d_out, hipStream_t st);
+int spec_reduce_launch(const ReducePlanes<R>& P, const SpecDev& S, const PixelWeight& W, double* d_partial, double* d_out, hipStream_t st);
 // … and the hook: the axis (nb), and bin and val at n triples (x, y, g), from the same device functions; any output may be null
 template <class R>
 int spec_points_launch(const R* d_xyg, uint64_t n, const SpecDev& S, double* d_axis, int64_t* d_bin, double* d_val, hipStream_t st);

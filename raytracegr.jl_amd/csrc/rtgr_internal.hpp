@@ -20,10 +20,13 @@
 //                           (kernels: rtgr_emit.hip)
 //   rtgr_observer_host.hip  the observer camera: the checks of an rtgr_observer, the observer trace (the frame and ray kernels + a plain trace of
 //                           their states, batch by batch, + the post-trace stage), the canvas and frame hooks (kernels: rtgr_observer.hip)
-//   rtgr_lightcurve_host.hip  hot-spot light curves: the checks of an rtgr_hot_spot, the stream's light-curve scratch, the stage (Omega_s from the
-//                           emission kernel in point mode, then the reduction), the traced light curve, the hook (kernels: rtgr_lightcurve.hip)
-//   rtgr_spectrum_host.hip  disk spectra: the checks of an rtgr_spectrum, the stage's share of the stream's light-curve scratch, the stage, the
-//                           traced spectrum, the hook (kernels: rtgr_spectrum.hip)
+//   rtgr_reduce_host.hip    THE path from a traced frame of an emitting disk to a reduced table, for the two files below: the stream's
+//                           reduction scratch, the pixel weight, the four bodies behind rtgr_<x>_device_*, rtgr_trace_<x>_device_* and
+//                           rtgr_trace_<x>_* (a Reduction says what <x> is; kernels: rtgr_reduce.hpp, instantiated in the two kernel units)
+//   rtgr_lightcurve_host.hip  hot-spot light curves: the checks of an rtgr_hot_spot, the stage (Omega_s from the emission kernel in point
+//                           mode, then the reduction), the entry points as a Reduction each, the hook (kernels: rtgr_lightcurve.hip)
+//   rtgr_spectrum_host.hip  disk spectra: the checks of an rtgr_spectrum, the stage, the entry points as a Reduction each, the hook
+//                           (kernels: rtgr_spectrum.hip)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -251,9 +254,55 @@ int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refin
 template <class R> int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, const rtgr_disk_emission* emit, DevEmission<R>& em);
 // the observer camera (rtgr_observer_host.hip): the checks of an rtgr_observer against its scene, and the record the frame kernel reads
 template <class R> int observer_resolve(const rtgr_scene* scene, const rtgr_observer* obs, DevObserver<R>& ob);
-// the pixel weight of an observer's canvas (rtgr_lightcurve_host.hip; obs may be null: w = 1): what lc_pixel_weight reads, for the light curve
-// and the disk spectra
-template <class R> int pixel_weight_resolve(const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, LcWeight& W);
+
+// ---- a traced frame of an emitting disk reduced to a table of (F, A, B) rows (rtgr_reduce_host.hip) -----------------------------------
+// The reduction scratch of a stream (StreamState::reduce) in one call, each block 256-aligned and an absent one no bytes.  Pure
+// arithmetic: the reduction's head (head_bytes, a multiple of 256), the partial sums of one pass (partial_bytes: reduce_partial_bytes,
+// rtgr_reduce.hpp), then the planes a traced call keeps there because the caller gave none — end states, hit map, frequency ratio, n
+// pixels of each, the scalars `scalar` bytes wide.
+struct ReduceGiven { bool state_end = false, hit32 = false, g = false; };
+struct ReduceLayout { size_t partial, state_end, hit32, g, bytes; };
+inline ReduceLayout reduce_layout(size_t head_bytes, size_t partial_bytes, uint64_t n, size_t scalar, const ReduceGiven& given) {
+    ReduceLayout at;
+    at.partial = head_bytes;
+    at.state_end = at.partial + align256(partial_bytes);
+    at.hit32 = at.state_end + (given.state_end ? 0 : align256((size_t)n * 8 * scalar));
+    at.g = at.hit32 + (given.hit32 ? 0 : align256((size_t)n * sizeof(uint32_t)));
+    at.bytes = at.g + (given.g ? 0 : align256((size_t)n * scalar));
+    return at;
+}
+// What differs between the reductions — a value per entry-point family, made by the caller for one call:
+template <class R>
+struct Reduction {
+    EntryWords device, traced;   // the words of rtgr_<x>_device_* and of rtgr_trace_<x>_* / rtgr_trace_<x>_device_*
+    const char* canvas;          // what the device entry calls its canvas ("a light curve")
+    const char* out_name;        // … and every entry its output, in "<entry>: <out_name> is NULL"
+    const void* record;          // the caller's record (rtgr_hot_spot, rtgr_spectrum) and the refusal of a NULL one
+    const char* record_null;
+    size_t head_bytes;           // the head of the scratch the stage wants in front of the partial sums
+    uint64_t rows;               // rows of the output table (read after `resolve` has accepted the record)
+    // every refusal the arguments deserve, and what the stage reads of them (kept by the caller); touches no device
+    std::function<int(uint64_t ni, uint64_t nj)> resolve;
+    // the kernels, enqueued on st (D.mu held, timed in slot 0): `base`: the stream's scratch — head, then the partial sums
+    std::function<int(DeviceCtx& D, const DevScene<R>& sc, const ReducePlanes<R>& P, char* base, double* d_out, hipStream_t st)> stage;
+};
+// rtgr_<x>_device_*: the stage over the caller's planes, on the device that holds d_out
+template <class R>
+int reduce_device(rtgr_context* ctx, const Reduction<R>& red, const rtgr_scene* scene, const rtgr_disk_emission* emit, uint64_t ni, uint64_t nj,
+                  const uint32_t* d_hit32, const R* d_state_end, const R* d_g, double* d_out, void* stream);
+// rtgr_trace_<x>_device_*: rtgr_trace_observer_device_* on the device that holds d_rgb, with the planes the stage reads borrowed from the
+// stream's reduction scratch where the caller gave none, then the stage
+template <class R>
+int trace_reduce_device(rtgr_context* ctx, const Reduction<R>& red, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                        uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, double* d_out,
+                        rtgr_counters* ctr, void* stream);
+// rtgr_trace_<x>_*, host pointers: the same on device 0 of the context, on its staging's compute stream; the frame and the table copied out
+template <class R>
+int trace_reduce(rtgr_context* ctx, const Reduction<R>& red, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                 uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, R* rgb, const rtgr_ray_outputs* out, R* g, double* table,
+                 rtgr_counters* ctr);
+// the pixel weight of an observer's canvas (obs may be null: w = 1): what pixel_weight (rtgr_reduce.hpp) reads
+template <class R> int pixel_weight_resolve(const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, PixelWeight& W);
 
 // scratch device buffers of the small host-pointer hooks (eval_*, make_canvas, the probe): RAII, synchronous
 struct DevBuf {

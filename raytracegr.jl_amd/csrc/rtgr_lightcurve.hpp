@@ -1,5 +1,6 @@
-// rtgr_lightcurve.hpp — hot-spot light curves (include/rtgr.h "hot-spot light curves"): the device functions of the reduction of ONE traced
-// frame over many observer times, and the sizes of its kernels (rtgr_lightcurve.hip; host side: rtgr_lightcurve_host.hip).
+// rtgr_lightcurve.hpp — hot-spot light curves (include/rtgr.h "hot-spot light curves"): the spot model, i.e. the device functions of the
+// reduction of ONE traced frame over many observer times (the reduction itself and its sizes: rtgr_reduce.hpp; its model and the other
+// kernels: rtgr_lightcurve.hip; host side: rtgr_lightcurve_host.hip).
 //
 // THE MODEL, restated (everything in double; the planes of a Float32 entry are promoted on read).  A rigid Gaussian spot rides in the
 // emitting disk at radius rho_s with the rate Omega_s of the disk's own emitter model there — which is NOT computed here: the emission
@@ -15,42 +16,20 @@
 //     e  = d² < (cut sigma)² ? max(exp(-d² / (2 sigma²)) - exp(-cut² / 2), 0) : 0            j = amp e
 // (a pair costs two FMAs and a compare, and an exp only inside the support; the cancellation error of d² is eps rho², eps rho² / sigma²
 // relative in e).  A pixel is ACTIVE iff hit32 == the disk, g finite and > 0, (t, x, y) finite and |rho_p - rho_s| < cut sigma — no other
-// pixel can ever have d < cut sigma.  With the pixel's (a, b) and weight w (lc_pixel_weight), W = amp w g^q:
+// pixel can ever have d < cut sigma.  With the pixel's (a, b) and weight w (pixel_weight, rtgr_reduce.hpp), W = amp w g^q:
 //     F_k = sum_p W e_pk      A_k = sum_p (W a) e_pk      B_k = sum_p (W b) e_pk
-//
-// THE KERNEL'S SIZES.  A block is one wave (LC_WAVE lanes).  Along the pixel axis a block owns a fixed range of `chunk` pixels —
-// LC_RANGE pixels while the frame has at most LC_RANGE x LC_MAX_RANGES of them, a multiple of LC_RANGE beyond — which it compacts, LC_RANGE
-// at a time and in pixel order, into records in LDS.  Along the time axis a block owns LC_TILE = LC_WAVE x LC_LANE_SAMPLES samples, each
-// lane LC_LANE_SAMPLES of them; the host walks the axis in passes of LC_PASS samples.  So the partial sums of a pass are at most
-// LC_MAX_RANGES x LC_PASS x 3 doubles = 25 165 824 bytes (24 MiB), whatever the frame and nt.
 #pragma once
-#include "rtgr_host.hpp"
-#include "rtgr_physics.hpp"   // (RTGR_DEV)
+#include "rtgr_reduce.hpp"   // (finite_f64, pixel_weight, the skeleton)
 
 namespace rtgr {
 
-constexpr unsigned LC_WAVE = 64;            // lanes per block: one wave
-constexpr unsigned LC_RANGE = 256;          // pixels compacted into LDS at a time; the range of a block in a frame of <= LC_RANGE x LC_MAX_RANGES pixels
-constexpr unsigned LC_LANE_SAMPLES = 4;     // time samples a lane owns
-constexpr unsigned LC_TILE = LC_WAVE * LC_LANE_SAMPLES;   // time samples a block owns
-constexpr unsigned LC_MAX_RANGES = 1024;    // blocks along the pixel axis at most
-constexpr uint64_t LC_PASS = 1024;          // time samples per pass of the host
 constexpr unsigned LC_REC = 6;              // doubles per record: P0, P1, P2, W, W a, W b
-
-// pixels per block and blocks along the pixel axis for a frame of n pixels
-inline uint64_t lc_chunk(uint64_t n) {
-    const uint64_t ranges = (n + LC_RANGE - 1) / LC_RANGE;
-    return ((ranges + LC_MAX_RANGES - 1) / LC_MAX_RANGES) * LC_RANGE;
-}
-inline uint64_t lc_blocks(uint64_t n) { const uint64_t c = lc_chunk(n); return c ? (n + c - 1) / c : 0; }
-
-RTGR_DEV bool lc_finite(double x) { return x - x == 0.0; }
 
 // the per-pixel factors P[3] of a point (t, x, y) of the disk; false: the point is not finite, or it lies off the ring the spot sweeps
 RTGR_DEV bool lc_record(const LcSpot& S, double Om, double t, double x, double y, double P[3]) {
     const double rho2 = x * x + y * y;
     const double rho = sqrt(rho2);
-    if (!lc_finite(t) || !(fabs(rho - S.rho_s) < S.cut_sigma)) return false;   // (a NaN or infinite radius fails the compare)
+    if (!finite_f64(t) || !(fabs(rho - S.rho_s) < S.cut_sigma)) return false;   // (a NaN or infinite radius fails the compare)
     const double theta = S.phi0 + Om * t;
     double st, ct;
     sincos(theta, &st, &ct);
@@ -66,19 +45,6 @@ RTGR_DEV double lc_d2(double P0, double P1, double P2, double cb, double sb) { r
 RTGR_DEV double lc_inside(const LcSpot& S, double d2) {
     const double e = exp(-(d2 * S.inv_2s2)) - S.e_cut;
     return e > 0.0 ? e : 0.0;
-}
-
-// pixel p of the ni x nj frame: its (a, b) and its weight
-RTGR_DEV double lc_pixel_weight(const LcWeight& W, uint64_t p, uint64_t ni, uint64_t nj, double& a, double& b) {
-    const uint64_t i = p % ni, j = p / ni;
-    a = 2.0 * ((double)i + 0.5) / (double)ni - 1.0;
-    b = 2.0 * ((double)j + 0.5) / (double)nj - 1.0;
-    if (W.proj == 1u) {
-        const double ax = a * W.hx, by = b * W.hy, s = 1.0 + ax * ax + by * by;
-        return W.scale / (s * sqrt(s));
-    }
-    if (W.proj == 2u) return cos(b * W.hy) * W.scale;
-    return 1.0;
 }
 
 }  // namespace rtgr

@@ -135,12 +135,6 @@ __global__ __launch_bounds__(256) void redshift_kernel(DevScene<R> sc, DevCamera
     else redshift_body<R>(sc, cam, state0, ni, nj, j0, jstride, n, out_offset, state_end, hit, hit32, red);
 }
 
-#define CHECK_LAUNCH()                                     \
-    do {                                                   \
-        hipError_t e_ = hipGetLastError();                 \
-        if (e_ != hipSuccess) return fail(RTGR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
-    } while (0)
-
 template <class R>
 int misc_canvas(const DevScene<R>& sc, const DevCamera<R>& cam, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t n, R* d_state0, hipStream_t st) {
     hipLaunchKernelGGL(canvas_kernel<R>, dim3(nblk(n)), dim3(256), 0, st, sc, cam, ni, nj, j0, (uint64_t)1, (uint64_t)0, n, d_state0);

@@ -35,12 +35,6 @@ __global__ __launch_bounds__(256) void observer_rays_kernel(const ObsFrame<R>* _
     for (int c = 0; c < 8; c++) state0[w * 8 + c] = s[c];
 }
 
-#define CHECK_LAUNCH()                                     \
-    do {                                                   \
-        hipError_t e_ = hipGetLastError();                 \
-        if (e_ != hipSuccess) return fail(RTGR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
-    } while (0)
-
 template <class R>
 int observer_frame_launch(const DevScene<R>& sc, const DevObserver<R>& ob, ObsFrame<R>* d_frame, hipStream_t st) {
     hipLaunchKernelGGL(observer_frame_kernel<R>, dim3(1), dim3(64), 0, st, sc, ob, d_frame);

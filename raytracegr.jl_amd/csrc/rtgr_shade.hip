@@ -67,12 +67,6 @@ __global__ __launch_bounds__(256) void eval_texture_kernel(const R* tex, uint32_
     for (int ch = 0; ch < 3; ch++) rgb[idx * 3 + ch] = col[ch];
 }
 
-#define CHECK_LAUNCH()                                     \
-    do {                                                   \
-        hipError_t e_ = hipGetLastError();                 \
-        if (e_ != hipSuccess) return fail(RTGR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
-    } while (0)
-
 template <class R>
 int shade_launch(const ShadeArgs<R>& A, hipStream_t st) {
     if (A.n == 0 || A.desc.nbind == 0) return RTGR_OK;

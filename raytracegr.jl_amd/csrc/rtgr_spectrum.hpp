@@ -1,10 +1,10 @@
-// rtgr_spectrum.hpp — disk spectra (include/rtgr.h "disk spectra"): the device functions of the reduction of ONE traced frame of an
-// emitting disk to a line profile or a thermal spectrum, and the sizes of its kernels (rtgr_spectrum.hip; host side:
-// rtgr_spectrum_host.hip).
+// rtgr_spectrum.hpp — disk spectra (include/rtgr.h "disk spectra"): the spectral model, i.e. the device functions of the reduction of ONE
+// traced frame of an emitting disk to a line profile or a thermal spectrum (the reduction itself and its sizes: rtgr_reduce.hpp; its
+// models and the hook's kernel: rtgr_spectrum.hip; host side: rtgr_spectrum_host.hip).
 //
 // THE MODEL, restated (everything in double; the planes of a Float32 entry are promoted on read).  Pixel p takes part iff
 // hit32[p] == the disk, g_p finite and > 0, (x_p, y_p) of its end state finite, and the mode's own condition holds; rho_p = sqrt(x² + y²).
-// Its weight w_p and its (a_p, b_p) are the light curve's (rtgr_lightcurve.hpp: lc_pixel_weight — called, not copied).
+// Its weight w_p and its (a_p, b_p) are the light curve's (rtgr_reduce.hpp: pixel_weight).
 //   LINE     s = nb / (hi - lo) from the host;  u = (g_p - lo) * s;  counts iff 0 <= u < nb and rho_min <= rho_p < rho_max;  b = (uint64)u
 //            W_p = w_p [amp (rho_p / rho_min)^(-alpha) g_p^q]        (the bracket: the hook's val)
 //            F_b = sum W_p      A_b = sum (W_p a_p)      B_b = sum (W_p b_p)      — plain additions
@@ -13,31 +13,19 @@
 //            e = 1 / expm1(theta_k tau_p);  F_k = fma(w_p, e, F_k), A_k = fma(w_p a_p, e, A_k), B_k = fma(w_p b_p, e, B_k)
 //            c_k = gain [RTGR_SPEC_NU3: gain theta_k³], applied once after the sum over the ranges
 // No expression of these functions is fused (fp contract off) except the accumulation the contract names.
-//
-// THE KERNEL'S SIZES.  A block is one wave (SPEC_WAVE lanes).  Along the pixel axis a block owns the light curve's range — lc_chunk(n)
-// pixels, lc_blocks(n) blocks — which it compacts, SPEC_RANGE at a time and in pixel order, into records of SPEC_REC doubles in LDS
-// (SPEC_RANGE x SPEC_REC x 8 = 8 KB).  Along the spectral axis a block owns SPEC_TILE = SPEC_WAVE x SPEC_LANE_BINS bins or samples, each
-// lane SPEC_LANE_BINS of them in registers; the host walks the axis in passes of SPEC_PASS.  So the partial sums of a pass are at most
-// LC_MAX_RANGES x SPEC_PASS x 3 doubles = 24 MiB, whatever the frame and nb.
 #pragma once
-#include "rtgr_lightcurve.hpp"   // (lc_chunk, lc_blocks, lc_finite, lc_pixel_weight)
-#include "rtgr_emission.hpp"     // (emission_temperature)
+#include "rtgr_reduce.hpp"     // (finite_f64, pixel_weight, the skeleton)
+#include "rtgr_emission.hpp"   // (emission_temperature)
 
 namespace rtgr {
 
-constexpr unsigned SPEC_WAVE = 64;           // lanes per block: one wave
-constexpr unsigned SPEC_RANGE = 256;         // pixels compacted into LDS at a time
-constexpr unsigned SPEC_LANE_BINS = 4;       // bins or samples a lane owns
-constexpr unsigned SPEC_TILE = SPEC_WAVE * SPEC_LANE_BINS;   // bins or samples a block owns
-constexpr uint64_t SPEC_PASS = 1024;         // bins or samples per pass of the host
 constexpr unsigned SPEC_REC = 4;             // doubles per record: LINE (bin - tile base, W, W a, W b), THERMAL (tau, W, W a, W b)
-static_assert(SPEC_RANGE == LC_RANGE && SPEC_PASS == LC_PASS, "the ranges and the partial sums are laid out as the light curve's");
 
 // rho of an end point; false: the point is not finite
 RTGR_DEV bool spec_rho(double x, double y, double& rho) {
 #pragma clang fp contract(off)
     rho = sqrt(x * x + y * y);
-    return lc_finite(x) && lc_finite(y);
+    return finite_f64(x) && finite_f64(y);
 }
 
 // LINE: the bin of a frequency ratio; false: outside [lo, hi)

@@ -27,6 +27,38 @@ def test_frame_scratch_layout(tmp_path):
     assert res.stdout.strip() == f"{4 * 2 * 3 * 8} cases"
 
 
+def test_reduce_scratch_layout(tmp_path):
+    """the reduction scratch of light curves and spectra: n in {1, 77, 2496, 1000003} x sizeof(R) in {4, 8} x head in {0, 1024} x items in
+    {1, 1024, 70000} x the 8 combinations of planes the caller gave: every offset equals the formula the two features each wrote out
+    before there was one layout, each block 256-aligned, inside the total, disjoint from the others, an absent plane no bytes
+    (tests/c/reduce_layout.cpp).  No device: nothing but the headers is linked."""
+    exe = str(tmp_path / "reduce_layout")
+    subprocess.check_call([HIPCC, "-x", "hip", "--offload-arch=gfx950", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "raytracegr.jl_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "c", "reduce_layout.cpp"), "-o", exe])
+    res = subprocess.run([exe], capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert res.stdout.strip() == f"{4 * 2 * 2 * 3 * 8} cases"
+
+
+def test_the_path_from_a_frame_to_a_table_is_written_once():
+    """light curves and spectra share one scratch, one staged copy-out and one layout of the borrowed planes: each of these lines stands
+    in exactly one file of csrc/ (the two features' host files hold none of them)"""
+    csrc = os.path.join(ROOT, "raytracegr.jl_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp"))}
+
+    def homes(line):
+        return [f for f, t in texts.items() if line in t]
+
+    # (the frame scratch of rtgr_frame_host.hip has a refusal of its own, which ends where this one goes on with the advice)
+    assert homes("scratch must grow but the stream is being captured") == ["rtgr_frame_host.hip", "rtgr_reduce_host.hip"]
+    assert homes('scratch must grow but the stream is being captured: make a "') == ["rtgr_reduce_host.hip"]
+    assert homes("hipMemcpyDeviceToHost));   // (staged_frame has synchronised its stream)") == ["rtgr_reduce_host.hip"]
+    assert homes("align256((size_t)n * 8 * scalar)") == ["rtgr_internal.hpp"] and homes("align256((size_t)n * 8 * sizeof(R))") == []
+    for f in ("rtgr_lightcurve_host.hip", "rtgr_spectrum_host.hip"):
+        for word in ("scratch_need", "staged_frame", "align256", "capture_check", "trace_observer_device"):
+            assert word not in texts[f], (f, word)
+
+
 @pytest.fixture(scope="module")
 def lib():
     lib = abi.load()

@@ -113,10 +113,13 @@ def test_the_entry_points_are_declared_and_exported():
 
 
 def test_the_tile_sizes_are_the_headers():
-    txt = open(os.path.join(ROOT, "raytracegr.jl_amd", "csrc", "rtgr_lightcurve.hpp")).read()
-    for name, val in (("LC_WAVE", LC_WAVE), ("LC_RANGE", LC_RANGE), ("LC_LANE_SAMPLES", LC_LANE_SAMPLES), ("LC_MAX_RANGES", LC_MAX_RANGES), ("LC_PASS", LC_PASS)):
+    # the sizes are the one reduction's (rtgr_reduce.hpp), the record length the light curve's own
+    txt = open(os.path.join(ROOT, "raytracegr.jl_amd", "csrc", "rtgr_reduce.hpp")).read()
+    for name, val in (("RED_WAVE", LC_WAVE), ("RED_RANGE", LC_RANGE), ("RED_LANE_ITEMS", LC_LANE_SAMPLES), ("RED_MAX_RANGES", LC_MAX_RANGES), ("RED_PASS", LC_PASS)):
         assert re.search(r"constexpr \w+ " + name + r" = " + str(val) + r";", txt), name
-    assert "LC_TILE = LC_WAVE * LC_LANE_SAMPLES" in txt and LC_TILE == LC_WAVE * LC_LANE_SAMPLES
+    assert "RED_TILE = RED_WAVE * RED_LANE_ITEMS" in txt and LC_TILE == LC_WAVE * LC_LANE_SAMPLES
+    lc = open(os.path.join(ROOT, "raytracegr.jl_amd", "csrc", "rtgr_lightcurve.hpp")).read()
+    assert re.search(r"constexpr \w+ LC_REC = 6;", lc) and not re.search(r"constexpr \w+ (LC|RED)_(WAVE|RANGE|LANE_\w+|TILE|MAX_RANGES|PASS) =", lc)
 
 
 def test_struct_layout_in_ctypes_a_compiled_c_caller_and_the_julia_stub(tmp_path):

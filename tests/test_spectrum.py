@@ -157,13 +157,19 @@ def test_the_entry_points_are_declared_and_exported():
 
 
 def test_the_tile_sizes_are_the_headers():
-    txt = open(os.path.join(ROOT, "raytracegr.jl_amd", "csrc", "rtgr_spectrum.hpp")).read()
-    for name, val in (("SPEC_WAVE", SPEC_WAVE), ("SPEC_RANGE", SPEC_RANGE), ("SPEC_LANE_BINS", SPEC_LANE_BINS), ("SPEC_PASS", SPEC_PASS), ("SPEC_REC", SPEC_REC)):
+    # the sizes are the one reduction's (rtgr_reduce.hpp), the record length the spectra's own
+    csrc = os.path.join(ROOT, "raytracegr.jl_amd", "csrc")
+    txt = open(os.path.join(csrc, "rtgr_reduce.hpp")).read()
+    for name, val in (("RED_WAVE", SPEC_WAVE), ("RED_RANGE", SPEC_RANGE), ("RED_LANE_ITEMS", SPEC_LANE_BINS), ("RED_PASS", SPEC_PASS), ("RED_MAX_RANGES", LC_MAX_RANGES)):
         assert re.search(r"constexpr \w+ " + name + r" = " + str(val) + r";", txt), name
-    assert "SPEC_TILE = SPEC_WAVE * SPEC_LANE_BINS" in txt and SPEC_TILE == SPEC_WAVE * SPEC_LANE_BINS
-    assert "lc_pixel_weight(" in open(os.path.join(ROOT, "raytracegr.jl_amd", "csrc", "rtgr_spectrum.hip")).read()     # (called, not copied)
-    lc = open(os.path.join(ROOT, "raytracegr.jl_amd", "csrc", "rtgr_lightcurve.hpp")).read()
-    assert re.search(r"constexpr \w+ LC_MAX_RANGES = " + str(LC_MAX_RANGES) + ";", lc)
+    assert "RED_TILE = RED_WAVE * RED_LANE_ITEMS" in txt and SPEC_TILE == SPEC_WAVE * SPEC_LANE_BINS
+    spec = open(os.path.join(csrc, "rtgr_spectrum.hpp")).read()
+    assert re.search(r"constexpr \w+ SPEC_REC = " + str(SPEC_REC) + ";", spec) and not re.search(r"constexpr \w+ (SPEC|RED)_(WAVE|RANGE|LANE_\w+|TILE|PASS) =", spec)
+    # the pixel weight: its defining body stands in one file of csrc/, the models call it, and no .hip file holds a copy of its expression
+    texts = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".hpp"))}
+    assert [f for f, t in texts.items() if re.search(r"RTGR_DEV double pixel_weight\(", t)] == ["rtgr_reduce.hpp"]
+    assert "pixel_weight(" in texts["rtgr_spectrum.hip"] and "pixel_weight(" in texts["rtgr_lightcurve.hip"]
+    assert [f for f, t in texts.items() if "W.scale / (s * sqrt(s))" in t] == ["rtgr_reduce.hpp"]
 
 
 def test_struct_layout_in_ctypes_a_compiled_c_caller_and_the_julia_stub(tmp_path):

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Device code of a parent revision against the working tree, kernel by kernel — the proof a refactor of the device headers owes.
 
-    python tools/listing_diff.py <parent-rev> [--unit NAME ...] [--user-units] [--jobs N]
+    python tools/listing_diff.py <parent-rev> [--unit NAME ...] [--user-units] [--jobs N] [--rename OLD=NEW ...] [--show]
 
 For every kernel unit of build.py (UNITS minus HOST_ONLY_UNITS; --unit picks some) the device listing is made the way the first step
 of build.compile_via_listing makes it (FLAGS, the fixed -cuid, --cuda-device-only -S), once from a `git worktree` of <parent-rev>
 under a temporary directory and once from the working tree.  --user-units adds two run-time units (a source of examples/ pasted into
 rtgr_user_unit.hip.in by each tree's own user_metric.py: its paste_source, FLAGS and unit_defines): SCHWARZSCHILD_ISOTROPIC declared
 stationary, and the objects of SHAPES_WITH_REACH for Kerr–Schild as written, a = 0.  A unit that only one side has counts as differing.
+Kernels are paired by symbol; --rename 'lc_sum_kernel<double>=reduce_sum_kernel<rtgr::LcModel<double>>' pairs a parent's kernel with its
+successor of another name (the names the table prints), and --show lists, for a pair whose histograms differ, the opcodes that do.
 
 Printed per kernel (the table of profiles/grid/refactor_isa.md): instruction count, whether the opcode histogram is the same — whole
 histograms are compared, no opcode is singled out —, vgpr / sgpr / agpr / scratch / LDS from the code object metadata, and whether the
@@ -119,8 +121,11 @@ def demangle(names):
         return {n: n for n in names}
 
 
-def compare(parent_dir, branch_dir, names):
-    """prints the table and the hashes; names: {unit: which sides have it}; -> number of listings that are not byte-identical on both sides"""
+def compare(parent_dir, branch_dir, names, renames=(), show=False):
+    """prints the table and the hashes; names: {unit: which sides have it}; renames: [(parent kernel, branch kernel)] by the names the
+    table prints, spaces ignored — the pair is compared with the branch's symbol read as the parent's; -> number of listings that are
+    not byte-identical on both sides"""
+    renames = {o.replace(" ", ""): n.replace(" ", "") for o, n in renames}
     print("| unit | kernel | instructions parent / branch | opcode histogram | vgpr | sgpr | agpr | scratch | lds | listing |")
     print("|---|---|---|---|---|---|---|---|---|---|")
     hashes, differing = [], 0
@@ -136,7 +141,13 @@ def compare(parent_dir, branch_dir, names):
         differing += pt != bt
         pk, bk = kernels_of(pt), kernels_of(bt)
         pretty = demangle(list(pk) + [k for k in bk if k not in pk])
-        for k in list(pk) + [k for k in bk if k not in pk]:
+        bare = {k: v.replace(" ", "") for k, v in pretty.items()}
+        heir = {k: next((b for b in bk if b not in pk and bare[b] == renames.get(bare[k])), None) for k in pk if k not in bk}
+        for k in list(pk) + [k for k in bk if k not in pk and k not in heir.values()]:
+            if k in heir and heir[k]:
+                b = heir[k]
+                bk[k] = (bk[b][0].replace(b, k),) + bk[b][1:]
+                pretty[k] += "` -> `" + pretty[b]
             if k not in pk or k not in bk:
                 print(f"| {name} | `{pretty[k]}` | {'only in the ' + ('parent' if k in pk else 'branch')} | | | | | | | |")
                 continue
@@ -144,6 +155,8 @@ def compare(parent_dir, branch_dir, names):
             same = "byte-identical" if ptxt == btxt else ("schedule differs" if ph == bh else "DIFFERS")
             print(f"| {name} | `{pretty[k]}` | {pn} / {bn} | {'identical' if ph == bh else 'DIFFERS'} | "
                   + " | ".join(f"{pr[r]} / {br[r]}" for r, _ in RESOURCES) + f" | {same} |")
+            if show and ph != bh:
+                print("|  |  | " + ", ".join(f"{op} {ph[op]} / {bh[op]}" for op in sorted(set(ph) | set(bh)) if ph[op] != bh[op]) + " | | | | | | | |")
     print("\n| unit | parent | branch | whole listing |\n|---|---|---|---|")
     for name, p, b in hashes:
         print(f"| `{name}` | `{p}` | `{b}` | {'byte-identical' if p == b and p != '—' else 'differs'} |")
@@ -156,6 +169,9 @@ def main():
     ap.add_argument("--unit", action="append", default=[], help="unit name without .hip (repeatable); default: every kernel unit")
     ap.add_argument("--user-units", action="store_true", help="also two run-time units built from examples/")
     ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 4))
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="pair the parent's kernel OLD with the branch's NEW (the names the table prints; repeatable)")
+    ap.add_argument("--show", action="store_true", help="for a pair whose histograms differ, print the opcodes that do (parent / branch)")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory(prefix="rtgr_listing_diff_") as tmp:
         tree, pdir, bdir = (os.path.join(tmp, d) for d in ("parent", "listings_parent", "listings_branch"))
@@ -169,7 +185,7 @@ def main():
                 for n, _, _ in jobs:
                     names.setdefault(n, []).append(side)
             run_jobs(pj + bj, max(1, min(16, a.jobs)))
-            differing = compare(pdir, bdir, names)
+            differing = compare(pdir, bdir, names, [r.split("=", 1) for r in a.rename], a.show)
         finally:
             subprocess.call(["git", "-C", ROOT, "worktree", "remove", "--force", tree])
     return 1 if differing else 0
