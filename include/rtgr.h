@@ -899,6 +899,120 @@ int rtgr_eval_spectrum_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtg
 int rtgr_eval_spectrum_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_spectrum* spec,
                            const float* xyg /* n x 3 */, uint64_t n, double* axis /* nb */, int64_t* bin /* n */, double* val);
 
+/* ---- polarized disk images: Stokes Q, U by Walker-Penrose transport -----------------------------------------------------------------
+ * AN EXTENSION.  In Kerr the parallel transport of a polarization vector f along a null geodesic has a closed first integral, the
+ * Walker-Penrose constant.  So the linear polarization a camera sees of a disk pixel is a function of the two ray states a traced frame
+ * already holds — the start state and state_end on the disk: one more small kernel around the untouched trace.
+ *
+ * The model (csrc/rtgr_polarization.hpp restates it; everything in the entry point's scalar type; no operation of it is fused).
+ * Coordinates are the library's Kerr-Schild ones, (t, x, y, z); the metric is RTGR_KS_TRUE with the scene's `a` (the forms do not contain
+ * M); RTGR_MINKOWSKI runs the same code with a = 0.
+ *   Scalars and 1-forms.  pw^2 = x^2 + y^2, r the textbook Kerr radius: r^2 = (q + sqrt(q^2 + 4 a^2 z^2)) / 2, q = x^2 + y^2 + z^2 - a^2.
+ *     dr     = (2 r^2 x, 2 r^2 y, 2 r^2 z + 2 a^2 z) / (4 r^3 - 2 q r)   on (dx, dy, dz)
+ *     c      = z / r,   dc = dz / r - (z / r^2) dr,   s^2 = 1 - c^2
+ *     dphi~  = (x dy - y dx) / pw^2 + a dr / (r^2 + a^2)
+ *     w1     = dt - a s^2 dphi~          (= l - dr, l the metric's own null covector (1, (r x + a y)/(r^2 + a^2), (r y - a x)/(r^2 + a^2), z/r))
+ *     w2     = (r^2 + a^2) dphi~ - a dt - a dr
+ *   The two 2-forms.   Y = -a c dr^w1 + r dc^w2  (Killing-Yano);   h = -r dr^w1 - a c dc^w2  (its dual, conformal Killing-Yano).
+ *   The constants.     For a null geodesic with tangent k and a vector f parallel-transported along it with g(k, f) = 0,
+ *                      kappa_1 = Y_ab k^a f^b and kappa_2 = h_ab k^a f^b are constant along the ray.  Adding a multiple of k to f changes
+ *                      neither; rescaling or reversing k scales both ends alike, so the traced ray's own past-directed tangent is used
+ *                      at both ends as it is.
+ *   Axis.              s^2 dphi~ is evaluated as (x dy - y dx)/(r^2 + a^2) + a s^2 dr/(r^2 + a^2) — regular on the axis — and
+ *                      (r^2 + a^2) dphi~ as (r^2 + a^2)(x dy - y dx)/pw^2 + a dr: only this term keeps a 1/pw^2.  A point with
+ *                      pw^2 <= 4096 eps (r^2 + a^2) is flagged INVALID (the forms are not evaluated there).  The disk is never there;
+ *                      an observer on the axis gets NaN planes.
+ *   The emitter's triad at the ray's end on the disk.  u = u_emit of "disk emission" above (the same device functions: KEPLER, RIGID).
+ *     cross(v, w)_a = -sqrt(-det g) eps_abcd u^b v^c w^d (eps_0123 = +1), raised with g^{-1}: the convention of e_right = look x up.
+ *     e_z'   = normalise(d_z + g(d_z, u) u)
+ *     e_rho' = normalise of (0, x, y, 0)/pw made orthogonal to u and e_z'
+ *     e_phi' = cross(e_z', e_rho')
+ *     p = k_end + g(k_end, u) u,   p^ = p / sqrt(g(p, p))
+ *   The emission law (rtgr_polarization).
+ *     RTGR_POL_SCATTER  an electron-scattering atmosphere, the electric vector in the disk plane:  f_em = normalise(cross(p^, e_z')),
+ *                       mu = |g(p^, e_z')|,  delta = deg0 (1 - mu) / (1 + deg1 mu),  aux = mu.
+ *     RTGR_POL_FIELD    synchrotron emission in an ordered field B^ = normalise(B_rho e_rho' + B_phi e_phi' + B_z e_z'):
+ *                       f_em = normalise(cross(p^, B^)),  delta = deg0,  aux = sin zeta = |cross(p^, B^)|.
+ *     The pixel is INVALID if the emitter is invalid or |cross|^2 <= 4096 eps (the direction is undefined): q = u = 0 there if delta
+ *     is finite, else NaN.  aux (and the hook's kappa, f_em, delta) is written before validity is known: at an invalid point it holds
+ *     whatever the formulas give there — finite, infinite or NaN — and means nothing; `valid` of the hook, or q = u = 0, tells.
+ *   At the camera.  State x_0, k_0 = (-e_0 + n)/sqrt(2); the frame record of `obs` (e_0, e_right, e_up, e_look).
+ *     n = sqrt(2) k_0 + e_0,   e^_y = normalise(e_up - g(e_up, n) n),   e^_x = normalise(e_right - g(e_right, n) n - g(e_right, e^_y) e^_y)
+ *     (alpha, beta) solve   kappa_1 = alpha Y(k_0, e^_x) + beta Y(k_0, e^_y),   kappa_2 = alpha h(k_0, e^_x) + beta h(k_0, e^_y).
+ *     THE OUTPUT is the fractional Stokes pair, its position angle chi measured from e^_x towards e^_y (f = cos chi e^_x + sin chi e^_y):
+ *       q = delta (alpha^2 - beta^2) / (alpha^2 + beta^2) = delta cos 2 chi,     u = 2 delta alpha beta / (alpha^2 + beta^2) = delta sin 2 chi.
+ *     So turning `up` by psi towards e_right (up' = cos psi up + sin psi right) turns chi by +psi: (q, u) -> delta (cos 2(chi+psi), sin 2(chi+psi)).
+ *     A degenerate screen basis (the squared norm of a projected vector <= 4096 eps) or an invalid frame gives NaN in q, u.
+ *   Pixels off the disk get NaN in every plane.
+ *
+ * rtgr_polarization_device_*: the stage alone over planes already on the device — d_hit32 (n), d_state0 and d_state_end (n x 8 each:
+ * the rays' start states, rtgr_make_observer_canvas_device_*'s, are READ, never regenerated) — into d_q, d_u (n each) and d_aux (n, may
+ * be NULL).  It only enqueues (one small frame kernel, then the polarization kernel) and needs the stream's frame scratch for the
+ * observer's record (512 bytes, grow-only).
+ * rtgr_trace_polarized_device_* / rtgr_trace_polarized_* (host pointers): the arguments of rtgr_trace_observer_* with `emit` required,
+ * plus `pol` and the three planes.  rgb, d_g, every per-ray output and the counters are rtgr_trace_observer_*'s bit for bit; the
+ * polarization kernel runs on each batch's window behind the emission kernel.  They only enqueue, with one synchronisation when `ctr` is
+ * given; capturable with ctr == NULL once workspace and scratch exist.  The result does not depend on max_batch_rays or on the stream.
+ * rtgr_eval_polarization_* (blocking, host pointers): the polarization kernel itself in point mode at n pairs (s0, s_end) under `obs`:
+ * kappa (n x 2), f_em (n x 4), aux, delta, q, u (n each), valid (n ints).  Any output may be NULL.
+ * rtgr_eval_walker_penrose_* (blocking, host pointers): kappa (n x 2) = (Y(k, f), h(k, f)) at n states s = (x, k) and n vectors f, by
+ * the kernel's own Y and h (NaN where the point is on the axis).
+ *   RTGR_ERR_BAD_ARG (with a message; the outputs are left untouched): a null pol, emit, obs, d_q, d_u or input plane; an unknown kind;
+ * flags or reserved != 0; a non-finite deg0, deg1 or field; deg0 < 0; SCATTER with deg1 <= -1 or a non-zero field; FIELD with a zero
+ * field; a scene metric other than RTGR_KS_TRUE or RTGR_MINKOWSKI, with or without RTGR_METRIC_GENERIC (RTGR_KS_REF's radius is not
+ * Kerr's: the constants do not exist; likewise RTGR_GRID, RTGR_USER and 4-D grids); everything rtgr_trace_emission_* and
+ * rtgr_trace_observer_* refuse.
+ *   Out of scope: the plane camera (obs == NULL); anti-aliasing; Q(t), U(t) of the hot spot and polarized spectra (the planes are shaped
+ * so that a later change can feed them to the frame reduction in place of the centroid weights); Faraday rotation, circular
+ * polarization, limb darkening; grids, RTGR_KS_REF, user metrics; the sharded, frames-in-flight, pixel-array and single-ray entries. */
+enum rtgr_polarization_kind { RTGR_POL_SCATTER = 0, RTGR_POL_FIELD = 1 };
+typedef struct rtgr_polarization {
+    uint32_t kind;        /* rtgr_polarization_kind */
+    uint32_t flags;       /* 0 */
+    double deg0;          /* degree scale, >= 0 */
+    double deg1;          /* SCATTER: delta = deg0 (1 - mu) / (1 + deg1 mu), > -1; FIELD: ignored */
+    double field[3];      /* FIELD: B_rho, B_phi, B_z in the emitter's triad (any normalisation); SCATTER: 0 */
+    double reserved[2];   /* 0 */
+} rtgr_polarization;      /* 64 bytes: kind 0, flags 4, deg0 8, deg1 16, field 24, reserved 48 */
+int rtgr_polarization_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_polarization* pol,
+                                 const rtgr_observer* obs, uint64_t ni, uint64_t nj, const uint32_t* d_hit32 /* n */,
+                                 const double* d_state0 /* n x 8 */, const double* d_state_end /* n x 8 */, double* d_q /* n */,
+                                 double* d_u /* n */, double* d_aux /* n, may be NULL */, void* stream);
+int rtgr_polarization_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_polarization* pol,
+                                 const rtgr_observer* obs, uint64_t ni, uint64_t nj, const uint32_t* d_hit32 /* n */,
+                                 const float* d_state0 /* n x 8 */, const float* d_state_end /* n x 8 */, float* d_q /* n */,
+                                 float* d_u /* n */, float* d_aux /* n, may be NULL */, void* stream);
+int rtgr_trace_polarized_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                    uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                                    const rtgr_polarization* pol, double* d_rgb, const rtgr_ray_outputs* out, double* d_g /* n, may be NULL */,
+                                    double* d_q /* n */, double* d_u /* n */, double* d_aux /* n, may be NULL */, rtgr_counters* ctr,
+                                    void* stream);
+int rtgr_trace_polarized_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                    uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                                    const rtgr_polarization* pol, float* d_rgb, const rtgr_ray_outputs* out, float* d_g /* n, may be NULL */,
+                                    float* d_q /* n */, float* d_u /* n */, float* d_aux /* n, may be NULL */, rtgr_counters* ctr,
+                                    void* stream);
+int rtgr_trace_polarized_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                             uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                             const rtgr_polarization* pol, double* rgb, const rtgr_ray_outputs* out, double* g /* n, may be NULL */,
+                             double* q /* n */, double* u /* n */, double* aux /* n, may be NULL */, rtgr_counters* ctr);
+int rtgr_trace_polarized_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                             uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit,
+                             const rtgr_polarization* pol, float* rgb, const rtgr_ray_outputs* out, float* g /* n, may be NULL */,
+                             float* q /* n */, float* u /* n */, float* aux /* n, may be NULL */, rtgr_counters* ctr);
+int rtgr_eval_polarization_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_polarization* pol,
+                               const rtgr_observer* obs, const double* s0 /* n x 8 */, const double* s_end /* n x 8 */, uint64_t n,
+                               double* kappa /* n x 2 */, double* f_em /* n x 4 */, double* aux /* n */, double* delta /* n */,
+                               double* q /* n */, double* u /* n */, int* valid /* n */);
+int rtgr_eval_polarization_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_polarization* pol,
+                               const rtgr_observer* obs, const float* s0 /* n x 8 */, const float* s_end /* n x 8 */, uint64_t n,
+                               float* kappa /* n x 2 */, float* f_em /* n x 4 */, float* aux /* n */, float* delta /* n */,
+                               float* q /* n */, float* u /* n */, int* valid /* n */);
+int rtgr_eval_walker_penrose_f64(rtgr_context* ctx, const rtgr_scene* scene, const double* s /* n x 8 */, const double* f /* n x 4 */,
+                                 uint64_t n, double* kappa /* n x 2 */);
+int rtgr_eval_walker_penrose_f32(rtgr_context* ctx, const rtgr_scene* scene, const float* s /* n x 8 */, const float* f /* n x 4 */,
+                                 uint64_t n, float* kappa /* n x 2 */);
+
 /* ---- camera: make_canvas (src/RayTraceGR.jl:457-478) on the device ------------------------------------------
  * Writes n x 8 ray states (pos, null past-directed 4-velocity) for rows [j0, j1).  Device / host variants. */
 int rtgr_make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni,

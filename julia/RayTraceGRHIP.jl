@@ -34,6 +34,7 @@
 #   RtgrObserver    176   pos 0, vel 32, look 64, up 96, fov_x 128, fov_y 136, orbit 144, kind 152, projection 156, flags 160, pad 164, max_batch_rays 168
 #   RtgrHotSpot      80   rho_s 0, phi0 8, sigma 16, cut 24, amp 32, g_power 40, t_start 48, dt 56, nt 64, flags 72, pad 76
 #   RtgrSpectrum     80   kind 0, flags 4, nb 8, lo 16, hi 24, amp 32, alpha 40, rho_min 48, rho_max 56, g_power 64, reserved 72
+#   RtgrPolarization 64   kind 0, flags 4, deg0 8, deg1 16, field 24, reserved 48
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64         (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -182,6 +183,14 @@ struct RtgrSpectrum            # a line profile or a thermal spectrum of the emi
     g_power::Float64            # line: q of the weight g^q
     reserved::Float64           # 0
 end
+struct RtgrPolarization        # the emission law of a polarized disk image (rtgr_trace_polarized_f64 / _f32)
+    kind::UInt32                # RTGR_POL_SCATTER / RTGR_POL_FIELD
+    flags::UInt32               # 0
+    deg0::Float64               # degree scale, >= 0
+    deg1::Float64               # SCATTER: delta = deg0 (1 - mu) / (1 + deg1 mu), > -1
+    field::NTuple{3,Float64}    # FIELD: B_rho, B_phi, B_z in the emitter's triad; SCATTER: 0
+    reserved::NTuple{2,Float64} # 0
+end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
     lambda_end::Ptr{Cvoid}
@@ -224,6 +233,8 @@ const RTGR_SPEC_LINE = UInt32(0)
 const RTGR_SPEC_THERMAL = UInt32(1)
 const RTGR_SPEC_LOG = UInt32(1)
 const RTGR_SPEC_NU3 = UInt32(2)
+const RTGR_POL_SCATTER = UInt32(0)
+const RTGR_POL_FIELD = UInt32(1)
 
 function check(rc)
     rc < 0 && error("librtgr_hip: ", unsafe_string(ccall((:rtgr_last_error, librtgr), Cstring, ())))
@@ -1117,6 +1128,121 @@ function spectrum(metric, objs, observer::RtgrObserver, ni::Integer, nj::Integer
         end
     end
     (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), g, axis, fab
+end
+
+"""
+    Polarization(kind; deg0 = 1, deg1 = 0, field = (0, 0, 0)) -> RtgrPolarization
+
+The emission law of a polarized disk image (include/rtgr.h "polarized disk images").  `kind = RTGR_POL_SCATTER`: an electron-scattering
+atmosphere, the electric vector in the disk plane, degree `deg0 (1 - mu) / (1 + deg1 mu)`.  `kind = RTGR_POL_FIELD`: synchrotron emission
+in the ordered field `field = (B_rho, B_phi, B_z)` of the emitter's triad, degree `deg0`.
+"""
+function Polarization(kind::UInt32; deg0::Real = 1, deg1::Real = 0, field = (0.0, 0.0, 0.0))
+    RtgrPolarization(kind, UInt32(0), Float64(deg0), Float64(deg1), (Float64(field[1]), Float64(field[2]), Float64(field[3])), (0.0, 0.0))
+end
+
+"""
+    trace_rays_polarized(metric, objs, observer, ni, nj, emission, pol; T = Float64, ctx = nothing) -> ((R, G, B), g, q, u, aux)
+
+A POLARIZED frame of an emitting disk (`rtgr_trace_polarized_f64/_f32`) — an extension: the frame of `trace_rays_observer` with
+`emission`, bit for bit, plus the fractional Stokes pair `(q, u)` by Walker-Penrose transport and `aux` (mu or sin zeta), `ni x nj`
+each, NaN off the disk.  The metric must be `KerrSchild(M, a)` with the textbook radius, or flat space.  The observer's frame is asked
+for first: an invalid frame or a refused record is an error.
+"""
+function trace_rays_polarized(metric, objs, observer::RtgrObserver, ni::Integer, nj::Integer, emission::RtgrDiskEmission, pol::RtgrPolarization;
+                              T::Type = Float64, ctx = nothing)
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("trace_rays_polarized has no CPU counterpart in the reference: ", why)
+    opt = solver_of(T)
+    obs = Ref(observer)
+    emit = Ref(emission)
+    pl = Ref(pol)
+    observer_frame(scene, obs; T = T, ctx = ctx)
+    rgb = Array{T}(undef, ni, nj, 3)                # plane-major: rgb[:, :, c] is plane c
+    g = Array{T}(undef, ni, nj)
+    q = Array{T}(undef, ni, nj)
+    u = Array{T}(undef, ni, nj)
+    aux = Array{T}(undef, ni, nj)
+    ctr = Ref{RtgrCounters}()
+    GC.@preserve rgb g q u aux begin
+        if T === Float64
+            check(ccall((:rtgr_trace_polarized_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission},
+                         Ptr{RtgrPolarization}, Ptr{Float64}, Ptr{RtgrRayOutputs}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                         Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, emit, pl, pointer(rgb), C_NULL, pointer(g), pointer(q), pointer(u),
+                        pointer(aux), ctr))
+        else
+            check(ccall((:rtgr_trace_polarized_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission},
+                         Ptr{RtgrPolarization}, Ptr{Float32}, Ptr{RtgrRayOutputs}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32},
+                         Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, emit, pl, pointer(rgb), C_NULL, pointer(g), pointer(q), pointer(u),
+                        pointer(aux), ctr))
+        end
+    end
+    (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), g, q, u, aux
+end
+
+"""
+    eval_polarization(metric, objs, emission, pol, observer, s0, s_end; ctx = nothing) -> (kappa, f_em, aux, delta, q, u, valid)
+
+The polarization kernel itself at `n` pairs of ray states (`rtgr_eval_polarization_f64/_f32`, blocking): `s0` (`8 x n`) at the camera,
+the observer's own states, and `s_end` (`8 x n`) on the disk.  `kappa` is `2 x n`, `f_em` `4 x n`, the others have length `n`.
+"""
+function eval_polarization(metric, objs, emission::RtgrDiskEmission, pol::RtgrPolarization, observer::RtgrObserver, s0::Matrix{T}, s_end::Matrix{T};
+                           ctx = nothing) where {T<:Union{Float64,Float32}}
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("eval_polarization: ", why)
+    size(s0) == size(s_end) && size(s0, 1) == 8 || error("eval_polarization: s0 and s_end must both be 8 x n")
+    n = size(s0, 2)
+    obs = Ref(observer)
+    emit = Ref(emission)
+    pl = Ref(pol)
+    observer_frame(scene, obs; T = T, ctx = ctx)
+    kappa = Array{T}(undef, 2, n); f_em = Array{T}(undef, 4, n)
+    aux = Array{T}(undef, n); delta = Array{T}(undef, n); q = Array{T}(undef, n); u = Array{T}(undef, n)
+    valid = Array{Cint}(undef, n)
+    GC.@preserve s0 s_end kappa f_em aux delta q u valid begin
+        if T === Float64
+            check(ccall((:rtgr_eval_polarization_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrDiskEmission}, Ptr{RtgrPolarization}, Ptr{RtgrObserver}, Ptr{Float64}, Ptr{Float64}, UInt64,
+                         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+                        handle(ctx), scene, emit, pl, obs, pointer(s0), pointer(s_end), n, pointer(kappa), pointer(f_em), pointer(aux),
+                        pointer(delta), pointer(q), pointer(u), pointer(valid)))
+        else
+            check(ccall((:rtgr_eval_polarization_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrDiskEmission}, Ptr{RtgrPolarization}, Ptr{RtgrObserver}, Ptr{Float32}, Ptr{Float32}, UInt64,
+                         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cint}),
+                        handle(ctx), scene, emit, pl, obs, pointer(s0), pointer(s_end), n, pointer(kappa), pointer(f_em), pointer(aux),
+                        pointer(delta), pointer(q), pointer(u), pointer(valid)))
+        end
+    end
+    kappa, f_em, aux, delta, q, u, map(v -> v != 0, valid)
+end
+
+"""
+    eval_walker_penrose(metric, s, f; ctx = nothing) -> kappa
+
+The two Walker-Penrose constants `(Y(k, f), h(k, f))` (`2 x n`) at `n` states `s = (x, k)` (`8 x n`) and `n` vectors `f` (`4 x n`), by the
+polarization kernel's own Killing-Yano forms (`rtgr_eval_walker_penrose_f64/_f32`, blocking); NaN on the axis.
+"""
+function eval_walker_penrose(metric, s::Matrix{T}, f::Matrix{T}; ctx = nothing) where {T<:Union{Float64,Float32}}
+    scene, why = scene_of(metric, RayTraceGR.Object{T}[], ctx)
+    scene === nothing && error("eval_walker_penrose: ", why)
+    size(s, 1) == 8 && size(f, 1) == 4 && size(s, 2) == size(f, 2) || error("eval_walker_penrose: s must be 8 x n and f 4 x n")
+    n = size(s, 2)
+    kappa = Array{T}(undef, 2, n)
+    GC.@preserve s f kappa begin
+        if T === Float64
+            check(ccall((:rtgr_eval_walker_penrose_f64, librtgr), Cint, (Ctx, Ptr{RtgrScene}, Ptr{Float64}, Ptr{Float64}, UInt64, Ptr{Float64}),
+                        handle(ctx), scene, pointer(s), pointer(f), n, pointer(kappa)))
+        else
+            check(ccall((:rtgr_eval_walker_penrose_f32, librtgr), Cint, (Ctx, Ptr{RtgrScene}, Ptr{Float32}, Ptr{Float32}, UInt64, Ptr{Float32}),
+                        handle(ctx), scene, pointer(s), pointer(f), n, pointer(kappa)))
+        end
+    end
+    kappa
 end
 
 """

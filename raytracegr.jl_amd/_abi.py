@@ -35,6 +35,8 @@ PROJ_PERSPECTIVE, PROJ_EQUIRECT = 0, 1
 SPEC_LINE, SPEC_THERMAL = 0, 1
 SPEC_LOG, SPEC_NU3 = 1, 2
 RTGR_SPECTRUM_MAX_BINS = 1 << 16
+# enum rtgr_polarization_kind
+POL_SCATTER, POL_FIELD = 0, 1
 # enum rtgr_status
 OK, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NAN_INPUT, ERR_NOT_INIT = 0, -1, -2, -3, -4, -5
 
@@ -150,6 +152,12 @@ class rtgr_spectrum(C.Structure):
 RtgrSpectrum = rtgr_spectrum
 
 
+class rtgr_polarization(C.Structure):
+    """the emission law of a polarized disk image (rtgr_trace_polarized_*): 64 bytes"""
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("deg0", C.c_double), ("deg1", C.c_double), ("field", C.c_double * 3),
+                ("reserved", C.c_double * 2)]
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -184,6 +192,9 @@ EXPORTS = [
     "rtgr_trace_light_curve_f64", "rtgr_trace_light_curve_f32", "rtgr_eval_hot_spot_f64", "rtgr_eval_hot_spot_f32",
     "rtgr_spectrum_device_f64", "rtgr_spectrum_device_f32", "rtgr_trace_spectrum_device_f64", "rtgr_trace_spectrum_device_f32",
     "rtgr_trace_spectrum_f64", "rtgr_trace_spectrum_f32", "rtgr_eval_spectrum_f64", "rtgr_eval_spectrum_f32",
+    "rtgr_polarization_device_f64", "rtgr_polarization_device_f32", "rtgr_trace_polarized_device_f64", "rtgr_trace_polarized_device_f32",
+    "rtgr_trace_polarized_f64", "rtgr_trace_polarized_f32", "rtgr_eval_polarization_f64", "rtgr_eval_polarization_f32",
+    "rtgr_eval_walker_penrose_f64", "rtgr_eval_walker_penrose_f32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -296,6 +307,17 @@ def _declare(lib):
             ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_spectrum), vp,
             P(rtgr_ray_outputs), vp, vp, P(rtgr_counters)]
         getattr(lib, f"rtgr_eval_spectrum_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_spectrum), vp, u64, vp, vp, vp]
+        getattr(lib, f"rtgr_polarization_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_polarization), P(rtgr_observer), u64, u64, vp, vp, vp, vp, vp, vp, vp]
+        getattr(lib, f"rtgr_trace_polarized_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_polarization), vp,
+            P(rtgr_ray_outputs), vp, vp, vp, vp, P(rtgr_counters), vp]
+        getattr(lib, f"rtgr_trace_polarized_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_polarization), vp,
+            P(rtgr_ray_outputs), vp, vp, vp, vp, P(rtgr_counters)]
+        getattr(lib, f"rtgr_eval_polarization_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_polarization), P(rtgr_observer), vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        getattr(lib, f"rtgr_eval_walker_penrose_{suf}").argtypes = [ctx, P(rtgr_scene), vp, vp, u64, vp]
     lib.rtgr_texture_load.argtypes = [ctx, P(rtgr_texture_desc), vp, P(u64)]
     lib.rtgr_texture_unload.argtypes = [ctx, u64]
     lib.rtgr_eval_fastmath_f64.argtypes = [ctx, vp, u64, vp, vp]

@@ -810,6 +810,79 @@ def spectrum(metric, objs, observer, ni, nj, emission, spec, textures=None, r_es
     return res
 
 
+# ---- polarized disk images (include/rtgr.h "polarized disk images") -------------------------------------------------------------------
+def Polarization(kind, deg0=1.0, deg1=0.0, field=(0.0, 0.0, 0.0)):
+    """The emission law of a polarized disk image -> rtgr_polarization.  kind "scatter": an electron-scattering atmosphere, the electric
+    vector in the disk plane, degree deg0 (1 - mu) / (1 + deg1 mu); "field": synchrotron emission in the ordered field (B_rho, B_phi,
+    B_z) of the emitter's triad, degree deg0."""
+    kinds = {"scatter": _abi.POL_SCATTER, "field": _abi.POL_FIELD}
+    if kind not in kinds:
+        raise ValueError(f"Polarization: kind must be 'scatter' or 'field', got {kind!r}")
+    return _abi.rtgr_polarization(kind=kinds[kind], flags=0, deg0=float(deg0), deg1=float(deg1), field=(C.c_double * 3)(*[float(c) for c in field]),
+                                  reserved=(C.c_double * 2)(0.0, 0.0))
+
+
+def trace_polarized(metric, objs, observer, ni, nj, emission, polarization, textures=None, r_escape=0.0, opt=None, dtype=np.float64, ctx=None,
+                    details=False):
+    """A POLARIZED frame of an emitting disk (rtgr_trace_polarized_f64 / _f32) — an extension: trace_observer's frame with emission, bit
+    for bit, plus the fractional Stokes pair by Walker-Penrose transport (Kerr with its own radius, or flat space).  Raises ValueError
+    for an observer with no valid frame.  -> trace_observer's dict + q, u, aux [ni*nj] (NaN off the disk)."""
+    lib = _lib()
+    _valid_observer(metric, objs, observer, dtype, ctx)
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    n = ni * nj
+    sh = make_shade(textures, r_escape) if textures else None
+    res = dict(rgb=np.zeros((3, n), dtype), g=np.zeros(n, dtype), q=np.zeros(n, dtype), u=np.zeros(n, dtype), aux=np.zeros(n, dtype))
+    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
+    ctr = rtgr_counters()
+    fn = lib.rtgr_trace_polarized_f64 if dtype == np.float64 else lib.rtgr_trace_polarized_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(observer), ni, nj, None if sh is None else C.byref(sh),
+                       None if emission is None else C.byref(emission), None if polarization is None else C.byref(polarization),
+                       res["rgb"].ctypes.data, outs, res["g"].ctypes.data, res["q"].ctypes.data, res["u"].ctypes.data, res["aux"].ctypes.data,
+                       C.byref(ctr)))
+    res["counters"] = ctr.as_dict()
+    return res
+
+
+def eval_polarization(metric, objs, emission, polarization, observer, s0, s_end, dtype=np.float64, ctx=None):
+    """rtgr_eval_polarization_f64 / _f32: the polarization kernel at n pairs of ray states — s0 [n, 8] at the camera (the observer's own
+    states), s_end [n, 8] on the disk.  Raises ValueError for an observer with no valid frame.
+    -> dict(kappa [n, 2], f_em [n, 4], aux, delta, q, u [n], valid [n] bool)."""
+    lib = _lib()
+    _valid_observer(metric, objs, observer, dtype, ctx)
+    sc = make_scene(metric, objs, ctx)
+    a = np.ascontiguousarray(s0, dtype=dtype).reshape(-1, 8)
+    e = np.ascontiguousarray(s_end, dtype=dtype).reshape(-1, 8)
+    if a.shape != e.shape:
+        raise ValueError(f"eval_polarization: s0 and s_end must have the same shape, got {a.shape} and {e.shape}")
+    n = a.shape[0]
+    res = dict(kappa=np.zeros((n, 2), dtype), f_em=np.zeros((n, 4), dtype), aux=np.zeros(n, dtype), delta=np.zeros(n, dtype), q=np.zeros(n, dtype),
+               u=np.zeros(n, dtype))
+    valid = np.zeros(n, np.int32)
+    fn = lib.rtgr_eval_polarization_f64 if dtype == np.float64 else lib.rtgr_eval_polarization_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(emission), C.byref(polarization), C.byref(observer), a.ctypes.data, e.ctypes.data, n,
+                       res["kappa"].ctypes.data, res["f_em"].ctypes.data, res["aux"].ctypes.data, res["delta"].ctypes.data, res["q"].ctypes.data,
+                       res["u"].ctypes.data, valid.ctypes.data))
+    res["valid"] = valid != 0
+    return res
+
+
+def eval_walker_penrose(metric, objs, s, f, dtype=np.float64, ctx=None):
+    """rtgr_eval_walker_penrose_f64 / _f32: (Y(k, f), h(k, f)) [n, 2] at n states s [n, 8] = (x, k) and n vectors f [n, 4], by the
+    polarization kernel's own Killing-Yano forms (NaN on the axis)."""
+    lib = _lib()
+    sc = make_scene(metric, objs, ctx)
+    a = np.ascontiguousarray(s, dtype=dtype).reshape(-1, 8)
+    v = np.ascontiguousarray(f, dtype=dtype).reshape(-1, 4)
+    if a.shape[0] != v.shape[0]:
+        raise ValueError(f"eval_walker_penrose: s and f must have the same length, got {a.shape[0]} and {v.shape[0]}")
+    kap = np.zeros((a.shape[0], 2), dtype)
+    fn = lib.rtgr_eval_walker_penrose_f64 if dtype == np.float64 else lib.rtgr_eval_walker_penrose_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), a.ctypes.data, v.ctypes.data, a.shape[0], kap.ctypes.data))
+    return kap
+
+
 def trace_ray(metric, objs, cb, p, opt=None, ctx=None):
     """Legacy single-pixel shape `trace_ray(metric, objs, cb, p)::Pixel` (test/runtests.jl:65-79).
     `cb` is accepted for signature parity and ignored: the callback is always
@@ -919,5 +992,5 @@ def example2(ni=200, nj=200, save=True, ctx=None):
 
 __all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
-           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "HotSpot", "eval_hot_spot", "light_curve", "Spectrum", "eval_spectrum", "spectrum", "dmetric", "christoffel", "geodesic", "example1", "example2",
+           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "HotSpot", "eval_hot_spot", "light_curve", "Spectrum", "eval_spectrum", "spectrum", "Polarization", "trace_polarized", "eval_polarization", "eval_walker_penrose", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

@@ -499,5 +499,48 @@ int spec_reduce_launch(const ReducePlanes<R>& P, const SpecDev& S, const PixelWe
 // … and the hook: the axis (nb), and bin and val at n triples (x, y, g), from the same device functions; any output may be null
 template <class R>
 int spec_points_launch(const R* d_xyg, uint64_t n, const SpecDev& S, double* d_axis, int64_t* d_bin, double* d_val, hipStream_t st);
+// polarized disk images (rtgr_polarize.hip; include/rtgr.h "polarized disk images").  The caller's rtgr_polarization as the kernel reads
+// it, converted by the host for one scalar type.
+template <class R>
+struct DevPolarization {
+    uint32_t kind, pad;
+    R deg0, deg1;
+    R field[3];
+};
+// the polarization kernel's argument block.  mode POL_FRAME: n pixels, hit32 given; q, u, aux: a plane each, every one optional.
+// POL_POINTS (rtgr_eval_polarization_*): n pairs (state0, state_end), every output optional.  POL_FORMS (rtgr_eval_walker_penrose_*): n
+// states (state0) and n vectors (fvec) into kappa.  The start states are read, never regenerated.
+enum PolMode : uint32_t { POL_FRAME = 0, POL_POINTS = 1, POL_FORMS = 2 };
+template <class R>
+struct PolArgs {
+    R* q;
+    R* u;
+    R* aux;
+    R* kappa;     // n x 2 (POL_POINTS, POL_FORMS)
+    R* f_em;      // n x 4 (POL_POINTS)
+    R* delta;     // n     (POL_POINTS)
+    int* valid;   // n     (POL_POINTS)
+    const uint32_t* hit32;
+    const R* state0;
+    const R* state_end;
+    const R* fvec;   // n x 4 (POL_FORMS)
+    uint64_t n;
+    uint32_t mode, pad;
+    DevScene<R> sc;
+    DevEmission<R> em;
+    DevPolarization<R> pol;
+    const ObsFrame<R>* obs;
+};
+template <class R>
+int polarize_launch(const PolArgs<R>& A, hipStream_t st);
+// what an observer trace applies to each batch behind the emission kernel when the call is rtgr_trace_polarized_*: the record and the
+// caller's three planes (whole frames; aux may be null)
+template <class R>
+struct PolStage {
+    DevPolarization<R> pol;
+    R* q = nullptr;
+    R* u = nullptr;
+    R* aux = nullptr;
+};
 
 }  // namespace rtgr

@@ -27,6 +27,8 @@
 //                           mode, then the reduction), the entry points as a Reduction each, the hook (kernels: rtgr_lightcurve.hip)
 //   rtgr_spectrum_host.hip  disk spectra: the checks of an rtgr_spectrum, the stage, the entry points as a Reduction each, the hook
 //                           (kernels: rtgr_spectrum.hip)
+//   rtgr_polarization_host.hip  polarized disk images: the checks of an rtgr_polarization, the stage alone, the polarized observer trace,
+//                           the two hooks (kernel: rtgr_polarize.hip)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -254,6 +256,12 @@ int shaded_check(const rtgr_camera* cam, const rtgr_aa* aa, const uint8_t* refin
 template <class R> int emission_resolve(const rtgr_scene* scene, const rtgr_shade* shade, const rtgr_disk_emission* emit, DevEmission<R>& em);
 // the observer camera (rtgr_observer_host.hip): the checks of an rtgr_observer against its scene, and the record the frame kernel reads
 template <class R> int observer_resolve(const rtgr_scene* scene, const rtgr_observer* obs, DevObserver<R>& ob);
+// … and its trace on device D, stream st; d_rgb, d_g and the members of `out` are pointers of that device.  pol (may be null; needs emit):
+// the polarization kernel on each batch's window behind the emission kernel (rtgr_trace_polarized_*, with its words in the refusals)
+template <class R>
+int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
+                      const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, rtgr_counters* ctr,
+                      hipStream_t st, const PolStage<R>* pol = nullptr);
 
 // ---- a traced frame of an emitting disk reduced to a table of (F, A, B) rows (rtgr_reduce_host.hip) -----------------------------------
 // The reduction scratch of a stream (StreamState::reduce) in one call, each block 256-aligned and an absent one no bytes.  Pure
@@ -460,6 +468,11 @@ template <class R> int spectrum_device(rtgr_context* ctx, const rtgr_scene* scen
 template <class R> int trace_spectrum_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_spectrum* spec, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, double* d_out, rtgr_counters* ctr, void* stream);
 template <class R> int trace_spectrum(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_spectrum* spec, R* rgb, const rtgr_ray_outputs* out, R* g, double* spectrum, rtgr_counters* ctr);
 template <class R> int eval_spectrum(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_spectrum* spec, const R* xyg, uint64_t n, double* axis, int64_t* bin, double* val);
+template <class R> int polarization_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_polarization* pol, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const uint32_t* d_hit32, const R* d_state0, const R* d_state_end, R* d_q, R* d_u, R* d_aux, void* stream);
+template <class R> int trace_polarized_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_polarization* pol, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, R* d_q, R* d_u, R* d_aux, rtgr_counters* ctr, void* stream);
+template <class R> int trace_polarized(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_polarization* pol, R* rgb, const rtgr_ray_outputs* out, R* g, R* q, R* u, R* aux, rtgr_counters* ctr);
+template <class R> int eval_polarization(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_polarization* pol, const rtgr_observer* obs, const R* s0, const R* s_end, uint64_t n, R* kappa, R* f_em, R* aux, R* delta, R* q, R* u, int* valid);
+template <class R> int eval_walker_penrose(rtgr_context* ctx, const rtgr_scene* scene, const R* s, const R* f, uint64_t n, R* kappa);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 

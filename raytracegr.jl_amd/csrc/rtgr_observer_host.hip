@@ -8,6 +8,7 @@ namespace rtgr {
 
 constexpr uint64_t OBS_DEFAULT_BATCH = 1ull << 22;   // rays per batch (rtgr_observer.max_batch_rays = 0), as rtgr_aa's
 constexpr EntryWords OBSERVER_WORDS = {"rtgr_trace_observer_*", "observer", true};
+constexpr EntryWords POLARIZED_WORDS = {"rtgr_trace_polarized_*", "observer", true};
 constexpr EntryWords OBSERVER_CANVAS_WORDS = {"rtgr_make_observer_canvas_device_*", "observer", false};
 constexpr const char* OBSERVER_CANVAS = "an observer frame";
 // (its metric must not depend on time through a 4-D grid: stationary_scene)
@@ -72,12 +73,14 @@ static int observer_trace_check(const rtgr_scene* scene, const rtgr_observer* ob
     return RTGR_OK;
 }
 
-// the call on device D, stream st; d_rgb, d_g and the members of `out` are pointers of that device
+// the call on device D, stream st; d_rgb, d_g and the members of `out` are pointers of that device.  pol (may be null): the polarization
+// kernel behind the emission kernel of each batch (rtgr_polarization_host.hip, which has checked the record against the scene)
 template <class R>
-static int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
-                             const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, rtgr_counters* ctr,
-                             hipStream_t st) {
+int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
+                      const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, rtgr_counters* ctr,
+                      hipStream_t st, const PolStage<R>* pol) {
     int rc;
+    const EntryWords& WORDS = pol ? POLARIZED_WORDS : OBSERVER_WORDS;
     if ((rc = observer_trace_check(scene, obs, ni, nj, emit, d_rgb, out, d_g))) return rc;
     DevObserver<R> ob;
     if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
@@ -93,7 +96,7 @@ static int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_s
     DeviceGuard guard(D.dev);
     if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
     bool capturing;
-    if ((rc = capture_check(st, OBSERVER_WORDS, ctr, &capturing))) return rc;
+    if ((rc = capture_check(st, WORDS, ctr, &capturing))) return rc;
     const uint64_t n = ni * nj;
     const uint64_t budget = obs->max_batch_rays ? obs->max_batch_rays : OBS_DEFAULT_BATCH;
     const uint64_t rows = budget / ni ? (budget / ni < nj ? budget / ni : nj) : 1;   // rows per batch
@@ -112,7 +115,7 @@ static int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_s
     {
         std::lock_guard<std::mutex> lk(D.mu);
         if ((rc = stationary_scene<R>(D, scene, sc, st, emit ? EMISSION_NEEDS_STATIONARY : OBSERVER_NEEDS_STATIONARY))) return rc;
-        if ((rc = frame_scratch(D, st, capturing, OBSERVER_WORDS, n, sizeof(R), need, align256((size_t)rows * ni * 8 * sizeof(R)), out, ctr, fs))) return rc;
+        if ((rc = frame_scratch(D, st, capturing, WORDS, n, sizeof(R), need, align256((size_t)rows * ni * 8 * sizeof(R)), out, ctr, fs))) return rc;
     }
     R* d_states = (R*)fs.ss->batch;
     ObsFrame<R>* d_frame = (ObsFrame<R>*)(fs.base + fs.at.obs);
@@ -141,6 +144,17 @@ static int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_s
             px.n = m; px.ni = ni; px.nj = nj;
             px.sc = &sc;
             if ((rc = after_trace<R>(D, st, after, px))) return rc;
+            if (pol) {   // the same window, the same start states: read, not regenerated
+                PolArgs<R> P;
+                std::memset(&P, 0, sizeof P);
+                P.q = pol->q + first; P.u = pol->u + first; P.aux = pol->aux ? pol->aux + first : nullptr;
+                P.hit32 = px.hit32; P.state0 = d_states; P.state_end = px.state_end;
+                P.n = m; P.mode = POL_FRAME;
+                P.sc = sc; P.em = em; P.pol = pol->pol; P.obs = d_frame;
+                std::lock_guard<std::mutex> lk(D.mu);
+                KernelTimer timer(D, st, 0);
+                if ((rc = polarize_launch<R>(P, st))) return rc;
+            }
         }
     }
     return counters_back(fs, ctr, st);
@@ -245,6 +259,7 @@ int api::eval_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_ob
     return RTGR_OK;
 }
 
+RTGR_INSTANTIATE_F64_F32(trace_observer_on);
 RTGR_INSTANTIATE_F64_F32(api::trace_observer_device);
 RTGR_INSTANTIATE_F64_F32(api::trace_observer);
 RTGR_INSTANTIATE_F64_F32(api::make_observer_canvas_device);
