@@ -1013,6 +1013,85 @@ int rtgr_eval_walker_penrose_f64(rtgr_context* ctx, const rtgr_scene* scene, con
 int rtgr_eval_walker_penrose_f32(rtgr_context* ctx, const rtgr_scene* scene, const float* s /* n x 8 */, const float* f /* n x 4 */,
                                  uint64_t n, float* kappa /* n x 2 */);
 
+/* ---- higher-order disk images: follow rays through the disk, order by order ---------------------------------------------------------
+ * AN EXTENSION.  The trace ends a ray at its first event, so an emitting disk is an opaque wall.  Here a ray that ends on the emitting
+ * disk D = (h, r_in, r_out) is carried through the slab and traced on; where it meets D again is the next ORDER of the image: order 1 is
+ * the lensed image of the far side and the underside, order >= 2 the photon ring.  The integrate kernels are untouched: every leg is an
+ * ordinary trace of caller-supplied states, and the way through the slab uses two things the library guarantees — a ray traced from a
+ * given state is that state's ray to the bit whatever is traced beside it, and a ray that starts inside an object ends with an event
+ * where it leaves it.
+ *
+ * The model (everything in the entry point's scalar type; no operation of the picture is fused).
+ *   Leg 0.  The frame of rtgr_trace_observer_* with `emit`: its rgb, state_end, hit32, status and g — or, with `state0` given, the same
+ *     of the caller's n = ni nj ray states in place of the observer's (as rtgr_trace_* takes them); `obs` may then be NULL: u_obs is the
+ *     static observer at the ray's start, the rule of rtgr_eval_disk_emission_*.
+ *   Continuing set after order k.  The pixels whose order-k leg has hit32 == emit->object (the emission kernel's own rule).
+ *   Crossing leg.  A trace of those end states in the scene S+ : the caller's metric and exactly ONE object, the inflated disk
+ *     D+ = (h + eta, r_in - eta, r_out + eta), eta = `margin` (0: h / 2).  The ray starts inside D+, at distance <= -eta, and ends with an
+ *     event on its surface — outside D, at distance eta.  The caller's other objects are NOT in S+: an object that pokes into the slab is
+ *     not seen from inside it.  The solver record is the caller's, and every leg runs lambda from lambda0 to lambda1 afresh.
+ *     A ray goes on iff its crossing leg ended with status RTGR_RAY_EVENT on object 1; any other ray stops there and contributes no
+ *     background (it is absorbed).
+ *   Continuation leg.  A trace of the crossing legs' end states in the caller's scene S: its hit32, status and state_end are order k + 1's.
+ *   Emission of order k.  "disk emission" above, evaluated by the emission kernel itself on the pair (the pixel's start state, its order-k
+ *     end state): g_k = (k_0 . u_obs) / (k_end,k . u_emit), with the e_0 of `obs` when it is given.  rtgr_eval_disk_emission_observer_*
+ *     (rtgr_eval_disk_emission_* for obs == NULL) predicts E_k and g_k to the bit.
+ *   The picture.  rgb starts as leg 0's (E_0 on the disk, the plain or shaded colour elsewhere); t = T (`transmission`); for
+ *     k = 1 .. m_p - 1:  rgb = rgb + t E_k, then t = t T  (m_p: the number of disk crossings found for the pixel, at most max_order + 1);
+ *     if the last continuation leg ended somewhere other than the disk:  rgb = rgb + t B,  B the colour the trace gave that end (the
+ *     shading kernel applied when `shade` binds that object or the escape).  A pixel that still continues after order max_order stops.
+ *     T = 0 reproduces the frame of rtgr_trace_observer_* with `emit`, with one exception: a pixel of the continuing set whose colour
+ *     channel is -0 becomes +0 (it has 0 added to it).
+ *   Outputs besides rgb (rtgr_order_planes; any member may be NULL).  count: n bytes, m_p.  Per-order planes, order-major, max_order + 1
+ *     blocks each: hit32 (n per block), state_end (n x 8), g (n), rgb_order (3 planes of n: the frame's own layout).  Block 0 is leg 0's,
+ *     as rtgr_trace_observer_* delivers it, for every pixel.  Block k >= 1: hit32 = emit->object, the end state, g_k and E_k where the
+ *     pixel has order k; 0 in hit32 and NaN in the others where it has not.  state0: n x 8, the rays' start states.  One block of these
+ *     planes plus state0 is what rtgr_light_curve_device_*, rtgr_spectrum_device_* and rtgr_polarization_device_* take: the Walker-Penrose
+ *     constants are conserved across the crossings, so the polarization of order k needs only the start state and the order-k end state.
+ *   ctr: the sum over all legs.
+ * rtgr_trace_orders_device_*: on the device that holds d_rgb, stream `stream`.  Legs run in chunks of at most obs->max_batch_rays rays
+ * (0 or obs == NULL: 2^22) through the stream's frame and batch scratch (grow-only).  The call reads the length of each leg's list back:
+ * two synchronisations per order, so it is refused while the stream is captured.  The result does not depend on max_batch_rays or on the
+ * stream.  rtgr_trace_orders_*: host pointers, on device 0 of the context.
+ *   RTGR_ERR_BAD_ARG (with a message): everything rtgr_trace_observer_* with `emit` refuses (obs == NULL is accepted with state0 only);
+ * a null ord, emit or rgb; max_order = 0 or > 8; a margin that is not finite, <= 0 after the default, or >= r_in; a transmission outside
+ * [0, 1] or NaN; flags or pad != 0; a stream under capture.
+ *   Out of scope: emission integrated through the slab's depth; an angle-dependent optical depth; more than one emitting disk;
+ * anti-aliasing; the sharded and frames-in-flight entry points; RTGR_USER metrics and 4-D grids; a light curve summed over orders in one
+ * call (the per-order stage calls cover it). */
+#define RTGR_MAX_DISK_ORDER 8
+typedef struct rtgr_disk_orders {
+    uint32_t max_order;    /* N: orders 1 .. N are looked for, 1 <= N <= RTGR_MAX_DISK_ORDER */
+    uint32_t flags;        /* 0 */
+    double margin;         /* eta; 0: half the disk's half thickness */
+    double transmission;   /* T in [0, 1] */
+    uint64_t pad;          /* 0 */
+} rtgr_disk_orders;        /* 32 bytes: max_order 0, flags 4, margin 8, transmission 16, pad 24 */
+typedef struct rtgr_order_planes {
+    uint8_t* count;        /* n */
+    uint32_t* hit32;       /* (N + 1) x n */
+    void* state_end;       /* (N + 1) x n x 8 scalars */
+    void* g;               /* (N + 1) x n scalars */
+    void* rgb_order;       /* (N + 1) x 3 x n scalars */
+    void* state0;          /* n x 8 scalars */
+} rtgr_order_planes;       /* 48 bytes; device or host pointers according to the call */
+int rtgr_trace_orders_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs /* may be NULL with d_state0 */,
+                                 const double* d_state0 /* n x 8, may be NULL */, uint64_t ni, uint64_t nj, const rtgr_shade* shade /* may be NULL */,
+                                 const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, double* d_rgb, const rtgr_order_planes* planes /* may be NULL */,
+                                 rtgr_counters* ctr, void* stream);
+int rtgr_trace_orders_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs /* may be NULL with d_state0 */,
+                                 const float* d_state0 /* n x 8, may be NULL */, uint64_t ni, uint64_t nj, const rtgr_shade* shade /* may be NULL */,
+                                 const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, float* d_rgb, const rtgr_order_planes* planes /* may be NULL */,
+                                 rtgr_counters* ctr, void* stream);
+int rtgr_trace_orders_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs /* may be NULL with state0 */,
+                          const double* state0 /* n x 8, may be NULL */, uint64_t ni, uint64_t nj, const rtgr_shade* shade /* may be NULL */,
+                          const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, double* rgb, const rtgr_order_planes* planes /* may be NULL */,
+                          rtgr_counters* ctr);
+int rtgr_trace_orders_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs /* may be NULL with state0 */,
+                          const float* state0 /* n x 8, may be NULL */, uint64_t ni, uint64_t nj, const rtgr_shade* shade /* may be NULL */,
+                          const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, float* rgb, const rtgr_order_planes* planes /* may be NULL */,
+                          rtgr_counters* ctr);
+
 /* ---- camera: make_canvas (src/RayTraceGR.jl:457-478) on the device ------------------------------------------
  * Writes n x 8 ray states (pos, null past-directed 4-velocity) for rows [j0, j1).  Device / host variants. */
 int rtgr_make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni,

@@ -35,6 +35,8 @@
 #   RtgrHotSpot      80   rho_s 0, phi0 8, sigma 16, cut 24, amp 32, g_power 40, t_start 48, dt 56, nt 64, flags 72, pad 76
 #   RtgrSpectrum     80   kind 0, flags 4, nb 8, lo 16, hi 24, amp 32, alpha 40, rho_min 48, rho_max 56, g_power 64, reserved 72
 #   RtgrPolarization 64   kind 0, flags 4, deg0 8, deg1 16, field 24, reserved 48
+#   RtgrDiskOrders 32   max_order 0, flags 4, margin 8, transmission 16, pad 24
+#   RtgrOrderPlanes 48   count 0, hit32 8, state_end 16, g 24, rgb_order 32, state0 40
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64         (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -190,6 +192,21 @@ struct RtgrPolarization        # the emission law of a polarized disk image (rtg
     deg1::Float64               # SCATTER: delta = deg0 (1 - mu) / (1 + deg1 mu), > -1
     field::NTuple{3,Float64}    # FIELD: B_rho, B_phi, B_z in the emitter's triad; SCATTER: 0
     reserved::NTuple{2,Float64} # 0
+end
+struct RtgrDiskOrders          # how far rays are followed through the emitting disk (rtgr_trace_orders_f64 / _f32)
+    max_order::UInt32           # N: orders 1 .. N are looked for, 1 .. 8
+    flags::UInt32               # 0
+    margin::Float64             # eta; 0: half the disk's half thickness
+    transmission::Float64       # T in [0, 1]
+    pad::UInt64                 # 0
+end
+struct RtgrOrderPlanes         # the optional outputs of rtgr_trace_orders_*; C_NULL = not wanted
+    count::Ptr{UInt8}           # n
+    hit32::Ptr{UInt32}          # (N + 1) x n
+    state_end::Ptr{Cvoid}       # (N + 1) x n x 8
+    g::Ptr{Cvoid}               # (N + 1) x n
+    rgb_order::Ptr{Cvoid}       # (N + 1) x 3 x n
+    state0::Ptr{Cvoid}          # n x 8
 end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
@@ -1243,6 +1260,65 @@ function eval_walker_penrose(metric, s::Matrix{T}, f::Matrix{T}; ctx = nothing) 
         end
     end
     kappa
+end
+
+"""
+    DiskOrders(max_order; transmission = 1, margin = 0) -> RtgrDiskOrders
+
+How far rays are followed through the emitting disk (include/rtgr.h "higher-order disk images"): orders `1 .. max_order` (at most 8) are
+looked for; order `k` adds `transmission^k` times its emission to the picture (1: an optically thin disk, 0: the opaque one); `margin`:
+how far the disk is inflated for the crossing legs (0: half its half thickness).
+"""
+function DiskOrders(max_order::Integer; transmission::Real = 1, margin::Real = 0)
+    RtgrDiskOrders(UInt32(max_order), UInt32(0), Float64(margin), Float64(transmission), UInt64(0))
+end
+
+"""
+    trace_rays_orders(metric, objs, observer, ni, nj, emission, orders; T = Float64, ctx = nothing)
+        -> ((R, G, B), count, hit32, state_end, g, rgb_order, state0)
+
+The emitting disk seen ORDER BY ORDER (`rtgr_trace_orders_f64/_f32`) — an extension: the frame of `trace_rays_observer` with `emission`
+(order 0), then every ray that ended on the disk carried through it and traced on; where it meets the disk again is the next order —
+order 1 the lensed far side and underside, order >= 2 the photon ring.  `(R, G, B)` is the sum over orders weighted `transmission^k`;
+`count` (`ni x nj`) the disk crossings per pixel; the per-order planes `hit32` (`ni x nj x (N+1)`), `state_end` (`8 x ni x nj x (N+1)`),
+`g` (`ni x nj x (N+1)`) and `rgb_order` (`ni x nj x 3 x (N+1)`) hold block 0 = the observer frame and, for `k >= 1`, NaN / 0 where the
+pixel has no order `k`; `state0` (`8 x ni x nj`) the rays' start states.  The observer's frame is asked for first: an invalid frame or a
+refused record is an error.
+"""
+function trace_rays_orders(metric, objs, observer::RtgrObserver, ni::Integer, nj::Integer, emission::RtgrDiskEmission, orders::RtgrDiskOrders;
+                           T::Type = Float64, ctx = nothing)
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("trace_rays_orders has no CPU counterpart in the reference: ", why)
+    opt = solver_of(T)
+    obs = Ref(observer)
+    emit = Ref(emission)
+    ord = Ref(orders)
+    observer_frame(scene, obs; T = T, ctx = ctx)
+    nb = Int(orders.max_order) + 1
+    rgb = Array{T}(undef, ni, nj, 3)                # plane-major: rgb[:, :, c] is plane c
+    count = Array{UInt8}(undef, ni, nj)
+    hit32 = Array{UInt32}(undef, ni, nj, nb)
+    state_end = Array{T}(undef, 8, ni, nj, nb)
+    g = Array{T}(undef, ni, nj, nb)
+    rgb_order = Array{T}(undef, ni, nj, 3, nb)
+    state0 = Array{T}(undef, 8, ni, nj)
+    ctr = Ref{RtgrCounters}()
+    GC.@preserve rgb count hit32 state_end g rgb_order state0 begin
+        planes = Ref(RtgrOrderPlanes(pointer(count), pointer(hit32), Ptr{Cvoid}(pointer(state_end)), Ptr{Cvoid}(pointer(g)),
+                                     Ptr{Cvoid}(pointer(rgb_order)), Ptr{Cvoid}(pointer(state0))))
+        if T === Float64
+            check(ccall((:rtgr_trace_orders_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, Ptr{Float64}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission},
+                         Ptr{RtgrDiskOrders}, Ptr{Float64}, Ptr{RtgrOrderPlanes}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, C_NULL, ni, nj, C_NULL, emit, ord, pointer(rgb), planes, ctr))
+        else
+            check(ccall((:rtgr_trace_orders_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, Ptr{Float32}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission},
+                         Ptr{RtgrDiskOrders}, Ptr{Float32}, Ptr{RtgrOrderPlanes}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, C_NULL, ni, nj, C_NULL, emit, ord, pointer(rgb), planes, ctr))
+        end
+    end
+    (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), count, hit32, state_end, g, rgb_order, state0
 end
 
 """

@@ -158,6 +158,17 @@ class rtgr_polarization(C.Structure):
                 ("reserved", C.c_double * 2)]
 
 
+class rtgr_disk_orders(C.Structure):
+    """how far a ray is followed through the emitting disk, order by order (rtgr_trace_orders_*): 32 bytes"""
+    _fields_ = [("max_order", C.c_uint32), ("flags", C.c_uint32), ("margin", C.c_double), ("transmission", C.c_double), ("pad", C.c_uint64)]
+
+
+class rtgr_order_planes(C.Structure):
+    """the optional outputs of rtgr_trace_orders_*: the crossings per pixel, the per-order planes, the start states; 48 bytes"""
+    _fields_ = [("count", C.c_void_p), ("hit32", C.c_void_p), ("state_end", C.c_void_p), ("g", C.c_void_p), ("rgb_order", C.c_void_p),
+                ("state0", C.c_void_p)]
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -195,6 +206,7 @@ EXPORTS = [
     "rtgr_polarization_device_f64", "rtgr_polarization_device_f32", "rtgr_trace_polarized_device_f64", "rtgr_trace_polarized_device_f32",
     "rtgr_trace_polarized_f64", "rtgr_trace_polarized_f32", "rtgr_eval_polarization_f64", "rtgr_eval_polarization_f32",
     "rtgr_eval_walker_penrose_f64", "rtgr_eval_walker_penrose_f32",
+    "rtgr_trace_orders_device_f64", "rtgr_trace_orders_device_f32", "rtgr_trace_orders_f64", "rtgr_trace_orders_f32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -318,6 +330,12 @@ def _declare(lib):
         getattr(lib, f"rtgr_eval_polarization_{suf}").argtypes = [
             ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_polarization), P(rtgr_observer), vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]
         getattr(lib, f"rtgr_eval_walker_penrose_{suf}").argtypes = [ctx, P(rtgr_scene), vp, vp, u64, vp]
+        getattr(lib, f"rtgr_trace_orders_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), vp, u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_disk_orders), vp,
+            P(rtgr_order_planes), P(rtgr_counters), vp]
+        getattr(lib, f"rtgr_trace_orders_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), vp, u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_disk_orders), vp,
+            P(rtgr_order_planes), P(rtgr_counters)]
     lib.rtgr_texture_load.argtypes = [ctx, P(rtgr_texture_desc), vp, P(u64)]
     lib.rtgr_texture_unload.argtypes = [ctx, u64]
     lib.rtgr_eval_fastmath_f64.argtypes = [ctx, vp, u64, vp, vp]

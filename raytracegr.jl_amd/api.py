@@ -608,10 +608,11 @@ def trace_emission(metric, objs, cam, ni, nj, emission, textures=None, r_escape=
     return res
 
 
-def eval_disk_emission(metric, objs, emission, s0, s_end, dtype=np.float64, ctx=None):
+def eval_disk_emission(metric, objs, emission, s0, s_end, dtype=np.float64, ctx=None, observer=None):
     """rtgr_eval_disk_emission_f64 / _f32: the emitter model at n pairs of ray states — s0 [n, 8] at the camera (make_canvas' states),
     s_end [n, 8] on the disk.  -> dict(omega [n], u_emit [n, 4], g [n], rgb [n, 3]); a point with no valid emitter gives NaN, NaN,
-    NaN and black."""
+    NaN and black.  observer (an Observer; rtgr_eval_disk_emission_observer_*): the frequency ratio is taken against ITS 4-velocity, as
+    trace_observer does; None: against the static observer at s0."""
     lib = _lib()
     sc = make_scene(metric, objs, ctx)
     a = np.ascontiguousarray(s0, dtype=dtype).reshape(-1, 8)
@@ -620,9 +621,13 @@ def eval_disk_emission(metric, objs, emission, s0, s_end, dtype=np.float64, ctx=
         raise ValueError(f"eval_disk_emission: s0 and s_end must have the same shape, got {a.shape} and {e.shape}")
     n = a.shape[0]
     res = dict(omega=np.zeros(n, dtype), u_emit=np.zeros((n, 4), dtype), g=np.zeros(n, dtype), rgb=np.zeros((n, 3), dtype))
-    fn = lib.rtgr_eval_disk_emission_f64 if dtype == np.float64 else lib.rtgr_eval_disk_emission_f32
-    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(emission), a.ctypes.data, e.ctypes.data, n, res["omega"].ctypes.data, res["u_emit"].ctypes.data,
-                       res["g"].ctypes.data, res["rgb"].ctypes.data))
+    outs = (res["omega"].ctypes.data, res["u_emit"].ctypes.data, res["g"].ctypes.data, res["rgb"].ctypes.data)
+    suf = "f64" if dtype == np.float64 else "f32"
+    if observer is None:
+        _abi.check(lib, getattr(lib, "rtgr_eval_disk_emission_" + suf)(ctx, C.byref(sc), C.byref(emission), a.ctypes.data, e.ctypes.data, n, *outs))
+    else:
+        _abi.check(lib, getattr(lib, "rtgr_eval_disk_emission_observer_" + suf)(ctx, C.byref(sc), C.byref(emission), C.byref(observer), a.ctypes.data,
+                                                                                 e.ctypes.data, n, *outs))
     return res
 
 
@@ -883,6 +888,47 @@ def eval_walker_penrose(metric, objs, s, f, dtype=np.float64, ctx=None):
     return kap
 
 
+# ---- higher-order disk images (include/rtgr.h "higher-order disk images") ---------------------------------------------------------------
+def DiskOrders(max_order, transmission=1.0, margin=0.0):
+    """How far rays are followed through the emitting disk -> rtgr_disk_orders.  max_order N (1..8): orders 1 .. N are looked for;
+    transmission T in [0, 1]: order k adds T^k times its emission to the picture (1: an optically thin disk, 0: the opaque one);
+    margin eta: how far the disk is inflated for the crossing legs (0: half its half thickness)."""
+    return _abi.rtgr_disk_orders(max_order=int(max_order), flags=0, margin=float(margin), transmission=float(transmission), pad=0)
+
+
+def trace_orders(metric, objs, observer, ni, nj, emission, orders, state0=None, textures=None, r_escape=0.0, opt=None, dtype=np.float64, ctx=None):
+    """The emitting disk seen ORDER BY ORDER (rtgr_trace_orders_f64 / _f32) — an extension: trace_observer's frame with emission (order 0),
+    then every ray that ended on the disk carried through it and traced on; where it meets the disk again is the next order — order 1 the
+    lensed far side and underside, order >= 2 the photon ring.  orders: a DiskOrders.  state0 [ni*nj, 8]: the rays are these states in
+    place of the observer's, and observer may then be None (the frequency ratio is taken against the static observer at the ray's start).
+    Raises ValueError for an observer with no valid frame.
+    -> dict(rgb [3, ni*nj] (the sum over orders, weighted T^k), count [ni*nj] uint8 (disk crossings per pixel), the per-order planes
+    hit32 [N+1, ni*nj], state_end [N+1, ni*nj, 8], g [N+1, ni*nj], rgb_order [N+1, 3, ni*nj] (block 0: trace_observer's; block k >= 1:
+    NaN / 0 where the pixel has no order k), state0 [ni*nj, 8], counters (summed over all legs))."""
+    lib = _lib()
+    if observer is not None:
+        _valid_observer(metric, objs, observer, dtype, ctx)
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    n = ni * nj
+    nb = max(int(orders.max_order), 0) + 1 if orders is not None else 1
+    sh = make_shade(textures, r_escape) if textures else None
+    s0 = None if state0 is None else np.ascontiguousarray(state0, dtype=dtype).reshape(-1, 8)
+    if s0 is not None and s0.shape[0] != n:
+        raise ValueError(f"trace_orders: state0 must hold ni*nj = {n} states, got {s0.shape[0]}")
+    res = dict(rgb=np.zeros((3, n), dtype), count=np.zeros(n, np.uint8), hit32=np.zeros((nb, n), np.uint32), state_end=np.zeros((nb, n, 8), dtype),
+               g=np.zeros((nb, n), dtype), rgb_order=np.zeros((nb, 3, n), dtype), state0=np.zeros((n, 8), dtype))
+    planes = _abi.rtgr_order_planes(count=res["count"].ctypes.data, hit32=res["hit32"].ctypes.data, state_end=res["state_end"].ctypes.data,
+                                    g=res["g"].ctypes.data, rgb_order=res["rgb_order"].ctypes.data, state0=res["state0"].ctypes.data)
+    ctr = rtgr_counters()
+    fn = lib.rtgr_trace_orders_f64 if dtype == np.float64 else lib.rtgr_trace_orders_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), None if observer is None else C.byref(observer), None if s0 is None else s0.ctypes.data, ni, nj,
+                       None if sh is None else C.byref(sh), None if emission is None else C.byref(emission),
+                       None if orders is None else C.byref(orders), res["rgb"].ctypes.data, C.byref(planes), C.byref(ctr)))
+    res["counters"] = ctr.as_dict()
+    return res
+
+
 def trace_ray(metric, objs, cb, p, opt=None, ctx=None):
     """Legacy single-pixel shape `trace_ray(metric, objs, cb, p)::Pixel` (test/runtests.jl:65-79).
     `cb` is accepted for signature parity and ignored: the callback is always
@@ -992,5 +1038,5 @@ def example2(ni=200, nj=200, save=True, ctx=None):
 
 __all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
-           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "HotSpot", "eval_hot_spot", "light_curve", "Spectrum", "eval_spectrum", "spectrum", "Polarization", "trace_polarized", "eval_polarization", "eval_walker_penrose", "dmetric", "christoffel", "geodesic", "example1", "example2",
+           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "HotSpot", "eval_hot_spot", "light_curve", "Spectrum", "eval_spectrum", "spectrum", "Polarization", "trace_polarized", "eval_polarization", "eval_walker_penrose", "DiskOrders", "trace_orders", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

@@ -29,6 +29,8 @@
 //                           (kernels: rtgr_spectrum.hip)
 //   rtgr_polarization_host.hip  polarized disk images: the checks of an rtgr_polarization, the stage alone, the polarized observer trace,
 //                           the two hooks (kernel: rtgr_polarize.hip)
+//   rtgr_orders_host.hip    higher-order disk images: the checks of an rtgr_disk_orders, the chain of legs through the inflated disk and the
+//                           caller's scene, the entry points (kernels: rtgr_orders.hip; argument blocks: rtgr_orders.hpp)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -181,8 +183,10 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
 // Pure arithmetic: the head — rtgr_counters (64 bytes), then the refined count of an anti-aliased frame — always; `obs`: the observer's
 // frame record; `list`: the index list of the refined pixels; then the end states / hit map / status bytes to borrow, n rays of each.
 constexpr size_t FRAME_HEAD = 256, FRAME_OBS = 512;
-struct FrameNeeds { bool state_end = false, hit32 = false, status = false, list = false, obs = false; };
-struct FrameLayout { size_t obs, list, state_end, hit32, status, bytes; };
+// `orders`: what the lists of a higher-order disk image add (rtgr_orders_host.hip): a second index list of n pixels behind the first, and,
+// with orders_state0, the start states of the n rays
+struct FrameNeeds { bool state_end = false, hit32 = false, status = false, list = false, obs = false, orders = false, orders_state0 = false; };
+struct FrameLayout { size_t obs, list, state_end, hit32, status, orders_list, orders_state0, bytes; };
 static_assert(sizeof(rtgr_counters) + sizeof(unsigned long long) <= FRAME_HEAD && sizeof(ObsFrame<double>) <= FRAME_OBS, "the head holds them");
 inline FrameLayout frame_layout(uint64_t n, size_t scalar, const FrameNeeds& need) {
     FrameLayout at;
@@ -191,7 +195,9 @@ inline FrameLayout frame_layout(uint64_t n, size_t scalar, const FrameNeeds& nee
     at.state_end = at.list + (need.list ? align256((size_t)n * sizeof(uint64_t)) : 0);
     at.hit32 = at.state_end + (need.state_end ? align256((size_t)n * 8 * scalar) : 0);
     at.status = at.hit32 + (need.hit32 ? align256((size_t)n * sizeof(uint32_t)) : 0);
-    at.bytes = at.status + (need.status ? align256((size_t)n) : 0);
+    at.orders_list = at.status + (need.status ? align256((size_t)n) : 0);
+    at.orders_state0 = at.orders_list + (need.orders ? align256((size_t)n * sizeof(uint64_t)) : 0);
+    at.bytes = at.orders_state0 + (need.orders_state0 ? align256((size_t)n * 8 * scalar) : 0);
     return at;
 }
 // the words of an entry point in its refusals: its name ("rtgr_trace_shaded_*"), what it calls its scratch ("shading"), and whether
@@ -473,6 +479,8 @@ template <class R> int trace_polarized_device(rtgr_context* ctx, const rtgr_scen
 template <class R> int trace_polarized(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_polarization* pol, R* rgb, const rtgr_ray_outputs* out, R* g, R* q, R* u, R* aux, rtgr_counters* ctr);
 template <class R> int eval_polarization(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_polarization* pol, const rtgr_observer* obs, const R* s0, const R* s_end, uint64_t n, R* kappa, R* f_em, R* aux, R* delta, R* q, R* u, int* valid);
 template <class R> int eval_walker_penrose(rtgr_context* ctx, const rtgr_scene* scene, const R* s, const R* f, uint64_t n, R* kappa);
+template <class R> int trace_orders_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, const R* d_state0, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, R* d_rgb, const rtgr_order_planes* planes, rtgr_counters* ctr, void* stream);
+template <class R> int trace_orders(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, const R* state0, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, R* rgb, const rtgr_order_planes* planes, rtgr_counters* ctr);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 
