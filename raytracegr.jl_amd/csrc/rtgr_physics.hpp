@@ -284,6 +284,12 @@ RTGR_DEV MetricK<R> metric_consts(R M, R a) {
 
 // a = 0 (the reference's configuration, :276): k_i = x_i/r, every gradient is radial, and the whole contraction
 // collapses to u̇^i = x_i·g, u̇^t = P − S·kL (derivation in DESIGN.md §RHS).  xs = (x,y,z), u = (u^t,u^x,u^y,u^z).
+// k = x/r(ρ) is a GRADIENT field, ∂_j k_i = ∂_i k_j, so the antisymmetric part Dk_i − W_i of ksform_accel's L_i is zero:
+// with κ = 1/r, ∇r = q x, D = q (x·u), Ku = κ (x·u) the term by term specialisation
+//     λ = κ (P − fκ K D) + q fκ K (K/2 + Ku) = κP + ½ q f κ K²
+// forms −fκ²qK(x·u) and +fκ²qK(x·u) and adds them; only the right-hand side is computed (4 instructions per evaluation less,
+// and their rounding noise; tools/check_identities_radial.py holds the identities to 40 digits, both radii).
+// -DRTGR_RADIAL_GENERAL_FORM=1 builds the term by term body instead: an experiment flag for timing one against the other.
 template <class R, int METRIC, bool FAST>
 RTGR_DEV void accel_radial(const R xs[3], const R u[4], const MetricK<R>& C, R ud[4]) {
     const R rho2 = rfma(xs[0], xs[0], rfma(xs[1], xs[1], xs[2] * xs[2]));
@@ -305,6 +311,8 @@ RTGR_DEV void accel_radial(const R xs[3], const R u[4], const MetricK<R>& C, R u
     const R K = u[0] + Ku;                                               // k_a u^a
     const R fi = f * invr;
     const R P = fi * rfma(-D, K + Ku, uu);                               // L_t = K Df + f A
+#if RTGR_RADIAL_GENERAL_FORM
+    // the general contraction specialised term by term (the body up to round 6; for the A/B of profiles/r07 only)
     const R alpha = rfma(-fi * K, D, P);
     const R beta = fi * K * rfma(R(0.5), K, Ku);
     const R lam = rfma(invr, alpha, rq2 * beta);                         // L_i = x_i λ
@@ -316,6 +324,17 @@ RTGR_DEV void accel_radial(const R xs[3], const R u[4], const MetricK<R>& C, R u
         S = f;                                                           // |k|² = 1
     }
     const R kL = rfma(invr * lam, rho2, -P);                             // k♯^d L_d
+#else
+    const R lam = rfma(invr, P, (rq2 * (fi * K)) * (R(0.5) * K));        // L_i = x_i λ,  λ = κP + ½ q f κ K²
+    const R t1 = rho2 * invr;                                            // ρ²/r: |k|² = t1/r, and k^i x_i
+    R S;
+    if constexpr (METRIC == RTGR_KS_REF) {
+        S = f * rcp_<FAST>(rfma(f, rfma(t1, invr, R(-1)), R(1)));        // r ≠ ρ as written: |k|² ≠ 1
+    } else {
+        S = f;                                                           // |k|² = 1
+    }
+    const R kL = rfma(t1, lam, -P);                                      // k♯^d L_d
+#endif
     const R SkL = S * kL;
     ud[0] = P - SkL;
     const R g = rfma(SkL, invr, -lam);

@@ -13,7 +13,8 @@ and/or alternative builds of the library.
         per-rank time of a cyclic N-way split, N = 1, 2, 4, 8 (a REHEARSAL of the strong-scaling curve: compute only, one GPU)
     python tools/launch_ab.py builds --flags "name1:-DA=1,-DB=2;name2:-DC=3" [--size ...]
         builds raytracegr.jl_amd/build/variants/librtgr_<name>.so with the extra flags and times each (fresh process per
-        library, RTGR_LIB) against the default build with `bench.py --full --cpu-sample 0 --extras 0`
+        library, RTGR_LIB) against the default build with `bench.py --full --cpu-sample 0 --extras 0`, --rounds times in turn
+        (default 1).  --no-build: time the variant libraries an earlier call built, as they are (where the objects are not at hand)
 """
 import argparse
 import ctypes
@@ -86,7 +87,9 @@ def main():
     ap.add_argument("--shares", default="1")
     ap.add_argument("--variants", default="ks_ref0")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
-    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=0, help="interleaved rounds (default: ab 3, builds 1)")
+    ap.add_argument("--no-build", action="store_true", help="builds: do not compile; the variant libraries must be there")
+    ap.add_argument("--run-timeout", type=float, default=300.0, help="builds: seconds one bench.py run may take; a run that exceeds it ends the comparison")
     ap.add_argument("--flags", default="")
     ap.add_argument("--bench-steps", type=int, default=0, help="builds: timed passes per run (default 3, 30 up to 2048²)")
     a = ap.parse_args()
@@ -102,9 +105,13 @@ def main():
         for item in [x for x in a.flags.split(";") if x]:
             name, fl = item.split(":")
             out = os.path.join(vdir, f"librtgr_{name}.so")
-            b.build(extra=fl.split(","), out=out, obj_dir=os.path.join(vdir, "obj_" + name), verbose=False)
+            if a.no_build:
+                if not os.path.exists(out):
+                    raise SystemExit(f"--no-build: {out} is not there")
+            else:
+                b.build(extra=fl.split(","), out=out, obj_dir=os.path.join(vdir, "obj_" + name), verbose=False)
             libs.append((name, out))
-        for variant in variants:
+        for variant, rnd in ((v, r) for v in variants for r in range(a.rounds or 1)):
             for name, path in libs:
                 env = dict(os.environ)
                 env.pop("RTGR_LIB", None)
@@ -113,13 +120,15 @@ def main():
                 steps = a.bench_steps or (30 if a.size <= 2048 else 3)
                 r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(max(1, steps // 5)), "--full", "--cpu-sample", "0",
                                     "--extras", "0", "--size", str(a.size), "--variant", variant, "--dtype", a.dtype],
-                                   capture_output=True, text=True, env=env)
+                                   capture_output=True, text=True, env=env, timeout=a.run_timeout)
+                if r.returncode not in (0, 2):      # (2: the line is there, its frame checksum differs from the recorded one)
+                    raise SystemExit(f"{variant} [{name}]: bench.py ended with status {r.returncode}: nothing more is started\n{r.stderr[-600:]}")
                 line = next((json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")), None)
                 if line is None:
                     print(f"{variant} [{name}] FAILED: {r.stderr[-300:]}")
                     continue
                 rf = line["roofline"]
-                print(f"{variant} {a.size}² [{name}]: {line['ms_per_step']:.2f} ms  steps/s {line['value']:.4g}  far {rf['far_pass_ms_per_pass']:.2f} "
+                print(f"{variant} {a.size}² round {rnd + 1} [{name}]: {line['ms_per_step']:.3f} ms  steps/s {line['value']:.4g}  far {rf['far_pass_ms_per_pass']:.2f} "
                       f"near {rf['near_pass_ms_per_pass']:.2f}", flush=True)
         return
     frame = device_runner(a)
@@ -150,7 +159,7 @@ def main():
             else:
                 sets = parse_sets(a.sets)
                 res, last = {}, {}
-                for _ in range(a.rounds):
+                for _ in range(a.rounds or 3):
                     for i, kw in enumerate(sets):
                         ms, k = timed(reps, **kw)
                         res.setdefault(i, []).append(ms)
