@@ -55,9 +55,7 @@ template <class R>
 int api::trace_emission_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
                                const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out,
                                R* d_g, uint8_t* d_refined, rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!d_rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     if (!emit) return fail(RTGR_ERR_BAD_ARG, "rtgr_disk_emission is NULL (emit)");
     if ((rc = shaded_check(cam, aa, d_refined, stats, ni, nj))) return rc;
@@ -71,9 +69,7 @@ template <class R>
 int api::trace_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
                         const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_aa* aa, R* rgb, const rtgr_ray_outputs* out, R* g,
                         uint8_t* refined, rtgr_counters* ctr, rtgr_aa_stats* stats) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     if (!emit) return fail(RTGR_ERR_BAD_ARG, "rtgr_disk_emission is NULL (emit)");
     if ((rc = shaded_check(cam, aa, refined, stats, ni, nj))) return rc;
@@ -88,9 +84,7 @@ int api::trace_emission(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_s
 template <class R>
 int api::eval_disk_emission_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_observer* obs, const R* s0,
                                      const R* s_end, uint64_t n, R* omega, R* u_emit, R* g, R* rgb) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (n && (!s0 || !s_end)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_disk_emission: NULL argument");
     if (n > (1ull << 32)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_disk_emission: at most 2^32 points per call");
     EmitArgs<R> E;
@@ -99,35 +93,21 @@ int api::eval_disk_emission_observer(rtgr_context* ctx, const rtgr_scene* scene,
     DevObserver<R> ob;
     if (obs && (rc = observer_resolve<R>(scene, obs, ob))) return rc;
     DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    HostMirror m(D);
+    if ((rc = m.status())) return rc;
     std::lock_guard<std::mutex> lk(D.mu);
     if ((rc = stationary_scene<R>(D, scene, E.sc, nullptr, EMISSION_NEEDS_STATIONARY))) return rc;
     if (n == 0) return RTGR_OK;
-    const size_t sbytes = (size_t)n * 8 * sizeof(R);
-    DevBuf d_s0, d_se, d_om, d_u, d_g, d_rgb, d_frame;
-    if ((rc = d_s0.alloc(sbytes)) || (rc = d_se.alloc(sbytes))) return rc;
-    if (obs) {
-        if ((rc = d_frame.alloc(sizeof(ObsFrame<R>)))) return rc;
-        if ((rc = observer_frame_launch<R>(E.sc, ob, (ObsFrame<R>*)d_frame.p, nullptr))) return rc;
-        E.obs = (const ObsFrame<R>*)d_frame.p;
-    }
-    if (omega && (rc = d_om.alloc((size_t)n * sizeof(R)))) return rc;
-    if (u_emit && (rc = d_u.alloc((size_t)n * 4 * sizeof(R)))) return rc;
-    if (g && (rc = d_g.alloc((size_t)n * sizeof(R)))) return rc;
-    if (rgb && (rc = d_rgb.alloc((size_t)n * 3 * sizeof(R)))) return rc;
-    HIP_TRY(hipMemcpy(d_s0.p, s0, sbytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_se.p, s_end, sbytes, hipMemcpyHostToDevice));
     // the emission kernel in point mode: no hit map, the start states given, n x 3 colours
-    E.rgb = (R*)d_rgb.p; E.g = (R*)d_g.p; E.omega = (R*)d_om.p; E.u_emit = (R*)d_u.p; E.state_end = (const R*)d_se.p; E.state0 = (const R*)d_s0.p;
+    E.state0 = m.in(s0, (size_t)n * 8); E.state_end = m.in(s_end, (size_t)n * 8);
+    ObsFrame<R>* d_frame = obs ? m.scratch<ObsFrame<R>>(1) : nullptr;
+    E.omega = m.out(omega, n); E.u_emit = m.out(u_emit, (size_t)n * 4); E.g = m.out(g, n); E.rgb = m.out(rgb, (size_t)n * 3);
+    if ((rc = m.status())) return rc;
+    if (obs && (rc = observer_frame_launch<R>(E.sc, ob, d_frame, nullptr))) return rc;
+    E.obs = d_frame;
     E.n = n; E.plane_stride = 1; E.pixel_stride = 3;
     if ((rc = emit_launch<R>(E, nullptr))) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (omega) HIP_TRY(hipMemcpy(omega, d_om.p, (size_t)n * sizeof(R), hipMemcpyDeviceToHost));
-    if (u_emit) HIP_TRY(hipMemcpy(u_emit, d_u.p, (size_t)n * 4 * sizeof(R), hipMemcpyDeviceToHost));
-    if (g) HIP_TRY(hipMemcpy(g, d_g.p, (size_t)n * sizeof(R), hipMemcpyDeviceToHost));
-    if (rgb) HIP_TRY(hipMemcpy(rgb, d_rgb.p, (size_t)n * 3 * sizeof(R), hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    return m.fetch();
 }
 
 RTGR_INSTANTIATE_F64_F32(api::trace_emission_device);

@@ -128,10 +128,12 @@ int stream_state(DeviceCtx& d, hipStream_t st, StreamState** out);
 int collect_timed(DeviceCtx& d);
 uint64_t fnv1a(const std::vector<char>& b);
 
-#define RESOLVE_DEVICE(ptr)                          \
+#define RESOLVE_CONTEXT()                            \
     rtgr_context* c = nullptr;                       \
     int rc = resolve_ctx(ctx, &c);                   \
-    if (rc) return rc;                               \
+    if (rc) return rc
+#define RESOLVE_DEVICE(ptr)                          \
+    RESOLVE_CONTEXT();                               \
     DeviceCtx* D = nullptr;                          \
     if ((rc = device_of(c, (ptr), &D))) return rc
 
@@ -318,7 +320,7 @@ int trace_reduce(rtgr_context* ctx, const Reduction<R>& red, const rtgr_scene* s
 // the pixel weight of an observer's canvas (obs may be null: w = 1): what pixel_weight (rtgr_reduce.hpp) reads
 template <class R> int pixel_weight_resolve(const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, PixelWeight& W);
 
-// scratch device buffers of the small host-pointer hooks (eval_*, make_canvas, the probe): RAII, synchronous
+// a device buffer of one call that mirrors no host array (the table of trace_reduce, the sampled states of auto_scene_check): RAII, synchronous
 struct DevBuf {
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -326,6 +328,67 @@ struct DevBuf {
         if (bytes == 0) return RTGR_OK;
         HIP_TRY(hipMalloc(&p, bytes));
         return RTGR_OK;
+    }
+};
+
+// The device-side mirror of the arrays of ONE blocking host-pointer call on one device (make_canvas, the rtgr_eval_* hooks, the probe,
+// the planes a host-pointer frame call adds to staged_frame's): each array is declared once, its count stated once — `in` goes up at
+// once, `out` and `inout` come back in `fetch`, `scratch` stays on the device.  One hipMalloc per array (a kernel that overruns one stays
+// as detectable as it is with an array of its own), blocking copies.  The mirror makes its device current for its lifetime and takes no
+// lock: who holds D.mu, and for how long, is the call's own business.  An omitted optional output legitimately gets a null device pointer,
+// so a failure is not told by the pointer: the first one is kept (what is declared after it gets null and no HIP call) and asked for
+// by status(), at once for the device and once more behind the declarations.
+// fetch is THE place where these calls wait for the device — hipDeviceSynchronize for a hook, the stream inside a staged frame call:
+// what they wait with is changed here, not hook by hook.
+class HostMirror {
+    DeviceGuard guard_;   // ahead of the arrays: they are freed on their device, then the calling thread's device is restored
+    struct Array { void* dev; void* host; size_t bytes; };   // host: where fetch copies it back to (null: nowhere)
+    std::vector<Array> arrays_;
+    int rc_ = RTGR_OK;
+
+    int alloc(const void* up, void* back, size_t bytes, void*& p) {
+        HIP_TRY(hipMalloc(&p, bytes));
+        arrays_.push_back({p, back, bytes});
+        if (up) HIP_TRY(hipMemcpy(p, up, bytes, hipMemcpyHostToDevice));
+        return RTGR_OK;
+    }
+    void* add(const void* up, void* back, size_t bytes) {
+        void* p = nullptr;
+        if (rc_ == RTGR_OK && bytes) rc_ = alloc(up, back, bytes, p);
+        return rc_ == RTGR_OK ? p : nullptr;
+    }
+    int back() {
+        for (const Array& a : arrays_)
+            if (a.host) HIP_TRY(hipMemcpy(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost));
+        return RTGR_OK;
+    }
+
+public:
+    explicit HostMirror(DeviceCtx& D) : guard_(D.dev) { if (!guard_.ok) rc_ = fail(RTGR_ERR_HIP, "hipSetDevice failed"); }
+    explicit HostMirror(rtgr_context* c) : HostMirror(*c->devs[0]) {}
+    HostMirror(const HostMirror&) = delete;
+    HostMirror& operator=(const HostMirror&) = delete;
+    ~HostMirror() { for (const Array& a : arrays_) (void)hipFree(a.dev); }
+    int status() const { return rc_; }
+    // count elements of T each; count = 0, or a null `host`: a null device pointer and no HIP call
+    template <class T> const T* in(const T* host, size_t count) { return (const T*)add(host, nullptr, host ? count * sizeof(T) : 0); }
+    template <class T> T* out(T* host, size_t count) { return (T*)add(nullptr, host, host ? count * sizeof(T) : 0); }
+    template <class T> T* inout(T* host, size_t count) { return (T*)add(host, host, host ? count * sizeof(T) : 0); }
+    template <class T> T* scratch(size_t count) { return (T*)add(nullptr, nullptr, count * sizeof(T)); }
+    int zero() {   // every array declared so far, blocking, on the null stream
+        for (const Array& a : arrays_) HIP_TRY(hipMemset(a.dev, 0, a.bytes));
+        return rc_;
+    }
+    // behind the launch: wait, then every out and inout back to its host array, in the order of their declaration
+    int fetch() {
+        if (rc_) return rc_;
+        HIP_TRY(hipDeviceSynchronize());
+        return back();
+    }
+    int fetch(hipStream_t st) {
+        if (rc_) return rc_;
+        HIP_TRY(hipStreamSynchronize(st));
+        return back();
     }
 };
 

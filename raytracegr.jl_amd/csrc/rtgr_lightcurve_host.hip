@@ -120,32 +120,29 @@ int api::trace_light_curve(rtgr_context* ctx, const rtgr_scene* scene, const rtg
 template <class R>
 int api::eval_hot_spot(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_hot_spot* spot, const R* xyt, uint64_t n,
                        R* omega_s, int* valid, double* j) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (n && (!xyt || !j)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_hot_spot: NULL argument");
     if (n > (1ull << 32)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_hot_spot: at most 2^32 points per call");
     LcResolved<R> L;
     if ((rc = lc_resolve<R>(scene, emit, spot, nullptr, 1, 1, L))) return rc;
     DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    HostMirror m(D);
+    if ((rc = m.status())) return rc;
     std::lock_guard<std::mutex> lk(D.mu);
     DevScene<R> sc;
     if ((rc = stationary_scene<R>(D, scene, sc, nullptr, EMISSION_NEEDS_STATIONARY))) return rc;
-    DevBuf head, d_xyt, d_j;
-    if ((rc = head.alloc(LC_HEAD)) || (rc = d_xyt.alloc((size_t)n * 3 * sizeof(R))) || (rc = d_j.alloc((size_t)n * sizeof(double)))) return rc;
-    if ((rc = lc_omega<R>(sc, L.em, L.S.rho_s, (char*)head.p, nullptr))) return rc;
-    if (n) {
-        HIP_TRY(hipMemcpy(d_xyt.p, xyt, (size_t)n * 3 * sizeof(R), hipMemcpyHostToDevice));
-        if ((rc = lc_points_launch<R>((const R*)d_xyt.p, n, L.S, (const char*)head.p, (double*)d_j.p, nullptr))) return rc;
-    }
-    HIP_TRY(hipDeviceSynchronize());
+    char head[LC_HEAD];   // the whole head comes back: Omega_s is read from it
+    char* d_head = m.out(head, LC_HEAD);
+    const R* d_xyt = m.in(xyt, (size_t)n * 3);
+    double* d_j = m.out(j, n);
+    if ((rc = m.status())) return rc;
+    if ((rc = lc_omega<R>(sc, L.em, L.S.rho_s, d_head, nullptr))) return rc;
+    if (n && (rc = lc_points_launch<R>(d_xyt, n, L.S, d_head, d_j, nullptr))) return rc;
+    if ((rc = m.fetch())) return rc;
     R om;
-    HIP_TRY(hipMemcpy(&om, (char*)head.p + LC_HEAD_OMEGA, sizeof om, hipMemcpyDeviceToHost));
+    std::memcpy(&om, head + LC_HEAD_OMEGA, sizeof om);
     if (omega_s) *omega_s = om;
     if (valid) *valid = std::isfinite((double)om) ? 1 : 0;
-    if (n) HIP_TRY(hipMemcpy(j, d_j.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return RTGR_OK;
 }
 

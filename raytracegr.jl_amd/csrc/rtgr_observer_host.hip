@@ -164,9 +164,7 @@ template <class R>
 int api::trace_observer_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
                                const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, rtgr_counters* ctr,
                                void* stream) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if ((rc = observer_trace_check(scene, obs, ni, nj, emit, d_rgb, out, d_g))) return rc;
     DeviceCtx* D = nullptr;
     if ((rc = device_of(c, d_rgb, &D))) return rc;
@@ -177,9 +175,7 @@ int api::trace_observer_device(rtgr_context* ctx, const rtgr_scene* scene, const
 template <class R>
 int api::trace_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
                         const rtgr_shade* shade, const rtgr_disk_emission* emit, R* rgb, const rtgr_ray_outputs* out, R* g, rtgr_counters* ctr) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if ((rc = observer_trace_check(scene, obs, ni, nj, emit, rgb, out, g))) return rc;
     return staged_frame<R>(c, ni * nj, rgb, out, nullptr, g, [&](DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs* d_out, uint8_t*, R* d_g, hipStream_t st) {
         return trace_observer_on<R>(D, scene, opt, obs, ni, nj, shade, emit, d_rgb, d_out, d_g, ctr, st);
@@ -216,43 +212,36 @@ int api::make_observer_canvas_device(rtgr_context* ctx, const rtgr_scene* scene,
 template <class R>
 int api::make_observer_canvas(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, uint64_t ni, uint64_t nj, uint64_t j0, uint64_t j1,
                               R* state0) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
     if (!state0) return fail(RTGR_ERR_BAD_ARG, "NULL argument");
     if ((rc = canvas_check(ni, nj, OBSERVER_CANVAS))) return rc;
     if (j1 <= j0 || j1 > nj) return fail(RTGR_ERR_BAD_ARG, "bad canvas range");
     const uint64_t n = ni * (j1 - j0);
-    DeviceGuard guard(c->devs[0]->dev);
-    DevBuf b;
-    if ((rc = b.alloc(n * 8 * sizeof(R)))) return rc;
-    if ((rc = make_observer_canvas_device<R>(c, scene, obs, ni, nj, j0, j1, (R*)b.p, nullptr))) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(state0, b.p, n * 8 * sizeof(R), hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    HostMirror m(c);   // (D.mu not held: make_observer_canvas_device takes it)
+    R* d_state0 = m.out(state0, n * 8);
+    if ((rc = m.status())) return rc;
+    if ((rc = make_observer_canvas_device<R>(c, scene, obs, ni, nj, j0, j1, d_state0, nullptr))) return rc;
+    return m.fetch();
 }
 
 // the frame the kernels would use, on device 0 of the context (host pointers, blocking): the frame kernel itself
 template <class R>
 int api::eval_observer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_observer* obs, R* frame, R* omega, int* valid) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     DevObserver<R> ob;
     if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
     DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    HostMirror m(D);
+    if ((rc = m.status())) return rc;
     std::lock_guard<std::mutex> lk(D.mu);
     DevScene<R> sc;
     if ((rc = stationary_scene<R>(D, scene, sc, nullptr, OBSERVER_NEEDS_STATIONARY))) return rc;
-    DevBuf b;
-    if ((rc = b.alloc(sizeof(ObsFrame<R>)))) return rc;
-    if ((rc = observer_frame_launch<R>(sc, ob, (ObsFrame<R>*)b.p, nullptr))) return rc;
-    HIP_TRY(hipDeviceSynchronize());
     ObsFrame<R> F;
-    HIP_TRY(hipMemcpy(&F, b.p, sizeof F, hipMemcpyDeviceToHost));
+    ObsFrame<R>* d_frame = m.out(&F, 1);
+    if ((rc = m.status())) return rc;
+    if ((rc = observer_frame_launch<R>(sc, ob, d_frame, nullptr))) return rc;
+    if ((rc = m.fetch())) return rc;
     if (frame) std::memcpy(frame, F.e, sizeof F.e);
     if (omega) *omega = F.omega;
     if (valid) *valid = F.valid ? 1 : 0;

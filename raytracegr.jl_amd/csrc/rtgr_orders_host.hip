@@ -280,9 +280,7 @@ template <class R>
 int api::trace_orders_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, const R* d_state0, uint64_t ni,
                              uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, R* d_rgb,
                              const rtgr_order_planes* planes, rtgr_counters* ctr, void* stream) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     OrdersPlan plan;
     DevObserver<R> ob;
     DevEmission<R> em;
@@ -297,9 +295,7 @@ template <class R>
 int api::trace_orders(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, const R* state0, uint64_t ni,
                       uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, R* rgb,
                       const rtgr_order_planes* planes, rtgr_counters* ctr) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     OrdersPlan plan;
     DevObserver<R> ob;
     DevEmission<R> em;
@@ -308,34 +304,17 @@ int api::trace_orders(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_sol
     rtgr_order_planes host;
     std::memset(&host, 0, sizeof host);
     if (planes) host = *planes;
-    // the planes the caller asks for, in the order of rtgr_order_planes, and the bytes of each
-    void* const want[6] = {host.count, host.hit32, host.state_end, host.g, host.rgb_order, host.state0};
-    const size_t bytes[6] = {(size_t)n, (size_t)(blocks * n) * sizeof(uint32_t), (size_t)(blocks * n) * 8 * sizeof(R), (size_t)(blocks * n) * sizeof(R),
-                             (size_t)(blocks * n) * 3 * sizeof(R), (size_t)n * 8 * sizeof(R)};
-    DevBuf buf[6], b_in;
-    {
-        DeviceGuard guard(c->devs[0]->dev);
-        if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-        for (int q = 0; q < 6; q++)
-            if (want[q] && (rc = buf[q].alloc(bytes[q]))) return rc;
-        if (state0) {
-            if ((rc = b_in.alloc(bytes[5]))) return rc;
-            HIP_TRY(hipMemcpy(b_in.p, state0, bytes[5], hipMemcpyHostToDevice));
-        }
-    }
+    // the planes the caller asks for, in the order of rtgr_order_planes, then the start states given
+    HostMirror m(c);
     rtgr_order_planes dev;
-    dev.count = (uint8_t*)buf[0].p; dev.hit32 = (uint32_t*)buf[1].p; dev.state_end = buf[2].p; dev.g = buf[3].p; dev.rgb_order = buf[4].p;
-    dev.state0 = buf[5].p;
-    rc = staged_frame<R>(c, n, rgb, nullptr, nullptr, nullptr, [&](DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs*, uint8_t*, R*, hipStream_t st) {
-        int r = trace_orders_on<R>(D, scene, opt, obs, (const R*)b_in.p, ni, nj, shade, emit, ord, d_rgb, planes ? &dev : nullptr, ctr, st);
-        if (r) return r;
-        HIP_TRY(hipStreamSynchronize(st));
-        for (int q = 0; q < 6; q++)
-            if (want[q]) HIP_TRY(hipMemcpy(want[q], buf[q].p, bytes[q], hipMemcpyDeviceToHost));
-        return (int)RTGR_OK;
+    dev.count = m.out(host.count, n); dev.hit32 = m.out(host.hit32, blocks * n); dev.state_end = m.out((R*)host.state_end, blocks * n * 8);
+    dev.g = m.out((R*)host.g, blocks * n); dev.rgb_order = m.out((R*)host.rgb_order, blocks * n * 3); dev.state0 = m.out((R*)host.state0, n * 8);
+    const R* d_state0 = m.in(state0, n * 8);
+    if ((rc = m.status())) return rc;
+    return staged_frame<R>(c, n, rgb, nullptr, nullptr, nullptr, [&](DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs*, uint8_t*, R*, hipStream_t st) {
+        int r = trace_orders_on<R>(D, scene, opt, obs, d_state0, ni, nj, shade, emit, ord, d_rgb, planes ? &dev : nullptr, ctr, st);
+        return r ? r : m.fetch(st);
     });
-    DeviceGuard guard(c->devs[0]->dev);   // (the buffers are freed on their device)
-    return rc;
 }
 
 RTGR_INSTANTIATE_F64_F32(api::trace_orders_device);

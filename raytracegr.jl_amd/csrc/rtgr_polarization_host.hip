@@ -93,9 +93,7 @@ template <class R>
 int api::trace_polarized_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
                                 const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_polarization* pol, R* d_rgb, const rtgr_ray_outputs* out,
                                 R* d_g, R* d_q, R* d_u, R* d_aux, rtgr_counters* ctr, void* stream) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     PolStage<R> stage;
     if ((rc = polarized_check<R>(scene, emit, pol, obs, d_q, d_u, stage))) return rc;
     if (!d_rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
@@ -110,42 +108,26 @@ template <class R>
 int api::trace_polarized(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
                          const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_polarization* pol, R* rgb, const rtgr_ray_outputs* out, R* g,
                          R* q, R* u, R* aux, rtgr_counters* ctr) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     PolStage<R> stage;
     if ((rc = polarized_check<R>(scene, emit, pol, obs, q, u, stage))) return rc;
     if (!rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     if ((rc = canvas_check(ni, nj, POLARIZATION_CANVAS))) return rc;
     const uint64_t n = ni * nj;
-    const size_t bytes = (size_t)n * sizeof(R);
-    DevBuf b_q, b_u, b_aux;
-    {
-        DeviceGuard guard(c->devs[0]->dev);
-        if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
-        if ((rc = b_q.alloc(bytes)) || (rc = b_u.alloc(bytes)) || (aux && (rc = b_aux.alloc(bytes)))) return rc;
-    }
-    stage.q = (R*)b_q.p; stage.u = (R*)b_u.p; stage.aux = (R*)b_aux.p;
-    rc = staged_frame<R>(c, n, rgb, out, nullptr, g, [&](DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs* d_out, uint8_t*, R* d_g, hipStream_t st) {
+    HostMirror m(c);
+    stage.q = m.out(q, n); stage.u = m.out(u, n); stage.aux = m.out(aux, n);
+    if ((rc = m.status())) return rc;
+    return staged_frame<R>(c, n, rgb, out, nullptr, g, [&](DeviceCtx& D, R* d_rgb, const rtgr_ray_outputs* d_out, uint8_t*, R* d_g, hipStream_t st) {
         int r = trace_observer_on<R>(D, scene, opt, obs, ni, nj, shade, emit, d_rgb, d_out, d_g, ctr, st, &stage);
-        if (r) return r;
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(q, b_q.p, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(u, b_u.p, bytes, hipMemcpyDeviceToHost));
-        if (aux) HIP_TRY(hipMemcpy(aux, b_aux.p, bytes, hipMemcpyDeviceToHost));
-        return (int)RTGR_OK;
+        return r ? r : m.fetch(st);
     });
-    DeviceGuard guard(c->devs[0]->dev);   // (the buffers are freed on their device)
-    return rc;
 }
 
 // the model at n pairs of states under obs, on device 0 of the context (host pointers): the polarization kernel itself, in point mode
 template <class R>
 int api::eval_polarization(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_polarization* pol,
                            const rtgr_observer* obs, const R* s0, const R* s_end, uint64_t n, R* kappa, R* f_em, R* aux, R* delta, R* q, R* u, int* valid) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!pol) return fail(RTGR_ERR_BAD_ARG, "rtgr_polarization is NULL (pol)");
     if (!emit) return fail(RTGR_ERR_BAD_ARG, "rtgr_disk_emission is NULL (emit)");
     if (!obs) return fail(RTGR_ERR_BAD_ARG, "rtgr_observer is NULL (obs)");
@@ -158,45 +140,26 @@ int api::eval_polarization(rtgr_context* ctx, const rtgr_scene* scene, const rtg
     DevObserver<R> ob;
     if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
     DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    HostMirror m(D);
+    if ((rc = m.status())) return rc;
     std::lock_guard<std::mutex> lk(D.mu);
     if ((rc = stationary_scene<R>(D, scene, P.sc, nullptr, POLARIZATION_NEEDS_STATIONARY))) return rc;
     if (n == 0) return RTGR_OK;
-    const size_t sbytes = (size_t)n * 8 * sizeof(R), one = (size_t)n * sizeof(R);
-    DevBuf d_s0, d_se, d_frame, d_k, d_f, d_a, d_d, d_q, d_u, d_v;
-    if ((rc = d_s0.alloc(sbytes)) || (rc = d_se.alloc(sbytes)) || (rc = d_frame.alloc(sizeof(ObsFrame<R>)))) return rc;
-    if (kappa && (rc = d_k.alloc(2 * one))) return rc;
-    if (f_em && (rc = d_f.alloc(4 * one))) return rc;
-    if (aux && (rc = d_a.alloc(one))) return rc;
-    if (delta && (rc = d_d.alloc(one))) return rc;
-    if (q && (rc = d_q.alloc(one))) return rc;
-    if (u && (rc = d_u.alloc(one))) return rc;
-    if (valid && (rc = d_v.alloc((size_t)n * sizeof(int)))) return rc;
-    HIP_TRY(hipMemcpy(d_s0.p, s0, sbytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_se.p, s_end, sbytes, hipMemcpyHostToDevice));
-    if ((rc = observer_frame_launch<R>(P.sc, ob, (ObsFrame<R>*)d_frame.p, nullptr))) return rc;
-    P.q = (R*)d_q.p; P.u = (R*)d_u.p; P.aux = (R*)d_a.p; P.kappa = (R*)d_k.p; P.f_em = (R*)d_f.p; P.delta = (R*)d_d.p; P.valid = (int*)d_v.p;
-    P.state0 = (const R*)d_s0.p; P.state_end = (const R*)d_se.p;
-    P.n = n; P.mode = POL_POINTS; P.obs = (const ObsFrame<R>*)d_frame.p;
+    P.state0 = m.in(s0, (size_t)n * 8); P.state_end = m.in(s_end, (size_t)n * 8);
+    ObsFrame<R>* d_frame = m.scratch<ObsFrame<R>>(1);
+    P.kappa = m.out(kappa, (size_t)n * 2); P.f_em = m.out(f_em, (size_t)n * 4); P.aux = m.out(aux, n); P.delta = m.out(delta, n);
+    P.q = m.out(q, n); P.u = m.out(u, n); P.valid = m.out(valid, n);
+    if ((rc = m.status())) return rc;
+    if ((rc = observer_frame_launch<R>(P.sc, ob, d_frame, nullptr))) return rc;
+    P.n = n; P.mode = POL_POINTS; P.obs = d_frame;
     if ((rc = polarize_launch<R>(P, nullptr))) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (kappa) HIP_TRY(hipMemcpy(kappa, d_k.p, 2 * one, hipMemcpyDeviceToHost));
-    if (f_em) HIP_TRY(hipMemcpy(f_em, d_f.p, 4 * one, hipMemcpyDeviceToHost));
-    if (aux) HIP_TRY(hipMemcpy(aux, d_a.p, one, hipMemcpyDeviceToHost));
-    if (delta) HIP_TRY(hipMemcpy(delta, d_d.p, one, hipMemcpyDeviceToHost));
-    if (q) HIP_TRY(hipMemcpy(q, d_q.p, one, hipMemcpyDeviceToHost));
-    if (u) HIP_TRY(hipMemcpy(u, d_u.p, one, hipMemcpyDeviceToHost));
-    if (valid) HIP_TRY(hipMemcpy(valid, d_v.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    return m.fetch();
 }
 
 // (Y(k, f), h(k, f)) at n states and vectors: the kernel's own forms
 template <class R>
 int api::eval_walker_penrose(rtgr_context* ctx, const rtgr_scene* scene, const R* s, const R* f, uint64_t n, R* kappa) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!scene) return fail(RTGR_ERR_BAD_ARG, "scene is NULL");
     if (n && (!s || !f || !kappa)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_walker_penrose: NULL argument");
     if (n > (1ull << 32)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_walker_penrose: at most 2^32 points per call");
@@ -207,22 +170,16 @@ int api::eval_walker_penrose(rtgr_context* ctx, const rtgr_scene* scene, const R
     PolArgs<R> P;
     std::memset(&P, 0, sizeof P);
     DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    HostMirror m(D);
+    if ((rc = m.status())) return rc;
     std::lock_guard<std::mutex> lk(D.mu);
     if ((rc = stationary_scene<R>(D, scene, P.sc, nullptr, POLARIZATION_NEEDS_STATIONARY))) return rc;
     if (n == 0) return RTGR_OK;
-    const size_t one = (size_t)n * sizeof(R);
-    DevBuf d_s, d_f, d_k;
-    if ((rc = d_s.alloc(8 * one)) || (rc = d_f.alloc(4 * one)) || (rc = d_k.alloc(2 * one))) return rc;
-    HIP_TRY(hipMemcpy(d_s.p, s, 8 * one, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_f.p, f, 4 * one, hipMemcpyHostToDevice));
-    P.kappa = (R*)d_k.p; P.state0 = (const R*)d_s.p; P.fvec = (const R*)d_f.p;
+    P.state0 = m.in(s, (size_t)n * 8); P.fvec = m.in(f, (size_t)n * 4); P.kappa = m.out(kappa, (size_t)n * 2);
+    if ((rc = m.status())) return rc;
     P.n = n; P.mode = POL_FORMS;
     if ((rc = polarize_launch<R>(P, nullptr))) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(kappa, d_k.p, 2 * one, hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    return m.fetch();
 }
 
 RTGR_INSTANTIATE_F64_F32(api::polarization_device);

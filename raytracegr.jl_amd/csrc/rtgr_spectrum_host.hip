@@ -112,9 +112,7 @@ int api::trace_spectrum(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_s
 template <class R>
 int api::eval_spectrum(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_disk_emission* emit, const rtgr_spectrum* spec, const R* xyg, uint64_t n,
                        double* axis, int64_t* bin, double* val) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (n && !xyg) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_spectrum: xyg is NULL");
     SpecDev S;
     PixelWeight W;
@@ -122,23 +120,18 @@ int api::eval_spectrum(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_di
     if (n > SPEC_MAX_POINT_VALUES || n * S.nb > SPEC_MAX_POINT_VALUES)
         return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_spectrum: n x nb = " + std::to_string(n) + " x " + std::to_string(S.nb) + ": at most 2^26 per call");
     DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    HostMirror m(D);
+    if ((rc = m.status())) return rc;
     std::lock_guard<std::mutex> lk(D.mu);
     DevScene<R> sc;
     if ((rc = stationary_scene<R>(D, scene, sc, nullptr, EMISSION_NEEDS_STATIONARY))) return rc;
-    const size_t nval = (size_t)(S.kind == RTGR_SPEC_THERMAL ? n * S.nb : n);
-    DevBuf d_xyg, d_axis, d_bin, d_val;
-    if ((n && (rc = d_xyg.alloc((size_t)n * 3 * sizeof(R)))) || (axis && (rc = d_axis.alloc((size_t)S.nb * sizeof(double)))) ||
-        (bin && n && (rc = d_bin.alloc((size_t)n * sizeof(int64_t)))) || (val && nval && (rc = d_val.alloc(nval * sizeof(double)))))
-        return rc;
-    if (n) HIP_TRY(hipMemcpy(d_xyg.p, xyg, (size_t)n * 3 * sizeof(R), hipMemcpyHostToDevice));
-    if ((rc = spec_points_launch<R>((const R*)d_xyg.p, n, S, (double*)d_axis.p, (int64_t*)d_bin.p, (double*)d_val.p, nullptr))) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (axis) HIP_TRY(hipMemcpy(axis, d_axis.p, (size_t)S.nb * sizeof(double), hipMemcpyDeviceToHost));
-    if (bin && n) HIP_TRY(hipMemcpy(bin, d_bin.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (val && nval) HIP_TRY(hipMemcpy(val, d_val.p, nval * sizeof(double), hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    const R* d_xyg = m.in(xyg, (size_t)n * 3);
+    double* d_axis = m.out(axis, S.nb);
+    int64_t* d_bin = m.out(bin, n);
+    double* d_val = m.out(val, (size_t)(S.kind == RTGR_SPEC_THERMAL ? n * S.nb : n));
+    if ((rc = m.status())) return rc;
+    if ((rc = spec_points_launch<R>(d_xyg, n, S, d_axis, d_bin, d_val, nullptr))) return rc;
+    return m.fetch();
 }
 
 RTGR_INSTANTIATE_F64_F32(api::spectrum_device);

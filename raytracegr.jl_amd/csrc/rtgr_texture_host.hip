@@ -14,9 +14,7 @@ static TableIds g_texture_ids{TEXTURE_ID_TAG, TEXTURE_ID_MASK};
 constexpr EntryWords SHADED_WORDS = {"rtgr_trace_shaded_*", "shading", true};
 
 int api::texture_load(rtgr_context* ctx, const rtgr_texture_desc* desc, const double* texels, uint64_t* id_out) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!desc || !texels || !id_out) return fail(RTGR_ERR_BAD_ARG, "rtgr_texture_load: NULL argument");
     const uint32_t W = desc->width, H = desc->height;
     if (W < 2u || W > RTGR_TEXTURE_MAX_SIDE || H < 2u || H > RTGR_TEXTURE_MAX_SIDE)
@@ -43,9 +41,7 @@ int api::texture_load(rtgr_context* ctx, const rtgr_texture_desc* desc, const do
 }
 
 int api::texture_unload(rtgr_context* ctx, uint64_t id) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     const bool found = table_unload(c, &DeviceCtx::textures, id, true);   // (id 0: all of them)
     if (!found) return fail(RTGR_ERR_BAD_ARG, "rtgr_texture_unload: no texture with id " + std::to_string(id) + " is loaded in this context");
     return RTGR_OK;
@@ -109,9 +105,7 @@ template <class R>
 int api::trace_shaded_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
                              const rtgr_shade* shade, const rtgr_aa* aa, R* d_rgb, const rtgr_ray_outputs* out, uint8_t* d_refined,
                              rtgr_counters* ctr, rtgr_aa_stats* stats, void* stream) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!d_rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     if ((rc = shaded_check(cam, aa, d_refined, stats, ni, nj))) return rc;
     DeviceCtx* D = nullptr;
@@ -124,9 +118,7 @@ template <class R>
 int api::trace_shaded(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj,
                       const rtgr_shade* shade, const rtgr_aa* aa, R* rgb, const rtgr_ray_outputs* out, uint8_t* refined, rtgr_counters* ctr,
                       rtgr_aa_stats* stats) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!rgb) return fail(RTGR_ERR_BAD_ARG, "rgb is NULL");
     if ((rc = shaded_check(cam, aa, refined, stats, ni, nj))) return rc;
     if ((rc = check_redshift_outputs(out))) return rc;
@@ -138,17 +130,15 @@ int api::trace_shaded(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_sol
 // the sampler at n points, on device 0 of the context (host pointers): rgb goes up too — a "no sample" point keeps its entry
 template <class R>
 int api::eval_texture(rtgr_context* ctx, uint64_t texture, uint32_t filter, const R* p, uint64_t n, const R* disk_range, R* rgb) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if ((n && !p) || (n && !rgb)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_texture: NULL argument");
     if ((rc = filter_check(filter))) return rc;
     if (n > (1ull << 32)) return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_texture: at most 2^32 points per call");
     if (disk_range && !(std::isfinite((double)disk_range[0]) && std::isfinite((double)disk_range[1])))
         return fail(RTGR_ERR_BAD_ARG, "rtgr_eval_texture: disk_range = {r_in, r_out} must be finite");
     DeviceCtx& D = *c->devs[0];
-    DeviceGuard guard(D.dev);
-    if (!guard.ok) return fail(RTGR_ERR_HIP, "hipSetDevice failed");
+    HostMirror m(D);
+    if ((rc = m.status())) return rc;
     TextureTable t;
     {
         std::lock_guard<std::mutex> lk(D.mu);
@@ -157,17 +147,13 @@ int api::eval_texture(rtgr_context* ctx, uint64_t texture, uint32_t filter, cons
         t = *found;
     }
     if (n == 0) return RTGR_OK;
-    const size_t bytes = (size_t)n * 3 * sizeof(R);
-    DevBuf d_p, d_rgb;
-    if ((rc = d_p.alloc(bytes)) || (rc = d_rgb.alloc(bytes))) return rc;
-    HIP_TRY(hipMemcpy(d_p.p, p, bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_rgb.p, rgb, bytes, hipMemcpyHostToDevice));
+    const R* d_p = m.in(p, (size_t)n * 3);
+    R* d_rgb = m.inout(rgb, (size_t)n * 3);
+    if ((rc = m.status())) return rc;
     if ((rc = eval_texture_launch<R>((const R*)(sizeof(R) == 8 ? t.d64 : t.d32), t.W, t.H, filter, disk_range != nullptr, disk_range ? disk_range[0] : R(0),
-                                     disk_range ? disk_range[1] : R(0), (const R*)d_p.p, n, (R*)d_rgb.p, nullptr)))
+                                     disk_range ? disk_range[1] : R(0), d_p, n, d_rgb, nullptr)))
         return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(rgb, d_rgb.p, bytes, hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    return m.fetch();
 }
 
 RTGR_INSTANTIATE_F64_F32(shade_resolve);

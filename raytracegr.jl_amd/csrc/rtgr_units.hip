@@ -31,9 +31,7 @@ int unload_locked(rtgr_context* c, uint64_t id) {
     return RTGR_OK;
 }
 int api::user_metric_unload(rtgr_context* ctx, uint64_t id) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     std::lock_guard<std::mutex> load_lock(c->modules_mu);
     return unload_locked(c, id);
 }
@@ -68,17 +66,16 @@ static int probe_trace(DeviceCtx& D, const rtgr_scene& sc, long split, ProbeFram
         std::memset(&cam, 0, sizeof cam);
         cam.pos[1] = 4; cam.pos[2] = -2; cam.widthx[1] = 1; cam.widthy[3] = 1; cam.normal[2] = 1;
     }
-    DevBuf b;
-    const size_t off_se = 3 * N * sizeof(R), off_lam = off_se + 8 * N * sizeof(R), off_na = off_lam + N * sizeof(R),
-                 off_nr = off_na + N * 4, off_hit = off_nr + N * 4, off_st = off_hit + N * 4, total = off_st + N;
+    // the frame's vectors are the call's host arrays, an array of the device for each
+    f.rgb.resize(3 * N); f.se.resize(8 * N); f.lam.resize(N); f.na.resize(N); f.nr.resize(N); f.status.resize(N); f.hit.resize(N);
     int rc;
-    if ((rc = b.alloc(total))) return rc;
-    char* base = (char*)b.p;
-    HIP_TRY(hipMemset(base, 0, total));
+    HostMirror m(D);
     rtgr_ray_outputs out;
     std::memset(&out, 0, sizeof out);
-    out.state_end = base + off_se; out.lambda_end = base + off_lam; out.n_accept = (uint32_t*)(base + off_na);
-    out.n_reject = (uint32_t*)(base + off_nr); out.status = (uint8_t*)(base + off_st); out.hit32 = (uint32_t*)(base + off_hit);
+    R* d_rgb = m.out(f.rgb.data(), 3 * N);
+    out.state_end = m.out(f.se.data(), 8 * N); out.lambda_end = m.out(f.lam.data(), N); out.n_accept = m.out(f.na.data(), N);
+    out.n_reject = m.out(f.nr.data(), N); out.status = m.out(f.status.data(), N); out.hit32 = m.out(f.hit.data(), N);
+    if ((rc = m.status()) || (rc = m.zero())) return rc;   // (every array zeroed ahead of the trace)
     Knobs mine;                                       // this call's launch options: the device's, with the pass structure (and grid cap) asked for
     { std::lock_guard<std::mutex> lk(D.mu); mine = D.knobs; }
     mine.split = split;
@@ -100,7 +97,6 @@ static int probe_trace(DeviceCtx& D, const rtgr_scene& sc, long split, ProbeFram
         const unsigned run_no = probe_runs++;
         const unsigned pattern = (run_no & 1u) ? 0x40091eb8u + 0x00010101u * (run_no & 0x3eu) : 0x7ff4a5a5u + 0x01010101u * (run_no & 0x3eu);
         {
-            DeviceGuard guard(D.dev);
             if ((rc = misc_poison_registers(D.num_cu, pattern, nullptr))) return rc;
             std::lock_guard<std::mutex> lk(D.mu);
             StreamState* ss = nullptr;
@@ -110,19 +106,9 @@ static int probe_trace(DeviceCtx& D, const rtgr_scene& sc, long split, ProbeFram
             const size_t scrub = ss->ws_bytes < ((size_t)256 << 20) ? ss->ws_bytes : ((size_t)256 << 20);   // (the probe's 1024 rays live in its head)
             HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ss->ws, (int)pattern, scrub / 4, nullptr));
         }
-        rc = trace_device<R>(D, &sc, &opt, d_state0, d_state0 ? nullptr : &cam, NI, NJ, 0, NJ, (R*)base, &out, nullptr, nullptr);
+        rc = trace_device<R>(D, &sc, &opt, d_state0, d_state0 ? nullptr : &cam, NI, NJ, 0, NJ, d_rgb, &out, nullptr, nullptr);
     }
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    f.rgb.resize(3 * N); f.se.resize(8 * N); f.lam.resize(N); f.na.resize(N); f.nr.resize(N); f.status.resize(N); f.hit.resize(N);
-    HIP_TRY(hipMemcpy(f.rgb.data(), base, off_se, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(f.se.data(), base + off_se, 8 * N * sizeof(R), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(f.lam.data(), base + off_lam, N * sizeof(R), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(f.na.data(), base + off_na, N * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(f.nr.data(), base + off_nr, N * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(f.status.data(), base + off_st, N, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(f.hit.data(), base + off_hit, N * 4, hipMemcpyDeviceToHost));
-    return RTGR_OK;
+    return rc ? rc : m.fetch();
 }
 template <class R>
 static bool probe_same_bits(const ProbeFrame<R>& a, const ProbeFrame<R>& b) {
@@ -175,20 +161,18 @@ static int probe_unit(DeviceCtx& D, const UserModule& U, std::string* why) {
         // the source offers sample objects (rtgr_user_sample): they take the small sphere's place — up to 14 beside the sky and the
         // far plane —, and the comparisons below then run through the unit's OWN distance / objcolor / reach functions: a reach bound
         // that lies about a sample keeps the unit from loading
-        DevBuf b;
         const size_t bytes = sizeof(unsigned) * (1 + RTGR_MAX_SAMPLES) + sizeof(double) * 9 * RTGR_MAX_SAMPLES + 8;
-        if ((rc = b.alloc(bytes))) return rc;
-        HIP_TRY(hipMemset(b.p, 0, bytes));
-        unsigned* d_count = (unsigned*)b.p;
-        unsigned* d_types = d_count + 1;
-        double* d_p = (double*)((char*)b.p + ((sizeof(unsigned) * (1 + RTGR_MAX_SAMPLES) + 7) & ~(size_t)7));
-        HIP_TRY(launch_module(U.samples, 1, 64, (hipStream_t) nullptr, d_count, d_types, d_p));
-        HIP_TRY(hipDeviceSynchronize());
-        std::vector<char> host(bytes);
-        HIP_TRY(hipMemcpy(host.data(), b.p, bytes, hipMemcpyDeviceToHost));
+        const size_t at_p = (sizeof(unsigned) * (1 + RTGR_MAX_SAMPLES) + 7) & ~(size_t)7;
+        std::vector<char> host(bytes);   // the block: the count, the types, then (8-aligned, at_p) 9 parameters of each
+        HostMirror m(D);
+        char* d_block = m.out(host.data(), bytes);
+        if ((rc = m.status()) || (rc = m.zero())) return rc;
+        unsigned* d_count = (unsigned*)d_block;
+        HIP_TRY(launch_module(U.samples, 1, 64, (hipStream_t) nullptr, d_count, d_count + 1, (double*)(d_block + at_p)));
+        if ((rc = m.fetch())) return rc;
         const unsigned count = *(const unsigned*)host.data();
         const unsigned* types = (const unsigned*)host.data() + 1;
-        const double* ps = (const double*)(host.data() + ((const char*)d_p - (const char*)b.p));
+        const double* ps = (const double*)(host.data() + at_p);
         if (count > 0 && count <= RTGR_MAX_SAMPLES) {
             sc.nobj = 2;
             for (unsigned k = 0; k < count && sc.nobj < RTGR_MAX_OBJECTS; k++) {
@@ -393,9 +377,7 @@ static std::string csrc_dir() {  // the device headers ship next to the library:
 
 
 int api::user_metric_load(rtgr_context* ctx, const char* code_object_path, uint64_t* id_out) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!code_object_path || !*code_object_path) return fail(RTGR_ERR_BAD_ARG, "code object path is NULL or empty");
     std::vector<char> image;
     if ((rc = read_file(code_object_path, image))) return rc;
@@ -539,9 +521,7 @@ static int write_image(const unit_build::Built& built, const char* code_object_p
 }
 
 int api::user_unit_compile(rtgr_context* ctx, const char* source, int stationary, const rtgr_scene* built_for, uint64_t* id_out) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     // Opt-in disk cache for callers without a build system of their own (C, Julia): with RTGR_UNIT_CACHE=<directory> the code object
     // of (source, what it is built for, the device headers) is kept there and a later process loads it in milliseconds instead of
     // compiling for seconds.  The key covers everything the image depends on; the file is audited and probed at load like any other.
@@ -780,12 +760,11 @@ template int auto_scene_check<float>(DeviceCtx&, const rtgr_scene*, const rtgr_s
                                      uint64_t, uint64_t, hipStream_t);
 
 int api::scene_check(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_camera* cam, uint64_t ni, uint64_t nj, int is_f32) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!scene || !opt || !cam) return fail(RTGR_ERR_BAD_ARG, "NULL argument");
     if (ni == 0 || nj == 0 || ni > 256 || nj > 256) return fail(RTGR_ERR_BAD_ARG, "rtgr_scene_check: a canvas of 1 .. 256 x 1 .. 256 rays");
-    if (is_f32) return fail(RTGR_ERR_BAD_ARG, "rtgr_scene_check: Float32 scenes run ONE pass structure (the single FULL pass): nothing to compare");
+    if (is_f32) return fail(RTGR_ERR_BAD_ARG, "rtgr_scene_check: Float32 is not checked: a Float32 scene of a user unit runs ONE pass structure (the single FULL pass) — nothing to "
+                                                  "compare —, and the FAR + NEAR passes of a Float32 list of 32 or more built-in objects are the library's own arithmetic");
     DeviceCtx& D = *c->devs[0];
     DeviceGuard guard(D.dev);
     // bit for bit where every kernel is the library's own arithmetic (a built-in metric — closed form or generic —, with or without
@@ -797,9 +776,7 @@ int api::scene_check(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solv
 }
 
 int api::user_unit_info(rtgr_context* ctx, uint64_t id, rtgr_unit_info* info) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     if (!info) return fail(RTGR_ERR_BAD_ARG, "info is NULL");
     DeviceCtx& d = *c->devs[0];
     std::lock_guard<std::mutex> lk(d.mu);
@@ -838,9 +815,7 @@ int api::listing_repair(const char* listing_path, const char* repaired_path, int
 }
 
 int api::user_metric_loaded(rtgr_context* ctx, uint64_t id) {
-    rtgr_context* c = nullptr;
-    int rc = resolve_ctx(ctx, &c);
-    if (rc) return rc;
+    RESOLVE_CONTEXT();
     DeviceCtx& d = *c->devs[0];
     std::lock_guard<std::mutex> lk(d.mu);
     if (id == 0) return d.modules.empty() ? 0 : 1;
