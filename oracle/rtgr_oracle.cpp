@@ -275,10 +275,32 @@ inline void expanding_isotropic(const S xx[D], T M, T H, S g[D][D]) {
     g[1][1] = g[2][2] = g[3][3] = pow2(s) * pow2(psi2);
 }
 
+// A fourth stand-in: g_ab = η_ab + a quadratic polynomial in (t, x, y, z) per component — the field whose Catmull-Rom interpolant
+// on ANY grid is the field itself, so that the grid kernels (which the oracle has no twin of: it knows no grids) can be held to
+// true geodesics (tests/grid_truth.py).  Here only the FORMULA: the same algorithm on the same field.  Coefficients
+// [component tt tx ty tz xx xy xz yy yz zz][monomial 1 x y z xx yy zz xy xz yz t tt tx ty tz], set by rtgr_oracle_set_polynomial.
+// Selected by rtgr_scene.user_metric == RTGR_ORACLE_POLY.
+constexpr uint64_t RTGR_ORACLE_POLY = 0x202;
+static double g_poly_coef[10][15];
+template <class T, class S>
+inline void polynomial_metric(const S xx[D], S g[D][D]) {
+    const S &t = xx[0], &x = xx[1], &y = xx[2], &z = xx[3];
+    const S mon[15] = {cst<T, S>(T(1)), x, y, z, x * x, y * y, z * z, x * y, x * z, y * z, t, t * t, t * x, t * y, t * z};
+    int c = 0;
+    for (int p = 0; p < D; p++)
+        for (int q = p; q < D; q++, c++) {
+            S v = cst<T, S>(T(p == q ? (p == 0 ? -1 : 1) : 0) + T(g_poly_coef[c][0]));
+            for (int m = 1; m < 15; m++)
+                if (g_poly_coef[c][m] != 0.0) v = v + T(g_poly_coef[c][m]) * mon[m];
+            g[p][q] = g[q][p] = v;
+        }
+}
+
 template <class T, class S>
 inline void metric_eval(const rtgr_scene& sc, const S x[D], S g[D][D]) {
     const uint32_t kind = sc.metric & ~RTGR_METRIC_GENERIC;  // the flag picks a product code path, not a metric
     if (kind == RTGR_MINKOWSKI) minkowski<T, S>(x, g);
+    else if (kind == RTGR_USER && sc.user_metric == RTGR_ORACLE_POLY) polynomial_metric<T, S>(x, g);
     else if (kind == RTGR_USER && sc.user_metric == RTGR_ORACLE_ZOO) helper_zoo<T, S>(x, T(sc.M), g);
     else if (kind == RTGR_USER && sc.user_metric == RTGR_ORACLE_EXPANDING) expanding_isotropic<T, S>(x, T(sc.M), T(sc.a), g);
     else if (kind == RTGR_USER) schwarzschild_isotropic<T, S>(x, T(sc.M), g);
@@ -877,6 +899,12 @@ int rtgr_oracle_metric_plain_f64(const rtgr_scene* sc, const double* x, uint64_t
         metric_eval<double, double>(*sc, x + 4 * p, gg);
         std::memcpy(g + 16 * p, gg, sizeof gg);
     }
+    return RTGR_OK;
+}
+// the coefficient table [10][15] of the polynomial metric (RTGR_ORACLE_POLY); process-wide, set before the calls that evaluate it
+int rtgr_oracle_set_polynomial(const double* coef) {
+    if (!coef) return RTGR_ERR_BAD_ARG;
+    std::memcpy(g_poly_coef, coef, sizeof g_poly_coef);
     return RTGR_OK;
 }
 int rtgr_oracle_inv4_f64(const double* m, double* o) {

@@ -86,6 +86,14 @@ def metric_plain(scene, x):
     return g
 
 
+def set_polynomial(coef):
+    """the (10, 15) coefficient table of the polynomial metric (tests/grid_truth.py): what a kind-USER scene whose user_metric is
+    grid_truth.POLY_MARKER evaluates from now on"""
+    coef = np.ascontiguousarray(coef, np.float64)
+    assert coef.shape == (10, 15)
+    assert lib().rtgr_oracle_set_polynomial(C.c_void_p(coef.ctypes.data)) == 0
+
+
 def inv4(m):
     m = np.ascontiguousarray(m, np.float64)
     o = np.zeros((4, 4))

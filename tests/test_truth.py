@@ -28,6 +28,8 @@ USER = "schw_iso"   # example2's scene around an isotropic-coordinates Schwarzsc
 TOL_SPHERE = 1e-9
 TOL_CAPTURED_LAMBDA, TOL_CAPTURED_STATE = 1e-8, 1e-5
 PLANE = 2  # 1-based index of Plane(-20) in every scene of scenes.scene_variant
+# Float32 at tol = eps(Float32)^(3/4) (test_hip_float32_global_error_against_true_geodesics; tests/test_grid_truth.py uses the same)
+F32_BARS = dict(tol_sphere=5e-4, tol_cap_lambda=5e-3, tol_cap_state=None, extra_flips=1, tol_cap_rgb=1e-7)   # (1/3 in Float32)
 
 
 def _truth(name):
@@ -217,8 +219,7 @@ def test_hip_float32_global_error_against_true_geodesics(name):
     sc, cam = scene_variant(name)
     n = int(f["n"])
     r = hip_trace(lib, sc, rt.solver_defaults(np.float32), n, n, cam=cam, dtype=np.float32)
-    _check_against_truth(name, r, f, tol_sphere=5e-4, tol_cap_lambda=5e-3, tol_cap_state=None, extra_flips=1,
-                         tol_cap_rgb=1e-7)   # (1/3 in Float32)
+    _check_against_truth(name, r, f, **F32_BARS)
 
 
 @pytest.mark.gpu

@@ -148,20 +148,33 @@ def object_colour(o, pos):
     return np.array([1.0, np.mod(rc, 1.0), np.mod(12 * np.arctan2(pos[2], pos[1]) / np.pi, 1.0)])
 
 
-def pixel_state(scene, cam, ni, nj, i, j):
-    """make_canvas for pixel (i, j), 0-based (:463-476)."""
+def pixel_state(scene, cam, ni, nj, i, j, metric_fn=None):
+    """make_canvas for pixel (i, j), 0-based (:463-476).  `metric_fn(pos) -> g[4][4]`: a field other than the scene's own
+    (tests/grid_truth.py)."""
     dx = (i + 0.5) / ni - 0.5
     dy = (j + 0.5) / nj - 0.5
     pos = np.array(cam.pos) + dx * np.array(cam.widthx) + dy * np.array(cam.widthy)
     n = np.array(cam.normal) + dx * np.array(cam.widthx) + dy * np.array(cam.widthy)
-    g = metric(scene, pos)
+    g = metric(scene, pos) if metric_fn is None else metric_fn(pos)
     t = np.linalg.solve(g, np.array([1.0, 0, 0, 0]))
     u = (t / np.sqrt(-t @ g @ t) + n / np.sqrt(n @ g @ n)) / np.sqrt(2.0)
     return np.concatenate([pos, u])
 
 
-def trace_ray(scene, opt, s0, rtol=1e-13, atol=1e-15, max_step=0.2):
-    """-> dict(state_end, lambda_end, hit (1-based object, 0 = nothing), rgb, nfev, clearance).
+def box_margin(box, pos):
+    """> 0 inside `box`, < 0 outside: the smallest distance of pos[a] to the two faces of its axis.  box[a] = (lo, hi) for
+    the axes (x, y, z), or (t, x, y, z) for a box with a time range."""
+    first = 4 - len(box)
+    return min(min(pos[first + a] - lo, hi - pos[first + a]) for a, (lo, hi) in enumerate(box))
+
+
+def trace_ray(scene, opt, s0, rtol=1e-13, atol=1e-15, max_step=0.2, rhs_fn=None, box=None, guard=None):
+    """-> dict(state_end, lambda_end, hit (1-based object, 0 = nothing), rgb, nfev, clearance, lambda_exit, state_exit).
+
+    `rhs_fn`: the right-hand side of another field than the scene's metric (tests/grid_truth.py: a polynomial, ∂_t g included).
+    `box`: the first λ at which the ray leaves it is recorded as lambda_exit (inf: never) by an event that is NOT terminal —
+    the ray goes on, so that an object met after leaving is seen as well.  `guard`: a radius at which a ray that has met
+    nothing ends (a scene without a sky: the field need not be a spacetime at any distance); not an object, hit = 0.
 
     `max_step`: scipy looks for an event only between the END POINTS of its steps, and an 8th-order method crosses flat
     space in a handful of them; 0.2 (objects here are ≥ 0.5 across, |ẋ| ≈ 1) keeps a chord from being stepped over.
@@ -176,9 +189,23 @@ def trace_ray(scene, opt, s0, rtol=1e-13, atol=1e-15, max_step=0.2):
         ev = (lambda o: lambda lam, s: object_distance(o, s))(o)
         ev.terminal = True
         events.append(ev)
-    sol = solve_ivp(rhs(scene), (opt.lambda0, opt.lambda1), s0, method="DOP853", rtol=rtol, atol=atol, events=events,
+    if guard is not None:
+        ev = lambda lam, s: guard * guard - s[1] * s[1] - s[2] * s[2] - s[3] * s[3]
+        ev.terminal = True
+        events.append(ev)
+    if box is not None:
+        ev = lambda lam, s: box_margin(box, s)
+        ev.terminal, ev.direction = False, -1
+        events.append(ev)
+    sol = solve_ivp(rhs_fn or rhs(scene), (opt.lambda0, opt.lambda1), s0, method="DOP853", rtol=rtol, atol=atol, events=events,
                     dense_output=True, max_step=max_step)
-    hit_events = [k for k, te in enumerate(sol.t_events) if len(te)]
+    lam_exit, s_exit = np.inf, np.full(8, np.nan)
+    if box is not None:
+        if box_margin(box, s0) < 0:
+            lam_exit, s_exit = opt.lambda0, np.array(s0)
+        elif len(sol.t_events[-1]):
+            lam_exit, s_exit = sol.t_events[-1][0], sol.y_events[-1][0]
+    hit_events = [k for k, te in enumerate(sol.t_events[:len(objs) + (guard is not None)]) if len(te)]
     if hit_events:
         k = hit_events[0]
         lam_end, s_end = sol.t_events[k][0], sol.y_events[k][0]
@@ -198,4 +225,5 @@ def trace_ray(scene, opt, s0, rtol=1e-13, atol=1e-15, max_step=0.2):
         if k + 1 == omin:
             continue
         clearance = min(clearance, min(abs(object_distance(o, path[:, m])) for m in range(path.shape[1])))
-    return dict(state_end=s_end, lambda_end=lam_end, hit=omin, rgb=rgb, nfev=sol.nfev, clearance=clearance)
+    return dict(state_end=s_end, lambda_end=lam_end, hit=omin, rgb=rgb, nfev=sol.nfev, clearance=clearance, lambda_exit=lam_exit,
+                state_exit=s_exit)
