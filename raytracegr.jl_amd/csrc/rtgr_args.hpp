@@ -13,8 +13,20 @@ struct DevObject {
     uint32_t kind;
     uint32_t type;   // RTGR_USER_OBJECT: the caller's tag for rtgr_user_distance / rtgr_user_objcolor (rtgr_object.type)
     R p[9];
+    // What the per-step tests would otherwise form again from wave-uniform data, every step (object_constants, rtgr_scene_host.hip — the
+    // ONE place that computes them):
+    R nR2;           // sphere, bounding sphere of a group / run of groups: −R² as the kernels' own arithmetic rounds it (RN(R·R) in R)
+    R floor_;        // the reach test's rounding floor, rounded UP: sphere F = 2 e R² (1 + 2e), plane Fp = 2 e |p0| (1 + 2e), e = reach_eps<R>()
     uint32_t orig;   // the object's index in the CALLER's list (the device list is regrouped: DevScene)
 };
+
+// The reach test's constants (rtgr_objects.hpp: sphere_reach, plane_out_of_reach).  e = 256 ulp of the scalar type, the
+// relative floor under which a distance counts as rounding noise; guard, the 1e-6 relative margin on the bound; g2 = guard (1 + 2e),
+// the margin with the floor's |D0| term folded in:  |D0| > guard B + e (|D0| + 2R²)  <=>  |D0| (1 − e) > guard B + 2 e R²  <=
+// |D0| > g2 B + 2 e R² (1 + 2e), because 1 / (1 − e) < 1 + 2e.
+template <class R> constexpr R reach_eps() { return sizeof(R) == 8 ? R(0x1p-44) : R(0x1p-15f); }
+template <class R> constexpr R reach_guard() { return R(1) + R(1e-6); }
+template <class R> constexpr R reach_guard2() { return R((double)reach_guard<R>() * (1.0 + 2.0 * (double)reach_eps<R>())); }
 
 // The object list (src/RayTraceGR.jl:433-441: a Vector of any length).  The first RTGR_MAX_OBJECTS objects sit in the kernels' argument
 // block (scalar loads from the kernarg segment), the rest — rare — in a device table the context keeps per distinct list
@@ -222,5 +234,11 @@ struct ResolveArgs {
     uint32_t* n_accept;
     uint32_t* n_reject;
 };
+
+// The argument blocks carry RTGR_MAX_OBJECTS inline objects each, derived constants included: they must stay inside the 4 KB a HIP
+// kernel's argument segment may hold.
+constexpr unsigned RTGR_KERNARG_LIMIT = 4096;
+static_assert(sizeof(TraceArgs<double>) <= RTGR_KERNARG_LIMIT && sizeof(IntegrateArgs<double>) <= RTGR_KERNARG_LIMIT &&
+              sizeof(ResolveArgs<double>) <= RTGR_KERNARG_LIMIT, "a kernel's argument block no longer fits the kernarg segment");
 
 }  // namespace rtgr

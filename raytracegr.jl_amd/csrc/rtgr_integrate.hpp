@@ -443,7 +443,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                     done = RTGR_RAY_NAN;
                 } else {
                     // ---- PI controller in log2 space: q = EEst^β1 / qold^β2 / γ ----------------------
-                    const float le = 0.5f * flog2(fmax1(EEst2, 1e-37f));  // log2 of the error estimate itself (floor 3e-19)
+                    const float le = 0.5f * flog2(fmax1_lit<__builtin_bit_cast(uint32_t, 1e-37f)>(EEst2));  // log2 of the error estimate itself (floor 3e-19)
                     float qf = fexp2(__builtin_fmaf(beta1, le, -beta2 * lq)) * igamma;
                     qf = (EEst2 == 0.0f) ? qmax_inv : fclamp1(qf, qmax_inv, qmin_inv);
         // [budget: reach bound]
@@ -507,22 +507,24 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                                 // value): then outside every member, by at least the same margin, for the whole step — no member's
                                 // distance changes sign.  The floor keeps that margin above the rounding noise of the members' own
                                 // distances (|X_g| − R_g > 64 eps (|X_g| + R_g), the noise is a few eps of |X_i| + R_i <= |X_g| + 2 R_g).
-                                R D0, B, mag;
-                                sphere_reach<R>(G, x, dl, D0, B, mag);
-                                const bool out = D0 > rfma(guard, B, R(256) * eps * mag);
+                                R lhs, rhs;
+                                sphere_reach<R, false>(G, x, dl, lhs, rhs);
+                                const bool out = lhs > rhs;
                                 if (level != 0) { run_out = out; group_out = out; }   // (a lane that has ruled the run out has ruled its groups out)
                                 else group_out = run_out || out;
                                 return __ballot(run && !group_out) != 0ull;
                               },
                               [&](const DevObject<R>& ob, uint32_t o) {   // the spheres of the list: no dispatch, one batch of scalar loads each
-                                R D0, B, mag;
-                                sphere_reach<R>(ob, x, dl, D0, B, mag);
-                                note(group_out || rabs(D0) > rfma(guard, B, R(256) * eps * mag), o);
+                                R lhs, rhs;
+                                sphere_reach<R, true>(ob, x, dl, lhs, rhs);
+                                note(group_out || lhs > rhs, o);
                               },
                               [&](const DevObject<R>& ob, uint32_t o) {   // everything else
                                 bool safe_o;
                                 if (ob.kind == RTGR_PLANE) {
-                                    safe_o = (rabs(x[0] - ob.p[0]) > rfma(guard, dl[0], R(256) * eps * (rabs(x[0]) + rabs(ob.p[0]))));
+                                    R lhs, rhs;
+                                    plane_reach<R>(ob, x, dl, lhs, rhs);
+                                    safe_o = lhs > rhs;
 #ifdef RTGR_USER_OBJECTS
                                 } else if (ob.kind == RTGR_USER_OBJECT) {
 #ifdef RTGR_USER_REACH
@@ -696,7 +698,7 @@ RTGR_DEV void integrate_body(const IntegrateArgs<R>& A) {
                         if (!is_event) {
                             commit = true;
                             t = tnew;
-                            dt = rmin(dtmax, dtnew);
+                            dt = rmin_su(dtmax, dtnew);
                             bool outside = false;   // RTGR_GRID: the step ended outside the valid box (the scan found no event in it)
                             if constexpr (Sampled<R, METRIC>::is) outside = !Sampled<R, METRIC>::inside(MK, xn);
                             if (outside) done = RTGR_RAY_OUTSIDE;

@@ -281,7 +281,7 @@ template <class R, int P, class V>
 RTGR_DEV void fold_sphere(const DevObject<R>& o, const V (&pos)[P][4], V (&dmin)[P]) {
     const V cx = V(o.p[1]), cy = V(o.p[2]), cz = V(o.p[3]);
     const R Rr = o.p[8];
-    const V nR2 = V(-Rr * Rr);
+    const V nR2 = V(o.nR2);   // −R², formed once by the host (object_constants) — the same bits the kernel's own −Rr·Rr gives
     if (Rr < R(0)) {                                                                   // :415-419, sign(R) * (|x − c|² − R²)
 #pragma unroll
         for (int p = 0; p < P; p++) {
@@ -325,15 +325,61 @@ RTGR_DEV void fold_distances(const DevObject<R>& o, const R (&pos)[P][4], R (&dm
 }
 
 // REACH.  Over a step every coordinate stays in a box |x_q(θ) − x_q| <= dl[q].  A sphere's (or bounding sphere's) distance D0 = |X|² − R²,
-// X = x − c, then moves by at most B = Σ_q δ_q (2|X_q| + δ_q); mag >= |X|² + R²: the operands' magnitude, for the callers' rounding floor.
-template <class R, class V>
-RTGR_DEV void sphere_reach(const DevObject<R>& o, const V x[4], const V dl[4], V& D0, V& B, V& mag) {   // (V: as for fold_sphere)
+// X = x − c, then moves by at most B = Σ_q δ_q (2|X_q| + δ_q).
+// (V: as for fold_sphere.  WALK: the object comes from a wave-uniform walk of the list — its −R² is then read from its SGPRs, rfma_sacc)
+template <class R, class V, bool WALK = false>
+RTGR_DEV void sphere_reach_terms(const DevObject<R>& o, const V x[4], const V dl[4], V& D0, V& B) {
     const V X0 = x[1] - V(o.p[1]), X1 = x[2] - V(o.p[2]), X2 = x[3] - V(o.p[3]);
-    const R Rr = o.p[8];
-    D0 = rfma<V>(X0, X0, rfma<V>(X1, X1, rfma<V>(X2, X2, V(-Rr * Rr))));
+    V D2;
+    if constexpr (WALK) D2 = rfma_sacc<V, R>(X2, X2, o.nR2);
+    else D2 = rfma<V>(X2, X2, V(o.nR2));
+    D0 = rfma<V>(X0, X0, rfma<V>(X1, X1, D2));
     B = rfma<V>(dl[1], rfma<V>(V(R(2)), rabs<V>(X0), dl[1]),
                 rfma<V>(dl[2], rfma<V>(V(R(2)), rabs<V>(X1), dl[2]), dl[3] * rfma<V>(V(R(2)), rabs<V>(X2), dl[3])));
-    mag = rabs<V>(D0) + V(R(2) * Rr * Rr);
+}
+// The step cannot change the sign of D0 when |D0| exceeds the move, with its 1e-6 guard, plus a floor of 256 ulp of the operands'
+// magnitude |D0| + 2R² (a distance that is itself rounding noise must go through the real scan): out of reach iff lhs > rhs.
+//     |D0| > guard B + e (|D0| + 2R²)   <=>   |D0| (1 − e) > guard B + 2 e R²   <=   |D0| − g2 B > F,
+// g2 = guard (1 + 2e), F = 2 e R² (1 + 2e) (1 / (1 − e) < 1 + 2e; rtgr_args.hpp: reach_guard2, DevObject::floor_ — formed once, by the
+// host).  So lhs = fma(−g2, B, |D0|) against rhs = F: ONE fma and a compare after D0 and B, each with a single scalar operand (an fma of
+// g2, B and F would read two, and the second costs a v_mov pair).  Rounding to nearest is monotone and F is a value of R: the rounded
+// lhs > F only if the exact |D0| − g2 B > F, and g2 carries a relative slack of e − ulp against its own rounding — the criterion IMPLIES
+// the term-by-term one (tests/test_reach_floor.py), the FAR pass hands over every ray it handed over before, and the frame is the same
+// bit for bit.  ABS = false: the group form, D0 itself instead of |D0| ("outside the bounding sphere").
+// -DRTGR_REACH_TERMWISE_FLOOR=1 builds the term-by-term floor instead (R², 2R², the magnitude and its scaling formed per step and per
+// object, with vector arithmetic on wave-uniform data): an experiment flag for timing one against the other.
+#ifndef RTGR_REACH_TERMWISE_FLOOR
+#define RTGR_REACH_TERMWISE_FLOOR 0
+#endif
+template <class R, bool ABS, class V>
+RTGR_DEV void sphere_reach(const DevObject<R>& o, const V x[4], const V dl[4], V& lhs, V& rhs) {
+#if RTGR_REACH_TERMWISE_FLOOR
+    const V X0 = x[1] - V(o.p[1]), X1 = x[2] - V(o.p[2]), X2 = x[3] - V(o.p[3]);
+    const R Rr = o.p[8];
+    const V D0 = rfma<V>(X0, X0, rfma<V>(X1, X1, rfma<V>(X2, X2, V(-Rr * Rr))));
+    const V B = rfma<V>(dl[1], rfma<V>(V(R(2)), rabs<V>(X0), dl[1]),
+                        rfma<V>(dl[2], rfma<V>(V(R(2)), rabs<V>(X1), dl[2]), dl[3] * rfma<V>(V(R(2)), rabs<V>(X2), dl[3])));
+    const V mag = rabs<V>(D0) + V(R(2) * Rr * Rr);
+    lhs = ABS ? rabs<V>(D0) : D0;
+    rhs = rfma<V>(V(reach_guard<R>()), B, V(reach_eps<R>()) * mag);
+#else
+    V D0, B;
+    sphere_reach_terms<R, V, true>(o, x, dl, D0, B);
+    lhs = rfma<V>(V(-reach_guard2<R>()), B, ABS ? rabs<V>(D0) : D0);
+    rhs = V(o.floor_);
+#endif
+}
+// … and a plane's distance d = x_t − p0 moves by at most δ_t; floor: 256 ulp of |x_t| + |p0| <= |d| + 2|p0|, folded the same way, Fp = 2 e |p0| (1 + 2e)
+template <class R, class V>
+RTGR_DEV void plane_reach(const DevObject<R>& o, const V x[4], const V dl[4], V& lhs, V& rhs) {
+    const V d = x[0] - V(o.p[0]);
+#if RTGR_REACH_TERMWISE_FLOOR
+    lhs = rabs<V>(d);
+    rhs = rfma<V>(V(reach_guard<R>()), dl[0], V(reach_eps<R>()) * (rabs<V>(x[0]) + V(rabs<R>(o.p[0]))));
+#else
+    lhs = rfma<V>(V(-reach_guard2<R>()), dl[0], rabs<V>(d));
+    rhs = V(o.floor_);
+#endif
 }
 // … and of any object, as an interval: its distance stays within [lower, upper] over the step (guards: select_objects, rtgr_resolve.hpp)
 template <class R>
@@ -341,9 +387,10 @@ RTGR_DEV void distance_bounds(const DevObject<R>& ob, const R x[4], const R dl[4
     const R eps = sizeof(R) == 8 ? R(2.220446049250313e-16) : R(1.1920929e-7);
     const R guard = R(1) + R(1e-6);
     R d0, B, mag;
-    if (ob.kind == RTGR_SPHERE) {
+    if (ob.kind == RTGR_SPHERE) {   // (the interval keeps its term-by-term floor: it is formed once per event, not once per step)
         R D0;
-        sphere_reach<R>(ob, x, dl, D0, B, mag);
+        sphere_reach_terms<R, R>(ob, x, dl, D0, B);
+        mag = rabs(D0) + R(-2) * ob.nR2;
         d0 = ob.p[8] < R(0) ? -D0 : D0;
     } else if (ob.kind == RTGR_PLANE) {
         d0 = x[0] - ob.p[0];

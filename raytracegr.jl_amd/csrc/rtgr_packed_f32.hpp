@@ -260,13 +260,9 @@ RTGR_DEV void integrate2_body(const IntegrateArgs<float>& A) {
             for_each_object<float>(A.sc, [&](const DevObject<float>& ob, uint32_t) {
                 V2 lhs, rhs;
                 if (ob.kind == RTGR_PLANE) {
-                    lhs = rabs<V2>(x[0] - V2(ob.p[0]));
-                    rhs = rfma<V2>(V2(guard), dl[0], V2(256.0f * eps) * (rabs<V2>(x[0]) + V2(__builtin_fabsf(ob.p[0]))));
+                    plane_reach<float>(ob, x, dl, lhs, rhs);
                 } else if (ob.kind == RTGR_SPHERE) {
-                    V2 D0, B, mag;
-                    sphere_reach<float>(ob, x, dl, D0, B, mag);
-                    lhs = rabs<V2>(D0);
-                    rhs = rfma<V2>(V2(guard), B, V2(256.0f * eps) * mag);
+                    sphere_reach<float, true>(ob, x, dl, lhs, rhs);
                 } else {
                     V2 px = x[1], py = x[2];
                     asm volatile("" : "+v"(px), "+v"(py));  // keep the disk's root inside this branch

@@ -32,6 +32,19 @@ template <> struct IsF64<double> { static constexpr bool v = true; };
 template <class R> RTGR_DEV R rfma(R a, R b, R c);
 template <> RTGR_DEV double rfma<double>(double a, double b, double c) { return __builtin_fma(a, b, c); }
 template <> RTGR_DEV float rfma<float>(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// a·b + s with a WAVE-UNIFORM addend read straight from its SGPRs (v_fma's third source).  Left to itself the compiler opens an FMA chain
+// on a scalar value with v_fmac, whose accumulator is a VGPR: a v_mov pair per chain to put the scalar there first.
+template <class V, class R> RTGR_DEV V rfma_sacc(V a, V b, R s) { return rfma<V>(a, b, V(s)); }   // (any other type: the plain fma)
+template <> RTGR_DEV double rfma_sacc<double, double>(double a, double b, double s) {
+    double r;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(s));
+    return r;
+}
+template <> RTGR_DEV float rfma_sacc<float, float>(float a, float b, float s) {
+    float r;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(s));
+    return r;
+}
 template <class R> RTGR_DEV R rsqrt_(R x);
 template <> RTGR_DEV double rsqrt_<double>(double x) { return __builtin_sqrt(x); }
 template <> RTGR_DEV float rsqrt_<float>(float x) { return __builtin_sqrtf(x); }
@@ -261,6 +274,13 @@ RTGR_DEV float uniform_(float v) {
 // one-instruction f32 max / min / clamp (fmaxf / fminf spend a second v_max x, x on canonicalising each computed operand)
 RTGR_DEV float fmax1(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 RTGR_DEV float fmin1(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// … with a WAVE-UNIFORM first operand (a kernel argument, a uniform_() value) read straight from its SGPRs — the VOP3 encoding takes one
+// scalar source —, and with a compile-time constant as the VOP2 literal: the "v"-only forms above make the compiler copy such an
+// operand into a VGPR first, a v_mov of its own in every step.  (Used for dtmax and the error estimate's floor.  lq_init keeps the
+// "v" form: its literal form, next to these two, cost the Float64 FAR kernel a third spill slot — profiles/r08/README.md.)
+RTGR_DEV double rmin_su(double s, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "s"(s), "v"(b)); return r; }
+RTGR_DEV float rmin_su(float s, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "s"(s), "v"(b)); return r; }
+template <uint32_t BITS> RTGR_DEV float fmax1_lit(float a) { float r; asm("v_max_f32_e32 %0, %2, %1" : "=v"(r) : "v"(a), "n"(BITS)); return r; }
 RTGR_DEV float fclamp1(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }  // v_med3_f32
 RTGR_DEV float flog2(float x) { return __builtin_amdgcn_logf(x); }   // v_log_f32
 RTGR_DEV float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }  // v_exp_f32

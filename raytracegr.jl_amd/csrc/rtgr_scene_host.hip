@@ -30,6 +30,31 @@ void scene_variant(const rtgr_scene* s, uint32_t* metric, bool* spin) {
     *spin = kind == RTGR_MINKOWSKI ? false : (generic ? true : s->a != 0.0);
 }
 
+// What the reach test of every step would otherwise form again from an object's (wave-uniform) parameters: DevObject::nR2 and ::floor_
+// (rtgr_args.hpp), from the object AS THE KERNELS SEE IT (the scalar type's values).  THE one place that computes them — every device
+// object passes through here: the caller's list (convert_object) and the bounding spheres of its groups (bounding_sphere).
+//   nR2    = −R²: it opens the FMA chain of every sphere distance, the scan's included, so it must be the value the kernels' own −R·R
+//            has: R·R rounded to nearest in R (the product of two R values is exact in double for Float32, and is the same double
+//            multiplication for Float64).
+//   floor_ = 2 e R² (1 + 2e) for a sphere, 2 e |p0| (1 + 2e) for a plane (e = reach_eps<R>()), evaluated in double and rounded UP into R
+//            — two ulp above the double value, which covers the roundings of the evaluation itself.  What the reach test needs of it is
+//            "no smaller than", not tightness.
+template <class R>
+static void object_constants(DevObject<R>& d) {
+    d.nR2 = R(0);
+    d.floor_ = R(0);
+    if (d.kind != RTGR_SPHERE && d.kind != RTGR_PLANE) return;
+    const double e = (double)reach_eps<R>();
+    const double r = (double)d.p[8];
+    if (d.kind == RTGR_SPHERE) d.nR2 = (R)(-(r * r));
+    const double scale = d.kind == RTGR_SPHERE ? r * r : std::fabs((double)d.p[0]);
+    double f = 2.0 * e * scale * (1.0 + 2.0 * e);
+    f = std::nextafter(std::nextafter(f, HUGE_VAL), HUGE_VAL);
+    R fr = (R)f;
+    if ((double)fr < f) fr = std::nextafter(fr, std::numeric_limits<R>::infinity());
+    d.floor_ = fr;   // (NaN parameters give a NaN floor: the test then never says "out of reach", as before)
+}
+
 // one object of the caller's list -> its device form (the scalar type's values; a disk's sign thresholds)
 template <class R>
 static int convert_object(const rtgr_object& in, DevObject<R>& d) {
@@ -42,6 +67,7 @@ static int convert_object(const rtgr_object& in, DevObject<R>& d) {
         disk_sqrt_band<R>(d.p[1], d.p[3], d.p[4]);
         disk_sqrt_band<R>(d.p[2], d.p[5], d.p[6]);
     }
+    object_constants<R>(d);
     return RTGR_OK;
 }
 
@@ -149,6 +175,7 @@ static void bounding_sphere(const DevObject<R>* t, const SphereGroup& g, DevObje
     R r = (R)rad;
     if ((double)r < rad) r = std::nextafter(r, std::numeric_limits<R>::infinity());
     out.p[8] = r;
+    object_constants<R>(out);
 }
 // … and a run of groups' bounding sphere: over ALL the members of its groups (they are neighbours in the device list too)
 template <class R>
@@ -285,6 +312,26 @@ template void convert_camera<double>(const rtgr_camera*, DevCamera<double>&);
 template void convert_camera<float>(const rtgr_camera*, DevCamera<float>&);
 
 }  // namespace rtgr
+
+// A test hook, not part of include/rtgr.h (tests/test_reach_floor.py; host code only — runs without a GPU): the reach test's constants as
+// the kernels of the scalar type get them.  Per object, through convert_object: rows[2k] = DevObject::nR2, rows[2k + 1] = ::floor_ (a
+// bounding sphere is a sphere of the scalar type's centre and radius: the same function); consts[0..2] = reach_eps, reach_guard,
+// reach_guard2 of that type.  Returns 0, or the error of a bad object.
+extern "C" int rtgr_testhook_reach_constants(const rtgr_object* objs, uint32_t n, int is_f32, double* rows, double* consts) {
+    using namespace rtgr;
+    auto fill = [&](auto zero) -> int {
+        typedef decltype(zero) R;
+        consts[0] = (double)reach_eps<R>(); consts[1] = (double)reach_guard<R>(); consts[2] = (double)reach_guard2<R>();
+        for (uint32_t k = 0; k < n; k++) {
+            DevObject<R> d;
+            if (int rc = convert_object<R>(objs[k], d)) return rc;
+            rows[2 * k] = (double)d.nR2;
+            rows[2 * k + 1] = (double)d.floor_;
+        }
+        return RTGR_OK;
+    };
+    return is_f32 ? fill(0.0f) : fill(0.0);
+}
 
 // A test hook, not part of include/rtgr.h (tests/test_host_logic.py; host code only — runs without a GPU): how convert_scene lays a
 // list's SPHERES out — `order` (n entries: indices into objs, loose spheres first, then the groups' members), the number of loose
