@@ -1092,6 +1092,117 @@ int rtgr_trace_orders_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr
                           const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, float* rgb, const rtgr_order_planes* planes /* may be NULL */,
                           rtgr_counters* ctr);
 
+/* ---- volume emission: radiative transfer through a hot flow along each ray ------------------------------------------------------------
+ * AN EXTENSION.  Every other emitter of the library is a surface: a ray carries no radiation until its first event.  Here a rotating,
+ * geometrically thick, optically thin (or grey) flow fills the space around the hole and the intensity is ACCUMULATED along the ray: the
+ * pictures whose ring is emission gathered by rays that wind round the photon orbit.  The trace is untouched; one more kernel runs behind
+ * it and integrates the transfer equations along each ray's own geodesic, as far as the trace followed that ray.
+ *
+ * The model (csrc/rtgr_transfer.hpp: ONE device function; everything in the entry point's scalar type; none of its own operations is
+ * fused).  The gas is axisymmetric and rotates on cylinders at the equatorial circular-orbit rate, exactly as the disk of "disk
+ * emission" does.  At a point x = (t, x, y, z) of a ray with tangent k, started at x_0 with tangent k_0:
+ *     rho = hypot(x, y),   r = sqrt(x^2 + y^2 + z^2)                                 (coordinate terms)
+ *     density   n = (r / r0)^(-alpha) exp(-z^2 / (2 H^2 rho^2));   a non-finite n counts as 0
+ *     flow      RTGR_EMIT_KEPLER: Omega = the orbital rate of "disk emission" at (t, x, y, 0), root `orbit` = +1 / -1 — the same device
+ *               function, so at z = 0 the flow's rate is the disk's bit for bit;   RTGR_EMIT_RIGID: Omega = orbit
+ *     emitter   xi = (1, -Omega y, Omega x, 0),   n2 = g(x)(xi, xi),   u_f = xi / sqrt(-n2)
+ *               the point is VALID iff the orbit exists (B^2 - A C >= 0, C != 0), Omega and n2 are finite and n2 < 0
+ *     w = g(x)(k, u_f),   kappa0 = g(x_0)(k_0, u_obs),   gfac = kappa0 / w
+ *               u_obs: the e_0 of the observer's frame (rtgr_trace_transfer_*; the hooks with `obs`), or, obs == NULL, the static
+ *               observer at x_0 as in rtgr_eval_disk_emission_*
+ *   The two transfer equations run along the traced direction, from the camera outwards.  I is the observed specific intensity at the
+ *   channel's own frequency, the emissivity j_nu ~ n nu^(-s), the absorption grey:
+ *     dtau/dlambda = kappa n w
+ *     dI/dlambda   = j0 n w gfac^(3+s) exp(-tau)
+ *   Both are 0 where the point is invalid or gfac is not > 0: there is no gas inside the photon orbit's cylinder.  The EMISSION goes to
+ *   0 continuously there (w gfac^(3+s) = kappa0 gfac^(2+s), gfac -> 0), with a kink: ~ (rho - rho_ph)^((2+s)/2).
+ *   A LIMITATION OF THE MODEL, kappa > 0.  The ABSORPTION does not: n2 -> 0- at the cylinder, so w ~ 1 / sqrt(-n2) and dtau/dlambda =
+ *   kappa n w is UNBOUNDED there (integrable, but no adaptive step gets across it at the solver's tolerance).  A Float64 ray that
+ *   crosses the cylinder where the density is not negligible ends with a step-size underflow: status 3, I = tau = NaN, and — it was
+ *   integrated, so the picture rule applies — rgb = NaN in all three channels.  In the a = 0.9 example at inclination 60 degrees that
+ *   is every pixel of the shadow and its rim, 12 % of the frame.  Rays that enter the cylinder far above the plane (n ~ 0), every ray
+ *   with kappa = 0, and Float32 (whose coarser steps get across) are not affected.  A dtau that stays bounded at the cylinder would
+ *   remove this; that is a change of the model, not made here.
+ *   The picture.  rgb_c = rgb_c(traced, shaded, emitted) exp(-tau_end) + gain weight_c I_end.  Three channels of a power law with grey
+ *   absorption differ by a constant only, so ONE I and ONE tau are integrated per ray.
+ *
+ * The integration (transfer_kernel, one lane per ray).  y = (x, k, tau, I), 10 components, from the ray's own start state over
+ * [lambda0, lambda_end], lambda_end what the trace reported for that ray.  Tsit5 with the trace's coefficients, the geodesic half the
+ * closed right-hand side of the scene's metric (also under RTGR_METRIC_GENERIC); the initial step from the geodesic part, the PI
+ * controller of the trace with the rms norm over all 10 components and the solver's abstol / reltol — the step adapts to the emission;
+ * the last step is clipped to lambda_end exactly.  It ends earlier
+ *   - at the first ACCEPTED step whose end has r < r_stop.  This is not a root-find: CHOOSE r_stop INSIDE THE DARK CYLINDER, where it
+ *     cannot change I (it spares a captured ray the steps towards the horizon); 0 for RTGR_MINKOWSKI;
+ *   - after opt->max_steps attempts; on a non-finite error estimate; on a step-size underflow.
+ * Per-ray status byte: 0 = reached lambda_end, 1 = r_stop, 2 = step cap, 3 = not integrated or not finite (I = tau = NaN).  Status 3
+ * has two sources.  Rays the trace ended as RTGR_RAY_NAN, or whose start state or lambda_end is not finite, are NOT INTEGRATED: tsteps
+ * = 0, and their rgb is left as traced.  Rays whose integration ended not finite (a non-finite error estimate, a step-size underflow
+ * — the kappa > 0 limitation above) WERE integrated: tsteps > 0, and their rgb is NaN.
+ *
+ * rtgr_trace_transfer_device_* / rtgr_trace_transfer_* (host pointers): the arguments of rtgr_trace_observer_*, plus `flow`, four
+ * optional planes — d_I, d_tau (n scalars), d_tstatus (n bytes), d_tsteps (n x uint32: step attempts) — and tctr, the counters of the
+ * transfer pass alone (rays integrated, accepted, rejected, rhs_evals, events = rays ended at r_stop, not_finished = status >= 2); ctr
+ * stays the trace's.  Every per-ray output of `out`, ctr and d_g are rtgr_trace_observer_*'s bit for bit.  Per batch: the observer
+ * trace's work, then the transfer kernel over the batch, reading the start states where the batch left them; lambda_end and the status
+ * bytes are borrowed from the stream's frame scratch when `out` does not ask for them (grow-only).  They only enqueue, with one
+ * synchronisation when ctr or tctr is given; capturable with ctr == tctr == NULL once workspace and scratch exist.  The result does
+ * not depend on max_batch_rays or on the stream.
+ * rtgr_eval_transfer_* (blocking, host pointers): the same kernel body over n listed rays (s0, lambda_end): I, tau, tstatus, tsteps
+ * and s_end (n x 8: where the integration ended).  Any output may be NULL.  It predicts a pixel of the frame to the bit.
+ * rtgr_eval_flow_* (blocking, host pointers): the pointwise model at n points s = (x, k) of rays started at s0: dens, omega,
+ * u_f (n x 4), gfac, dtau and dI0 = dI/dlambda at tau = 0.  Any output may be NULL.  An invalid point gives NaN in omega, u_f and
+ * gfac and 0 in the two derivatives.
+ *   RTGR_ERR_BAD_ARG (with a message that names the field; the outputs are left untouched): a null flow; an unknown emitter;
+ * flags != 0; KEPLER with orbit other than +1 / -1; j0 < 0, kappa < 0, r0 <= 0, H <= 0, r_stop < 0, or any parameter NaN or infinite;
+ * RTGR_USER metrics; RTGR_GRID and 4-D grids; everything rtgr_trace_observer_* refuses.
+ *   Out of scope: grids and user metrics; plunging gas inside the innermost stable orbit (the orbits used there are the unstable
+ * circular ones); frequency-dependent absorption and thermal synchrotron emissivities; polarized transfer; anti-aliasing, the sharded
+ * and frames-in-flight entries; orders >= 1 of "higher-order disk images" (the flow is integrated along leg 0 only); a per-wave table
+ * of Omega(rho) or a persistent refilling kernel, the obvious next steps if the transfer pass is to cost less. */
+typedef struct rtgr_flow {
+    uint32_t emitter;     /* rtgr_emitter */
+    uint32_t flags;       /* 0 */
+    double orbit;         /* KEPLER: +1 / -1; RIGID: Omega */
+    double j0, kappa;     /* >= 0; kappa = 0: optically thin */
+    double r0, alpha, H, s;   /* r0 > 0, H > 0, finite alpha, s */
+    double r_stop;        /* >= 0 */
+    double gain, weight[3];
+} rtgr_flow;  /* 104 bytes: emitter 0, flags 4, orbit 8, j0 16, kappa 24, r0 32, alpha 40, H 48, s 56, r_stop 64, gain 72, weight 80 */
+int rtgr_trace_transfer_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                   uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit /* may be NULL */,
+                                   const rtgr_flow* flow, double* d_rgb, const rtgr_ray_outputs* out, double* d_g /* n, NULL without emit */,
+                                   double* d_I /* n, may be NULL */, double* d_tau /* n, may be NULL */, uint8_t* d_tstatus /* n, may be NULL */,
+                                   uint32_t* d_tsteps /* n, may be NULL */, rtgr_counters* ctr, rtgr_counters* tctr, void* stream);
+int rtgr_trace_transfer_device_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                                   uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit /* may be NULL */,
+                                   const rtgr_flow* flow, float* d_rgb, const rtgr_ray_outputs* out, float* d_g /* n, NULL without emit */,
+                                   float* d_I /* n, may be NULL */, float* d_tau /* n, may be NULL */, uint8_t* d_tstatus /* n, may be NULL */,
+                                   uint32_t* d_tsteps /* n, may be NULL */, rtgr_counters* ctr, rtgr_counters* tctr, void* stream);
+int rtgr_trace_transfer_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                            uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit /* may be NULL */,
+                            const rtgr_flow* flow, double* rgb, const rtgr_ray_outputs* out, double* g /* n, NULL without emit */,
+                            double* I /* n, may be NULL */, double* tau /* n, may be NULL */, uint8_t* tstatus /* n, may be NULL */,
+                            uint32_t* tsteps /* n, may be NULL */, rtgr_counters* ctr, rtgr_counters* tctr);
+int rtgr_trace_transfer_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni,
+                            uint64_t nj, const rtgr_shade* shade /* may be NULL */, const rtgr_disk_emission* emit /* may be NULL */,
+                            const rtgr_flow* flow, float* rgb, const rtgr_ray_outputs* out, float* g /* n, NULL without emit */,
+                            float* I /* n, may be NULL */, float* tau /* n, may be NULL */, uint8_t* tstatus /* n, may be NULL */,
+                            uint32_t* tsteps /* n, may be NULL */, rtgr_counters* ctr, rtgr_counters* tctr);
+int rtgr_eval_transfer_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_flow* flow,
+                           const rtgr_observer* obs /* may be NULL: static observer */, const double* s0 /* n x 8 */,
+                           const double* lambda_end /* n */, uint64_t n, double* I /* n */, double* tau /* n */, double* s_end /* n x 8 */,
+                           uint8_t* tstatus /* n */, uint32_t* tsteps /* n */);
+int rtgr_eval_transfer_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_flow* flow,
+                           const rtgr_observer* obs /* may be NULL: static observer */, const float* s0 /* n x 8 */,
+                           const float* lambda_end /* n */, uint64_t n, float* I /* n */, float* tau /* n */, float* s_end /* n x 8 */,
+                           uint8_t* tstatus /* n */, uint32_t* tsteps /* n */);
+int rtgr_eval_flow_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_flow* flow, const rtgr_observer* obs /* may be NULL */,
+                       const double* s0 /* n x 8 */, const double* s /* n x 8: a point and tangent */, uint64_t n, double* dens /* n */,
+                       double* omega /* n */, double* u_f /* n x 4 */, double* gfac /* n */, double* dtau /* n */, double* dI0 /* n */);
+int rtgr_eval_flow_f32(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_flow* flow, const rtgr_observer* obs /* may be NULL */,
+                       const float* s0 /* n x 8 */, const float* s /* n x 8: a point and tangent */, uint64_t n, float* dens /* n */,
+                       float* omega /* n */, float* u_f /* n x 4 */, float* gfac /* n */, float* dtau /* n */, float* dI0 /* n */);
+
 /* ---- camera: make_canvas (src/RayTraceGR.jl:457-478) on the device ------------------------------------------
  * Writes n x 8 ray states (pos, null past-directed 4-velocity) for rows [j0, j1).  Device / host variants. */
 int rtgr_make_canvas_device_f64(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_camera* cam, uint64_t ni,

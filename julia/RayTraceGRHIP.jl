@@ -37,6 +37,7 @@
 #   RtgrPolarization 64   kind 0, flags 4, deg0 8, deg1 16, field 24, reserved 48
 #   RtgrDiskOrders 32   max_order 0, flags 4, margin 8, transmission 16, pad 24
 #   RtgrOrderPlanes 48   count 0, hit32 8, state_end 16, g 24, rgb_order 32, state0 40
+#   RtgrFlow        104   emitter 0, flags 4, orbit 8, j0 16, kappa 24, r0 32, alpha 40, H 48, s 56, r_stop 64, gain 72, weight 80
 #   Pixel{Float64}   88   pos 0, normal 32, rgb 64         (the reference's own type, src/RayTraceGR.jl:446-450)
 #   Pixel{Float32}   44   pos 0, normal 16, rgb 32
 #
@@ -207,6 +208,20 @@ struct RtgrOrderPlanes         # the optional outputs of rtgr_trace_orders_*; C_
     g::Ptr{Cvoid}               # (N + 1) x n
     rgb_order::Ptr{Cvoid}       # (N + 1) x 3 x n
     state0::Ptr{Cvoid}          # n x 8
+end
+struct RtgrFlow                # a hot, rotating flow that emits and absorbs along each ray (rtgr_trace_transfer_f64 / _f32)
+    emitter::UInt32             # RTGR_EMIT_KEPLER / RTGR_EMIT_RIGID
+    flags::UInt32               # 0
+    orbit::Float64              # KEPLER: +1 / -1; RIGID: Omega
+    j0::Float64                 # emissivity scale, >= 0
+    kappa::Float64              # grey absorption, >= 0 (0: optically thin)
+    r0::Float64                 # density (r / r0)^(-alpha) exp(-z^2 / (2 H^2 rho^2)); r0 > 0
+    alpha::Float64
+    H::Float64                  # > 0
+    s::Float64                  # j_nu ~ nu^(-s)
+    r_stop::Float64             # >= 0: a ray's integration ends once it is inside this radius
+    gain::Float64
+    weight::NTuple{3,Float64}   # rgb_c = rgb_c exp(-tau) + gain weight_c I
 end
 struct RtgrRayOutputs          # optional per-ray outputs; C_NULL = not wanted
     state_end::Ptr{Cvoid}
@@ -1260,6 +1275,112 @@ function eval_walker_penrose(metric, s::Matrix{T}, f::Matrix{T}; ctx = nothing) 
         end
     end
     kappa
+end
+
+"""
+    Flow(j0; kappa = 0, r0 = 1, alpha = 1, H = 0.3, s = 0, r_stop = 0, orbit = 1, emitter = RTGR_EMIT_KEPLER, gain = 1, weight = (1, 1, 1)) -> RtgrFlow
+
+A hot, rotating flow that emits and absorbs along each ray (include/rtgr.h "volume emission").  Density `(r / r0)^(-alpha)
+exp(-z^2 / (2 H^2 rho^2))`; `emitter = RTGR_EMIT_KEPLER`: gas on cylinders at the circular-orbit rate of the scene's own metric, `orbit`
+= +1 or -1; `RTGR_EMIT_RIGID`: Omega = `orbit`.  Emissivity `j0 n nu^(-s)`, grey absorption `kappa n`.  Choose `r_stop` between the
+horizon's coordinate radius and the photon orbit's cylinder (0 in flat space).
+"""
+function Flow(j0::Real; kappa::Real = 0, r0::Real = 1, alpha::Real = 1, H::Real = 0.3, s::Real = 0, r_stop::Real = 0, orbit::Real = 1,
+              emitter::UInt32 = RTGR_EMIT_KEPLER, gain::Real = 1, weight = (1.0, 1.0, 1.0))
+    RtgrFlow(emitter, UInt32(0), Float64(orbit), Float64(j0), Float64(kappa), Float64(r0), Float64(alpha), Float64(H), Float64(s), Float64(r_stop),
+             Float64(gain), (Float64(weight[1]), Float64(weight[2]), Float64(weight[3])))
+end
+
+# the solver record of T with lambda1 and / or max_steps replaced (nothing: the default)
+function solver_with(::Type{T}, lambda1, max_steps) where {T}
+    opt = solver_of(T)
+    o = opt[]
+    opt[] = RtgrSolver(o.reltol, o.abstol, o.lambda0, lambda1 === nothing ? o.lambda1 : Float64(lambda1), o.hit_threshold, o.miss_rgb,
+                       max_steps === nothing ? o.max_steps : UInt32(max_steps), o.interp_points)
+    opt
+end
+
+"""
+    trace_rays_transfer(metric, objs, observer, ni, nj, flow; emission = nothing, lambda1 = nothing, max_steps = nothing, T = Float64, ctx = nothing)
+        -> ((R, G, B), I, tau, tstatus, tsteps)
+
+A frame with VOLUME EMISSION (`rtgr_trace_transfer_f64/_f32`) — an extension: the frame of `trace_rays_observer` (with `emission`, an
+emitting disk, if given), then the transfer equations of `flow` integrated along every ray as far as the trace followed it:
+`rgb = rgb exp(-tau) + gain weight I`.  `I`, `tau` are `ni x nj`; `tstatus` (0 reached the ray's end, 1 r_stop, 2 step cap, 3 not
+integrated or not finite: NaN) and `tsteps` (step attempts) likewise.  The observer's frame is asked for first: an invalid frame or a
+refused record is an error.
+"""
+function trace_rays_transfer(metric, objs, observer::RtgrObserver, ni::Integer, nj::Integer, flow::RtgrFlow; emission = nothing, lambda1 = nothing,
+                             max_steps = nothing, T::Type = Float64, ctx = nothing)
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("trace_rays_transfer has no CPU counterpart in the reference: ", why)
+    opt = solver_with(T, lambda1, max_steps)
+    obs = Ref(observer)
+    fl = Ref(flow)
+    emit = emission === nothing ? nothing : Ref(emission::RtgrDiskEmission)
+    observer_frame(scene, obs; T = T, ctx = ctx)
+    rgb = Array{T}(undef, ni, nj, 3)                # plane-major: rgb[:, :, c] is plane c
+    g = Array{T}(undef, ni, nj)
+    I = Array{T}(undef, ni, nj)
+    tau = Array{T}(undef, ni, nj)
+    tstatus = Array{UInt8}(undef, ni, nj)
+    tsteps = Array{UInt32}(undef, ni, nj)
+    ctr = Ref{RtgrCounters}()
+    tctr = Ref{RtgrCounters}()
+    GC.@preserve rgb g I tau tstatus tsteps emit begin
+        pe = emit === nothing ? Ptr{RtgrDiskEmission}(C_NULL) : Base.unsafe_convert(Ptr{RtgrDiskEmission}, emit)
+        pg = emit === nothing ? Ptr{T}(C_NULL) : pointer(g)
+        if T === Float64
+            check(ccall((:rtgr_trace_transfer_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission},
+                         Ptr{RtgrFlow}, Ptr{Float64}, Ptr{RtgrRayOutputs}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{UInt32},
+                         Ptr{RtgrCounters}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, pe, fl, pointer(rgb), C_NULL, pg, pointer(I), pointer(tau),
+                        pointer(tstatus), pointer(tsteps), ctr, tctr))
+        else
+            check(ccall((:rtgr_trace_transfer_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrObserver}, UInt64, UInt64, Ptr{RtgrShade}, Ptr{RtgrDiskEmission},
+                         Ptr{RtgrFlow}, Ptr{Float32}, Ptr{RtgrRayOutputs}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}, Ptr{UInt32},
+                         Ptr{RtgrCounters}, Ptr{RtgrCounters}),
+                        handle(ctx), scene, opt, obs, ni, nj, C_NULL, pe, fl, pointer(rgb), C_NULL, pg, pointer(I), pointer(tau),
+                        pointer(tstatus), pointer(tsteps), ctr, tctr))
+        end
+    end
+    (rgb[:, :, 1], rgb[:, :, 2], rgb[:, :, 3]), I, tau, tstatus, tsteps
+end
+
+"""
+    eval_transfer(metric, objs, flow, s0, lambda_end; lambda1 = nothing, max_steps = nothing, ctx = nothing) -> (I, tau, s_end, tstatus, tsteps)
+
+The transfer kernel itself over `n` listed rays (`rtgr_eval_transfer_f64/_f32`, blocking): `s0` (`8 x n`) their start states,
+`lambda_end` (`n`) how far each is integrated; u_obs is the static observer at each ray's start.  `s_end` is `8 x n`.
+"""
+function eval_transfer(metric, objs, flow::RtgrFlow, s0::Matrix{T}, lambda_end::Vector{T}; lambda1 = nothing, max_steps = nothing,
+                       ctx = nothing) where {T<:Union{Float64,Float32}}
+    scene, why = scene_of(metric, objs, ctx)
+    scene === nothing && error("eval_transfer: ", why)
+    size(s0, 1) == 8 && size(s0, 2) == length(lambda_end) || error("eval_transfer: s0 must be 8 x n and lambda_end of length n")
+    n = size(s0, 2)
+    opt = solver_with(T, lambda1, max_steps)
+    fl = Ref(flow)
+    I = Array{T}(undef, n); tau = Array{T}(undef, n); s_end = Array{T}(undef, 8, n)
+    tstatus = Array{UInt8}(undef, n); tsteps = Array{UInt32}(undef, n)
+    GC.@preserve s0 lambda_end I tau s_end tstatus tsteps begin
+        if T === Float64
+            check(ccall((:rtgr_eval_transfer_f64, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrFlow}, Ptr{RtgrObserver}, Ptr{Float64}, Ptr{Float64}, UInt64, Ptr{Float64},
+                         Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{UInt32}),
+                        handle(ctx), scene, opt, fl, C_NULL, pointer(s0), pointer(lambda_end), n, pointer(I), pointer(tau), pointer(s_end),
+                        pointer(tstatus), pointer(tsteps)))
+        else
+            check(ccall((:rtgr_eval_transfer_f32, librtgr), Cint,
+                        (Ctx, Ptr{RtgrScene}, Ptr{RtgrSolver}, Ptr{RtgrFlow}, Ptr{RtgrObserver}, Ptr{Float32}, Ptr{Float32}, UInt64, Ptr{Float32},
+                         Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}, Ptr{UInt32}),
+                        handle(ctx), scene, opt, fl, C_NULL, pointer(s0), pointer(lambda_end), n, pointer(I), pointer(tau), pointer(s_end),
+                        pointer(tstatus), pointer(tsteps)))
+        end
+    end
+    I, tau, s_end, tstatus, tsteps
 end
 
 """

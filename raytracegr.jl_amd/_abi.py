@@ -169,6 +169,13 @@ class rtgr_order_planes(C.Structure):
                 ("state0", C.c_void_p)]
 
 
+class rtgr_flow(C.Structure):
+    """a hot, rotating flow that emits and absorbs along each ray (rtgr_trace_transfer_*): 104 bytes"""
+    _fields_ = [("emitter", C.c_uint32), ("flags", C.c_uint32), ("orbit", C.c_double), ("j0", C.c_double), ("kappa", C.c_double),
+                ("r0", C.c_double), ("alpha", C.c_double), ("H", C.c_double), ("s", C.c_double), ("r_stop", C.c_double), ("gain", C.c_double),
+                ("weight", C.c_double * 3)]
+
+
 class rtgr_ray_outputs(C.Structure):
     _fields_ = [("state_end", C.c_void_p), ("lambda_end", C.c_void_p), ("status", C.c_void_p),
                 ("hit", C.c_void_p), ("n_accept", C.c_void_p), ("n_reject", C.c_void_p), ("redshift", C.c_void_p),
@@ -207,6 +214,8 @@ EXPORTS = [
     "rtgr_trace_polarized_f64", "rtgr_trace_polarized_f32", "rtgr_eval_polarization_f64", "rtgr_eval_polarization_f32",
     "rtgr_eval_walker_penrose_f64", "rtgr_eval_walker_penrose_f32",
     "rtgr_trace_orders_device_f64", "rtgr_trace_orders_device_f32", "rtgr_trace_orders_f64", "rtgr_trace_orders_f32",
+    "rtgr_trace_transfer_device_f64", "rtgr_trace_transfer_device_f32", "rtgr_trace_transfer_f64", "rtgr_trace_transfer_f32",
+    "rtgr_eval_transfer_f64", "rtgr_eval_transfer_f32", "rtgr_eval_flow_f64", "rtgr_eval_flow_f32",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -330,6 +339,15 @@ def _declare(lib):
         getattr(lib, f"rtgr_eval_polarization_{suf}").argtypes = [
             ctx, P(rtgr_scene), P(rtgr_disk_emission), P(rtgr_polarization), P(rtgr_observer), vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]
         getattr(lib, f"rtgr_eval_walker_penrose_{suf}").argtypes = [ctx, P(rtgr_scene), vp, vp, u64, vp]
+        getattr(lib, f"rtgr_trace_transfer_device_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_flow), vp,
+            P(rtgr_ray_outputs), vp, vp, vp, vp, vp, P(rtgr_counters), P(rtgr_counters), vp]
+        getattr(lib, f"rtgr_trace_transfer_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_flow), vp,
+            P(rtgr_ray_outputs), vp, vp, vp, vp, vp, P(rtgr_counters), P(rtgr_counters)]
+        getattr(lib, f"rtgr_eval_transfer_{suf}").argtypes = [
+            ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_flow), P(rtgr_observer), vp, vp, u64, vp, vp, vp, vp, vp]
+        getattr(lib, f"rtgr_eval_flow_{suf}").argtypes = [ctx, P(rtgr_scene), P(rtgr_flow), P(rtgr_observer), vp, vp, u64, vp, vp, vp, vp, vp, vp]
         getattr(lib, f"rtgr_trace_orders_device_{suf}").argtypes = [
             ctx, P(rtgr_scene), P(rtgr_solver), P(rtgr_observer), vp, u64, u64, P(rtgr_shade), P(rtgr_disk_emission), P(rtgr_disk_orders), vp,
             P(rtgr_order_planes), P(rtgr_counters), vp]

@@ -987,6 +987,93 @@ def geodesic(s, metric, lam=0.0, path=0, dtype=np.float64):
     return ds[0] if ds.shape[0] == 1 else ds
 
 
+# ---- volume emission (include/rtgr.h "volume emission") -----------------------------------------------------------------------------------
+def Flow(j0, kappa=0.0, r0=1.0, alpha=1.0, H=0.3, s=0.0, r_stop=0.0, orbit=+1, emitter="kepler", gain=1.0, weight=(1.0, 1.0, 1.0)):
+    """A hot, rotating flow that emits and absorbs along each ray -> rtgr_flow.  Density (r / r0)^(-alpha) exp(-z² / (2 H² rho²));
+    emitter "kepler": gas on cylinders at the circular-orbit rate of the scene's own metric, orbit = +1 or -1; "rigid": Omega = orbit.
+    Emissivity j0 n nu^(-s), grey absorption kappa n (0: optically thin).  r_stop: the integration of a ray ends once it is inside this
+    radius — choose it inside the photon orbit's cylinder, where there is no gas (0 in flat space).  The picture gets gain weight_c I."""
+    kinds = {"kepler": _abi.EMIT_KEPLER, "rigid": _abi.EMIT_RIGID}
+    if emitter not in kinds:
+        raise ValueError(f"Flow: emitter must be 'kepler' or 'rigid', got {emitter!r}")
+    w = [float(v) for v in weight]
+    if len(w) != 3:
+        raise ValueError("Flow: weight needs three channels (r, g, b)")
+    return _abi.rtgr_flow(emitter=kinds[emitter], flags=0, orbit=float(orbit), j0=float(j0), kappa=float(kappa), r0=float(r0), alpha=float(alpha),
+                          H=float(H), s=float(s), r_stop=float(r_stop), gain=float(gain), weight=(C.c_double * 3)(*w))
+
+
+def trace_transfer(metric, objs, observer, ni, nj, flow, emission=None, textures=None, r_escape=0.0, opt=None, dtype=np.float64, ctx=None,
+                   details=False):
+    """A frame with VOLUME EMISSION (rtgr_trace_transfer_f64 / _f32) — an extension: trace_observer's frame, then the transfer equations
+    of `flow` (a Flow) integrated along every ray as far as the trace followed it: rgb = rgb exp(-tau) + gain weight I.  Raises
+    ValueError for an observer with no valid frame.  -> trace_observer's dict + I, tau [ni*nj], tstatus [ni*nj] (0 reached the ray's
+    end, 1 r_stop, 2 step cap, 3 not integrated or not finite), tsteps [ni*nj] (step attempts), transfer_counters."""
+    lib = _lib()
+    _valid_observer(metric, objs, observer, dtype, ctx)
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    n = ni * nj
+    sh = make_shade(textures, r_escape) if textures else None
+    res = dict(rgb=np.zeros((3, n), dtype), I=np.zeros(n, dtype), tau=np.zeros(n, dtype), tstatus=np.zeros(n, np.uint8), tsteps=np.zeros(n, np.uint32))
+    if emission is not None:
+        res["g"] = np.zeros(n, dtype)
+    outs = _ray_details(res, n, dtype, sc.nobj) if details else None
+    ctr, tctr = rtgr_counters(), rtgr_counters()
+    fn = lib.rtgr_trace_transfer_f64 if dtype == np.float64 else lib.rtgr_trace_transfer_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), C.byref(observer), ni, nj, None if sh is None else C.byref(sh),
+                       None if emission is None else C.byref(emission), None if flow is None else C.byref(flow), res["rgb"].ctypes.data, outs,
+                       res["g"].ctypes.data if emission is not None else None, res["I"].ctypes.data, res["tau"].ctypes.data,
+                       res["tstatus"].ctypes.data, res["tsteps"].ctypes.data, C.byref(ctr), C.byref(tctr)))
+    res["counters"] = ctr.as_dict()
+    res["transfer_counters"] = tctr.as_dict()
+    return res
+
+
+def eval_transfer(metric, objs, flow, s0, lambda_end, observer=None, opt=None, dtype=np.float64, ctx=None):
+    """rtgr_eval_transfer_f64 / _f32: the transfer kernel itself over n listed rays — s0 [n, 8] their start states, lambda_end [n] how
+    far each is integrated.  observer (an Observer): u_obs is its 4-velocity, as in trace_transfer; None: the static observer at s0.
+    -> dict(I, tau [n], s_end [n, 8], tstatus [n], tsteps [n])."""
+    lib = _lib()
+    if observer is not None:
+        _valid_observer(metric, objs, observer, dtype, ctx)
+    sc = make_scene(metric, objs, ctx)
+    opt = opt or solver_defaults(dtype)
+    a = np.ascontiguousarray(s0, dtype=dtype).reshape(-1, 8)
+    le = np.ascontiguousarray(lambda_end, dtype=dtype).reshape(-1)
+    if a.shape[0] != le.shape[0]:
+        raise ValueError(f"eval_transfer: s0 and lambda_end must have the same length, got {a.shape[0]} and {le.shape[0]}")
+    n = a.shape[0]
+    res = dict(I=np.zeros(n, dtype), tau=np.zeros(n, dtype), s_end=np.zeros((n, 8), dtype), tstatus=np.zeros(n, np.uint8), tsteps=np.zeros(n, np.uint32))
+    fn = lib.rtgr_eval_transfer_f64 if dtype == np.float64 else lib.rtgr_eval_transfer_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), C.byref(opt), None if flow is None else C.byref(flow), None if observer is None else C.byref(observer),
+                       a.ctypes.data if n else None, le.ctypes.data if n else None, n, *[res[k].ctypes.data if n else None
+                                                                                       for k in ("I", "tau", "s_end", "tstatus", "tsteps")]))
+    return res
+
+
+def eval_flow(metric, objs, flow, s0, s, observer=None, dtype=np.float64, ctx=None):
+    """rtgr_eval_flow_f64 / _f32: the flow model at n points — s [n, 8] a point and the ray's tangent there, s0 [n, 8] the ray's start
+    state (for kappa0).  -> dict(dens, omega [n], u_f [n, 4], gfac, dtau, dI0 [n]); an invalid point gives NaN in omega, u_f and gfac
+    and 0 in the two derivatives."""
+    lib = _lib()
+    if observer is not None:
+        _valid_observer(metric, objs, observer, dtype, ctx)
+    sc = make_scene(metric, objs, ctx)
+    a = np.ascontiguousarray(s0, dtype=dtype).reshape(-1, 8)
+    p = np.ascontiguousarray(s, dtype=dtype).reshape(-1, 8)
+    if a.shape != p.shape:
+        raise ValueError(f"eval_flow: s0 and s must have the same shape, got {a.shape} and {p.shape}")
+    n = a.shape[0]
+    res = dict(dens=np.zeros(n, dtype), omega=np.zeros(n, dtype), u_f=np.zeros((n, 4), dtype), gfac=np.zeros(n, dtype), dtau=np.zeros(n, dtype),
+               dI0=np.zeros(n, dtype))
+    fn = lib.rtgr_eval_flow_f64 if dtype == np.float64 else lib.rtgr_eval_flow_f32
+    _abi.check(lib, fn(ctx, C.byref(sc), None if flow is None else C.byref(flow), None if observer is None else C.byref(observer),
+                       a.ctypes.data if n else None, p.ctypes.data if n else None, n, *[res[k].ctypes.data if n else None
+                                                                                      for k in ("dens", "omega", "u_f", "gfac", "dtau", "dI0")]))
+    return res
+
+
 # ---- example scenes (src/RayTraceGR.jl:542-612) -------------------------------------------------------------------
 outdir = "scenes"  # :540
 
@@ -1038,5 +1125,5 @@ def example2(ni=200, nj=200, save=True, ctx=None):
 
 __all__ = ["D", "Metric", "UserMetric", "GridMetric", "sample_metric", "UserObjects", "UserObject", "minkowski", "kerr_schild", "KerrSchild", "Object", "Plane", "Sphere", "Disk",
            "make_scene", "check_scene", "eval_objects", "solver_defaults", "make_camera", "Pixel", "pixel_dtype", "Canvas", "make_canvas",
-           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "HotSpot", "eval_hot_spot", "light_curve", "Spectrum", "eval_spectrum", "spectrum", "Polarization", "trace_polarized", "eval_polarization", "eval_walker_penrose", "DiskOrders", "trace_orders", "dmetric", "christoffel", "geodesic", "example1", "example2",
+           "trace_rays", "trace_ray", "trace_frames", "trace_aa", "Texture", "texture_load", "texture_unload", "eval_texture", "make_shade", "trace_shaded", "DiskEmission", "trace_emission", "eval_disk_emission", "Observer", "eval_observer", "make_observer_canvas", "trace_observer", "HotSpot", "eval_hot_spot", "light_curve", "Spectrum", "eval_spectrum", "spectrum", "Polarization", "trace_polarized", "eval_polarization", "eval_walker_penrose", "DiskOrders", "trace_orders", "Flow", "trace_transfer", "eval_transfer", "eval_flow", "dmetric", "christoffel", "geodesic", "example1", "example2",
            "example1_scene", "example2_scene"]

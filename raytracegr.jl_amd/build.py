@@ -3,8 +3,8 @@
     python raytracegr.jl_amd/build.py [--force] [--resource-usage] [--save-temps] [--via-listing] [-DNAME[=V] ...]
 
 The library is several translation units (csrc/tu_*.hip hold the kernels of one metric-variant group each,
-csrc/rtgr_misc.hip, rtgr_aa.hip, rtgr_shade.hip, rtgr_emit.hip, rtgr_observer.hip, rtgr_lightcurve.hip, rtgr_spectrum.hip, rtgr_polarize.hip and rtgr_orders.hip the small kernels — the light-curve and spectrum units instantiate the one reduction of csrc/rtgr_reduce.hpp; the host side is kernel-free: csrc/rtgr_context.hip, rtgr_tables.hip, rtgr_scene_host.hip, rtgr_host_pipeline.hip, rtgr_sharded.hip,
-rtgr_hooks.hip, rtgr_units.hip, rtgr_frame_host.hip, rtgr_aa_host.hip, rtgr_texture_host.hip, rtgr_emission_host.hip, rtgr_observer_host.hip, rtgr_reduce_host.hip, rtgr_lightcurve_host.hip, rtgr_spectrum_host.hip, rtgr_polarization_host.hip, rtgr_orders_host.hip and the extern "C" shims of csrc/rtgr_abi.hip — rtgr_internal.hpp says what is where); they are compiled in parallel
+csrc/rtgr_misc.hip, rtgr_aa.hip, rtgr_shade.hip, rtgr_emit.hip, rtgr_observer.hip, rtgr_lightcurve.hip, rtgr_spectrum.hip, rtgr_polarize.hip and rtgr_orders.hip the small kernels, csrc/tu_transfer_f64.hip and tu_transfer_f32.hip the transfer kernels of volume emission — the light-curve and spectrum units instantiate the one reduction of csrc/rtgr_reduce.hpp; the host side is kernel-free: csrc/rtgr_context.hip, rtgr_tables.hip, rtgr_scene_host.hip, rtgr_host_pipeline.hip, rtgr_sharded.hip,
+rtgr_hooks.hip, rtgr_units.hip, rtgr_frame_host.hip, rtgr_aa_host.hip, rtgr_texture_host.hip, rtgr_emission_host.hip, rtgr_observer_host.hip, rtgr_reduce_host.hip, rtgr_lightcurve_host.hip, rtgr_spectrum_host.hip, rtgr_polarization_host.hip, rtgr_orders_host.hip, rtgr_transfer_host.hip and the extern "C" shims of csrc/rtgr_abi.hip — rtgr_internal.hpp says what is where); they are compiled in parallel
 into raytracegr.jl_amd/build/obj/ and linked with `hipcc -shared`.
 
 After linking, the library AUDITS the kernels embedded in it for the EXEC-flip fault of ROCm 7.2's compiler (DESIGN.md §4.6;
@@ -25,8 +25,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 UNITS = ["tu_f64_ksref.hip", "tu_f64_kstrue.hip", "tu_f64_generic.hip", "tu_f64_mink.hip", "tu_f32_closed.hip",
-         "tu_f32_generic.hip", "tu_f64_grid.hip", "tu_f32_grid.hip", "tu_f64_grid4.hip", "tu_f32_grid4.hip", "rtgr_misc.hip", "rtgr_aa.hip", "rtgr_shade.hip", "rtgr_emit.hip", "rtgr_observer.hip", "rtgr_lightcurve.hip", "rtgr_spectrum.hip", "rtgr_polarize.hip", "rtgr_orders.hip", "rtgr_context.hip", "rtgr_tables.hip", "rtgr_scene_host.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip",
-         "rtgr_units.hip", "rtgr_grid.hip", "rtgr_frame_host.hip", "rtgr_aa_host.hip", "rtgr_texture_host.hip", "rtgr_emission_host.hip", "rtgr_observer_host.hip", "rtgr_reduce_host.hip", "rtgr_lightcurve_host.hip", "rtgr_spectrum_host.hip", "rtgr_polarization_host.hip", "rtgr_orders_host.hip", "rtgr_abi.hip"]
+         "tu_f32_generic.hip", "tu_f64_grid.hip", "tu_f32_grid.hip", "tu_f64_grid4.hip", "tu_f32_grid4.hip", "tu_transfer_f64.hip", "tu_transfer_f32.hip", "rtgr_misc.hip", "rtgr_aa.hip", "rtgr_shade.hip", "rtgr_emit.hip", "rtgr_observer.hip", "rtgr_lightcurve.hip", "rtgr_spectrum.hip", "rtgr_polarize.hip", "rtgr_orders.hip", "rtgr_context.hip", "rtgr_tables.hip", "rtgr_scene_host.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip",
+         "rtgr_units.hip", "rtgr_grid.hip", "rtgr_frame_host.hip", "rtgr_aa_host.hip", "rtgr_texture_host.hip", "rtgr_emission_host.hip", "rtgr_observer_host.hip", "rtgr_reduce_host.hip", "rtgr_lightcurve_host.hip", "rtgr_spectrum_host.hip", "rtgr_polarization_host.hip", "rtgr_orders_host.hip", "rtgr_transfer_host.hip", "rtgr_abi.hip"]
 # THE list of device headers (csrc/): what every kernel — the library's and a run-time unit's — is made of.  A new device header goes
 # here and into rtgr_units.hip header_hash_of (the C++ build route of a unit, which runs without Python; tests/test_build_checks.py
 # holds the two lists against each other and against the #include lines).
@@ -37,15 +37,16 @@ KERNEL_HEADERS = DEVICE_HEADERS + ["rtgr_packed_f32.hpp"]
 # (rtgr_texture.hpp: the sampler of rtgr_shade.hip only — no run-time unit and no kernel of the trace includes it; likewise
 #  rtgr_emission.hpp, the emitter model of rtgr_emit.hip, rtgr_observer.hpp, the observer camera of rtgr_observer.hip, rtgr_reduce.hpp,
 #  the reduction of a traced frame, and its models rtgr_lightcurve.hpp, the hot spot of rtgr_lightcurve.hip, and rtgr_spectrum.hpp, the
-#  spectra of rtgr_spectrum.hip, and rtgr_polarization.hpp, the Walker-Penrose model of rtgr_polarize.hip, and rtgr_orders.hpp, the argument blocks of rtgr_orders.hip)
-HEADERS = KERNEL_HEADERS + ["rtgr_texture.hpp", "rtgr_emission.hpp", "rtgr_observer.hpp", "rtgr_reduce.hpp", "rtgr_lightcurve.hpp", "rtgr_spectrum.hpp", "rtgr_polarization.hpp", "rtgr_orders.hpp", "rtgr_host.hpp", "rtgr_internal.hpp", "rtgr_pipeline.hpp", "rtgr_isa_audit.hpp", "rtgr_isa_repair.hpp", "rtgr_unit_build.hpp"]
+#  spectra of rtgr_spectrum.hip, and rtgr_polarization.hpp, the Walker-Penrose model of rtgr_polarize.hip, and rtgr_orders.hpp, the argument blocks of rtgr_orders.hip,
+#  and rtgr_transfer.hpp, the flow model and the transfer kernel of tu_transfer_f64.hip / tu_transfer_f32.hip)
+HEADERS = KERNEL_HEADERS + ["rtgr_texture.hpp", "rtgr_emission.hpp", "rtgr_observer.hpp", "rtgr_reduce.hpp", "rtgr_lightcurve.hpp", "rtgr_spectrum.hpp", "rtgr_polarization.hpp", "rtgr_orders.hpp", "rtgr_transfer.hpp", "rtgr_host.hpp", "rtgr_internal.hpp", "rtgr_pipeline.hpp", "rtgr_isa_audit.hpp", "rtgr_isa_repair.hpp", "rtgr_unit_build.hpp"]
 DEPS = [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(HERE, "..", "include", "rtgr.h")]
 OUT = os.path.join(HERE, "librtgr_hip.so")
 OBJ = os.path.join(HERE, "build", "obj")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 LLVM_BIN = os.path.join(os.path.dirname(os.path.realpath(HIPCC)), "..", "lib", "llvm", "bin")
 # no kernel in them: they never need the listing route
-HOST_ONLY_UNITS = ("rtgr_context.hip", "rtgr_tables.hip", "rtgr_scene_host.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip", "rtgr_units.hip", "rtgr_grid.hip", "rtgr_frame_host.hip", "rtgr_aa_host.hip", "rtgr_texture_host.hip", "rtgr_emission_host.hip", "rtgr_observer_host.hip", "rtgr_reduce_host.hip", "rtgr_lightcurve_host.hip", "rtgr_spectrum_host.hip", "rtgr_polarization_host.hip", "rtgr_orders_host.hip", "rtgr_abi.hip")
+HOST_ONLY_UNITS = ("rtgr_context.hip", "rtgr_tables.hip", "rtgr_scene_host.hip", "rtgr_host_pipeline.hip", "rtgr_sharded.hip", "rtgr_hooks.hip", "rtgr_units.hip", "rtgr_grid.hip", "rtgr_frame_host.hip", "rtgr_aa_host.hip", "rtgr_texture_host.hip", "rtgr_emission_host.hip", "rtgr_observer_host.hip", "rtgr_reduce_host.hip", "rtgr_lightcurve_host.hip", "rtgr_spectrum_host.hip", "rtgr_polarization_host.hip", "rtgr_orders_host.hip", "rtgr_transfer_host.hip", "rtgr_abi.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 

@@ -33,7 +33,7 @@
 // emit_kernel, which serves the frame and the hook), so that a pixel and the hook cannot differ in what the compiler fused around it.
 #pragma once
 #include "rtgr_host.hpp"      // (DevEmission: the parameters as the host converted them)
-#include "rtgr_camera.hpp"
+#include "rtgr_tile.hpp"     // (rpow; it brings rtgr_camera.hpp)
 #include "rtgr_texture.hpp"   // (rhypot, rfinite)
 
 namespace rtgr {
@@ -41,9 +41,6 @@ namespace rtgr {
 template <class R> RTGR_DEV R rexpm1(R x);
 template <> RTGR_DEV double rexpm1<double>(double x) { return expm1(x); }
 template <> RTGR_DEV float rexpm1<float>(float x) { return expm1f(x); }
-template <class R> RTGR_DEV R rpow(R x, R p);
-template <> RTGR_DEV double rpow<double>(double x, double p) { return pow(x, p); }
-template <> RTGR_DEV float rpow<float>(float x, float p) { return powf(x, p); }
 
 // g and dg of a stationary scene (a built-in metric or a 3-D grid) at x
 template <class R>

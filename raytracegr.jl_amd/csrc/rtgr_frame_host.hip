@@ -65,6 +65,7 @@ int frame_scratch(DeviceCtx& D, hipStream_t st, bool capturing, const EntryWords
     if (need.state_end) fs.o1.state_end = fs.base + fs.at.state_end;
     if (need.hit32) fs.o1.hit32 = (uint32_t*)(fs.base + fs.at.hit32);
     if (need.status) fs.o1.status = (uint8_t*)(fs.base + fs.at.status);
+    if (need.lambda_end) fs.o1.lambda_end = fs.base + fs.at.lambda_end;
     if (ctr) fs.d_ctr = (rtgr_counters*)fs.base;
     if (ctr || need.list) HIP_TRY(hipMemsetAsync(fs.base, 0, FRAME_HEAD, st));
     return RTGR_OK;

@@ -542,5 +542,67 @@ struct PolStage {
     R* u = nullptr;
     R* aux = nullptr;
 };
+// volume emission (tu_transfer_f64.hip / tu_transfer_f32.hip; include/rtgr.h "volume emission"; the model and the kernels:
+// rtgr_transfer.hpp).  The caller's rtgr_flow as the kernels read it, converted by the host for one scalar type.
+template <class R>
+struct DevFlow {
+    uint32_t emitter, pad;
+    R orbit, j0, kappa, r0, alpha, H, s, r_stop, gain;
+    R weight[3];
+};
+// the transfer kernel's argument block.  Frame mode (ni > 0): a batch of nrows rows of ni pixels — state0 the batch's start states
+// (nrows ni x 8); lambda_end, status (the trace's), rgb (three planes plane_stride apart) and the four optional planes I, tau, tstatus,
+// tsteps already point at the batch's first pixel.  List mode (ni == 0; rtgr_eval_transfer_*): n rays, status and rgb null, s_end
+// (n x 8) optional as well.  counters: the eight words of an rtgr_counters of the transfer pass, or null.
+template <class R>
+struct TransferArgs {
+    const R* state0;
+    const R* lambda_end;
+    const uint8_t* status;
+    R* rgb;
+    R* I;
+    R* tau;
+    uint8_t* tstatus;
+    uint32_t* tsteps;
+    R* s_end;
+    unsigned long long* counters;
+    const ObsFrame<R>* obs;   // null: u_obs is the static observer at the ray's start
+    uint64_t ni, nrows, n, plane_stride;
+    DevScene<R> sc;
+    DevSolver<R> opt;
+    DevFlow<R> fl;
+};
+// the instantiation the scene's (metric, a) selects — the closed right-hand side also under RTGR_METRIC_GENERIC
+template <class R>
+int transfer_launch(const TransferArgs<R>& A, hipStream_t st);
+// the pointwise hook's argument block (rtgr_eval_flow_*): n pairs (state0, state); every output optional
+template <class R>
+struct FlowArgs {
+    const R* state0;
+    const R* state;
+    R* dens;
+    R* omega;
+    R* u_f;
+    R* gfac;
+    R* dtau;
+    R* dI0;
+    const ObsFrame<R>* obs;
+    uint64_t n;
+    DevScene<R> sc;
+    DevFlow<R> fl;
+};
+template <class R>
+int flow_launch(const FlowArgs<R>& A, hipStream_t st);
+// what an observer trace applies to each batch behind its post-trace stage when the call is rtgr_trace_transfer_*: the record, the
+// caller's four planes (whole frames; each may be null) and the device counters of the transfer pass (or null)
+template <class R>
+struct TransferStage {
+    DevFlow<R> fl;
+    R* I = nullptr;
+    R* tau = nullptr;
+    uint8_t* tstatus = nullptr;
+    uint32_t* tsteps = nullptr;
+    rtgr_counters* tctr = nullptr;      // the caller's (host) record: filled behind the call's one synchronisation
+};
 
 }  // namespace rtgr

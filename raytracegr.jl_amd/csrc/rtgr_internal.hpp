@@ -31,6 +31,8 @@
 //                           the two hooks (kernel: rtgr_polarize.hip)
 //   rtgr_orders_host.hip    higher-order disk images: the checks of an rtgr_disk_orders, the chain of legs through the inflated disk and the
 //                           caller's scene, the entry points (kernels: rtgr_orders.hip; argument blocks: rtgr_orders.hpp)
+//   rtgr_transfer_host.hip  volume emission: the checks of an rtgr_flow, the observer trace with the transfer kernel behind each batch, the
+//                           listed-ray and pointwise hooks (kernels: tu_transfer_f64.hip, tu_transfer_f32.hip; model: rtgr_transfer.hpp)
 //   rtgr_abi.hip            the `extern "C"` symbols of include/rtgr.h, each a one-line shim onto rtgr::api::<name> (an _f64 / _f32
 //                           pair: onto rtgr::api::<name><double> / <float>, defined and instantiated in the unit that holds the code)
 //
@@ -187,8 +189,10 @@ int trace_device(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, 
 constexpr size_t FRAME_HEAD = 256, FRAME_OBS = 512;
 // `orders`: what the lists of a higher-order disk image add (rtgr_orders_host.hip): a second index list of n pixels behind the first, and,
 // with orders_state0, the start states of the n rays
-struct FrameNeeds { bool state_end = false, hit32 = false, status = false, list = false, obs = false, orders = false, orders_state0 = false; };
-struct FrameLayout { size_t obs, list, state_end, hit32, status, orders_list, orders_state0, bytes; };
+// `lambda_end`: the end parameters of n rays, which the transfer kernel of volume emission reads (rtgr_transfer_host.hip) — the last block,
+// so every other frame's layout is what it was
+struct FrameNeeds { bool state_end = false, hit32 = false, status = false, list = false, obs = false, orders = false, orders_state0 = false, lambda_end = false; };
+struct FrameLayout { size_t obs, list, state_end, hit32, status, orders_list, orders_state0, lambda_end, bytes; };
 static_assert(sizeof(rtgr_counters) + sizeof(unsigned long long) <= FRAME_HEAD && sizeof(ObsFrame<double>) <= FRAME_OBS, "the head holds them");
 inline FrameLayout frame_layout(uint64_t n, size_t scalar, const FrameNeeds& need) {
     FrameLayout at;
@@ -199,7 +203,8 @@ inline FrameLayout frame_layout(uint64_t n, size_t scalar, const FrameNeeds& nee
     at.status = at.hit32 + (need.hit32 ? align256((size_t)n * sizeof(uint32_t)) : 0);
     at.orders_list = at.status + (need.status ? align256((size_t)n) : 0);
     at.orders_state0 = at.orders_list + (need.orders ? align256((size_t)n * sizeof(uint64_t)) : 0);
-    at.bytes = at.orders_state0 + (need.orders_state0 ? align256((size_t)n * 8 * scalar) : 0);
+    at.lambda_end = at.orders_state0 + (need.orders_state0 ? align256((size_t)n * 8 * scalar) : 0);
+    at.bytes = at.lambda_end + (need.lambda_end ? align256((size_t)n * scalar) : 0);
     return at;
 }
 // the words of an entry point in its refusals: its name ("rtgr_trace_shaded_*"), what it calls its scratch ("shading"), and whether
@@ -269,7 +274,11 @@ template <class R> int observer_resolve(const rtgr_scene* scene, const rtgr_obse
 template <class R>
 int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
                       const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, rtgr_counters* ctr,
-                      hipStream_t st, const PolStage<R>* pol = nullptr);
+                      hipStream_t st, const PolStage<R>* pol = nullptr, const TransferStage<R>* xfer = nullptr);
+// (xfer, may be null: the transfer kernel of volume emission on each batch's window behind everything else — rtgr_trace_transfer_*, with
+// its words in the refusals; its counters sit in the frame scratch's head, FRAME_HEAD_TCTR bytes in)
+constexpr size_t FRAME_HEAD_TCTR = 128;
+static_assert(FRAME_HEAD_TCTR >= sizeof(rtgr_counters) + sizeof(unsigned long long) && FRAME_HEAD_TCTR + sizeof(rtgr_counters) <= FRAME_HEAD, "the head holds both");
 
 // ---- a traced frame of an emitting disk reduced to a table of (F, A, B) rows (rtgr_reduce_host.hip) -----------------------------------
 // The reduction scratch of a stream (StreamState::reduce) in one call, each block 256-aligned and an absent one no bytes.  Pure
@@ -544,6 +553,10 @@ template <class R> int eval_polarization(rtgr_context* ctx, const rtgr_scene* sc
 template <class R> int eval_walker_penrose(rtgr_context* ctx, const rtgr_scene* scene, const R* s, const R* f, uint64_t n, R* kappa);
 template <class R> int trace_orders_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, const R* d_state0, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, R* d_rgb, const rtgr_order_planes* planes, rtgr_counters* ctr, void* stream);
 template <class R> int trace_orders(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, const R* state0, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_disk_orders* ord, R* rgb, const rtgr_order_planes* planes, rtgr_counters* ctr);
+template <class R> int trace_transfer_device(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_flow* flow, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, R* d_I, R* d_tau, uint8_t* d_tstatus, uint32_t* d_tsteps, rtgr_counters* ctr, rtgr_counters* tctr, void* stream);
+template <class R> int trace_transfer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj, const rtgr_shade* shade, const rtgr_disk_emission* emit, const rtgr_flow* flow, R* rgb, const rtgr_ray_outputs* out, R* g, R* I, R* tau, uint8_t* tstatus, uint32_t* tsteps, rtgr_counters* ctr, rtgr_counters* tctr);
+template <class R> int eval_transfer(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_flow* flow, const rtgr_observer* obs, const R* s0, const R* lambda_end, uint64_t n, R* I, R* tau, R* s_end, uint8_t* tstatus, uint32_t* tsteps);
+template <class R> int eval_flow(rtgr_context* ctx, const rtgr_scene* scene, const rtgr_flow* flow, const rtgr_observer* obs, const R* s0, const R* s, uint64_t n, R* dens, R* omega, R* u_f, R* gfac, R* dtau, R* dI0);
 int quantize_device_f64(rtgr_context* ctx, const double* d_rgb, uint64_t ni, uint64_t nj, uint8_t* d_img, void* stream);
 }  // namespace api
 

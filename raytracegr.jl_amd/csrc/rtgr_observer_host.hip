@@ -9,6 +9,7 @@ namespace rtgr {
 constexpr uint64_t OBS_DEFAULT_BATCH = 1ull << 22;   // rays per batch (rtgr_observer.max_batch_rays = 0), as rtgr_aa's
 constexpr EntryWords OBSERVER_WORDS = {"rtgr_trace_observer_*", "observer", true};
 constexpr EntryWords POLARIZED_WORDS = {"rtgr_trace_polarized_*", "observer", true};
+constexpr EntryWords TRANSFER_WORDS = {"rtgr_trace_transfer_*", "observer", true};
 constexpr EntryWords OBSERVER_CANVAS_WORDS = {"rtgr_make_observer_canvas_device_*", "observer", false};
 constexpr const char* OBSERVER_CANVAS = "an observer frame";
 // (its metric must not depend on time through a 4-D grid: stationary_scene)
@@ -78,9 +79,9 @@ static int observer_trace_check(const rtgr_scene* scene, const rtgr_observer* ob
 template <class R>
 int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* opt, const rtgr_observer* obs, uint64_t ni, uint64_t nj,
                       const rtgr_shade* shade, const rtgr_disk_emission* emit, R* d_rgb, const rtgr_ray_outputs* out, R* d_g, rtgr_counters* ctr,
-                      hipStream_t st, const PolStage<R>* pol) {
+                      hipStream_t st, const PolStage<R>* pol, const TransferStage<R>* xfer) {
     int rc;
-    const EntryWords& WORDS = pol ? POLARIZED_WORDS : OBSERVER_WORDS;
+    const EntryWords& WORDS = xfer ? TRANSFER_WORDS : pol ? POLARIZED_WORDS : OBSERVER_WORDS;
     if ((rc = observer_trace_check(scene, obs, ni, nj, emit, d_rgb, out, d_g))) return rc;
     DevObserver<R> ob;
     if ((rc = observer_resolve<R>(scene, obs, ob))) return rc;
@@ -109,13 +110,21 @@ int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* 
     need.obs = true;
     need.state_end = post && !(out && out->state_end);
     need.hit32 = post && !(out && out->hit32);
-    need.status = after.shade && !(out && out->status);
+    need.status = (after.shade || xfer) && !(out && out->status);
+    need.lambda_end = xfer && !(out && out->lambda_end);   // (the transfer kernel integrates each ray as far as the trace went)
     DevScene<R> sc;
+    DevSolver<R> ds;
+    if (xfer && (rc = convert_solver<R>(opt, ds))) return rc;
     FrameScratch fs;
+    unsigned long long* d_tctr = nullptr;
     {
         std::lock_guard<std::mutex> lk(D.mu);
         if ((rc = stationary_scene<R>(D, scene, sc, st, emit ? EMISSION_NEEDS_STATIONARY : OBSERVER_NEEDS_STATIONARY))) return rc;
         if ((rc = frame_scratch(D, st, capturing, WORDS, n, sizeof(R), need, align256((size_t)rows * ni * 8 * sizeof(R)), out, ctr, fs))) return rc;
+        if (xfer && xfer->tctr) {
+            d_tctr = (unsigned long long*)(fs.base + FRAME_HEAD_TCTR);
+            HIP_TRY(hipMemsetAsync(d_tctr, 0, sizeof(rtgr_counters), st));
+        }
     }
     R* d_states = (R*)fs.ss->batch;
     ObsFrame<R>* d_frame = (ObsFrame<R>*)(fs.base + fs.at.obs);
@@ -156,8 +165,26 @@ int trace_observer_on(DeviceCtx& D, const rtgr_scene* scene, const rtgr_solver* 
                 if ((rc = polarize_launch<R>(P, st))) return rc;
             }
         }
+        if (xfer) {   // the same window, the same start states, as far as the trace went: behind every kernel that colours the pixel
+            TransferArgs<R> T;
+            std::memset(&T, 0, sizeof T);
+            T.state0 = d_states; T.lambda_end = (const R*)o1.lambda_end + first; T.status = o1.status + first;
+            T.rgb = d_rgb + first; T.plane_stride = n;
+            T.I = xfer->I ? xfer->I + first : nullptr; T.tau = xfer->tau ? xfer->tau + first : nullptr;
+            T.tstatus = xfer->tstatus ? xfer->tstatus + first : nullptr; T.tsteps = xfer->tsteps ? xfer->tsteps + first : nullptr;
+            T.counters = d_tctr; T.obs = d_frame;
+            T.ni = ni; T.nrows = jb - ja; T.n = m;
+            T.sc = sc; T.opt = ds; T.fl = xfer->fl;
+            std::lock_guard<std::mutex> lk(D.mu);
+            KernelTimer timer(D, st, 0);
+            if ((rc = transfer_launch<R>(T, st))) return rc;
+        }
     }
-    return counters_back(fs, ctr, st);
+    // the end of a call that counts — ONE path for the trace's counters and the transfer pass's: both copies, then one wait
+    if (ctr) HIP_TRY(hipMemcpyAsync(ctr, fs.d_ctr, sizeof *ctr, hipMemcpyDeviceToHost, st));
+    if (d_tctr) HIP_TRY(hipMemcpyAsync(xfer->tctr, d_tctr, sizeof(rtgr_counters), hipMemcpyDeviceToHost, st));
+    if (ctr || d_tctr) HIP_TRY(hipStreamSynchronize(st));
+    return RTGR_OK;
 }
 
 template <class R>
